@@ -29,7 +29,10 @@ How a batch is driven (`--launch`):
       is still taken, for three steps, and reported as `secondary.resident_replay`.
 The VGG16 trunks / FC head are not part of the path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|test] [--ring R] [--batches-per-step M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|test] [--ring R] [--batches-per-step M] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes, after the timed steps, what the path returned for the last batch of the last step (PathDriver.path_outputs)
+as DIR/<name>.npy; the inputs are seeded, so two runs (or two builds) with the same arguments can be compared array for array.
 
 `--gpus N` with N > 1 and no launcher environment re-executes itself under `python -m torch.distributed.run` with one
 rank per GPU (RCCL); under the driver's own torchrun launch the ranks come from RANK / LOCAL_RANK / WORLD_SIZE.  Frames
@@ -51,6 +54,7 @@ import subprocess
 import sys
 import threading
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -60,6 +64,7 @@ import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec
 METRIC = "KITTI-shape frames/sec (RPN+3-view ROI-pool+NMS) at 1/2/4/8 MI355X"
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs: array data in all (the .npy headers stay well inside 64 MB with it)
 
 
 def parse():
@@ -90,6 +95,9 @@ def parse():
     ap.add_argument("--secondary-seconds", type=float, default=1.0, help="minimum timed window of every with-trunk leg (training / serving step variants)")
     ap.add_argument("--secondary-timeout", type=int, default=1500, help="seconds the secondary legs may take before the line is printed without the rest")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one rank per GPU) | gloo (logic tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last batch as DIR/<name>.npy (float32 / "
+                         "float64, <= 64 MB in all: larger arrays as a fixed, seeded sample of their elements); rank 0, --launch path only")
     return ap.parse_args()
 
 
@@ -284,6 +292,32 @@ class PathDriver:
             if capture is not None:
                 capture.append((k0 + i, out))
         self.cursor = k0 + nb
+        if nb > 0:
+            self.last = (k0 + nb - 1, out)                          # (read by path_outputs(); its slot is reused only by a later run)
+
+    def path_outputs(self):
+        """What the caller of the path received for the last batch of the last run(), read back from that batch's slot once the
+        device is idle: the training path's outputs (TrainPathStream.finish) and the RoiPool pair's top / bottom_diff of the three
+        views.  Only rows the path wrote are taken (anchors: n_anchors per frame; ROI rows: the batch's row count).  The pair's
+        argmax plane holds private one-byte codes, no caller's result, so it is left out; top and bottom_diff depend on it."""
+        torch.cuda.synchronize()
+        k, out = self.last
+        d = self.bufs[k % self.depth]
+        St = out["rois"]["bev"].shape[0]
+        h = lambda t: t.cpu().numpy()
+        na = h(out["n_anchors"])
+        bv, img, b3, _, _ = out["proposals"]
+        arrays = {"proposals_bv": h(bv), "proposals_img": h(img), "proposals_3d": h(b3),
+                  "num_proposals": np.asarray(out["num_proposals"], np.float64),
+                  "rpn_labels": h(out["rpn_labels"]), "rpn_targets": h(out["rpn_targets"]),
+                  "anchors": np.concatenate([h(out["anchors"][b, :n]) for b, n in enumerate(na)]),
+                  "anchors_3d": np.concatenate([h(out["anchors_3d"][b, :n]) for b, n in enumerate(na)]),
+                  "rois_3d": h(out["rois_3d"]), "labels": h(out["labels"]).astype(np.float64), "bbox_targets": h(out["bbox_targets"])}
+        for v in self.views:
+            arrays["rois_" + v] = h(out["rois"][v])
+            arrays["top_" + v] = h(d[v][0][:St])
+            arrays["bottom_diff_" + v] = h(d[v][3])
+        return k, arrays
 
     def in_flight_us(self, nb=64):
         """average duration of the RoiPool forward / backward calls as the timed loop runs them: `depth` batches in flight, HIP
@@ -694,6 +728,28 @@ def fresh_inputs_line(rank, variant, seconds=1.5, depth=3, nstreams=3):
                      "is the reference's subsampling contract; one process draws for one GPU"}
 
 
+def write_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 kept, any other type as float64, `budget` bytes of data in all.
+    The arrays are served smallest first, each up to an even share of what is left; one that does not fit whole is written as a
+    sample of its flattened elements at positions drawn by a RandomState seeded with its name (sorted), so that two runs or two
+    builds with the same shapes write the same positions.  Returns {name: {"shape", "elements_written"}}."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (np.asarray(kv[1]).size, kv[0]))
+    left, info = budget, {}
+    for i, (name, a) in enumerate(items):
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+        keep = min(a.size, left // (len(items) - i) // a.itemsize)
+        shape = list(a.shape)
+        if keep < a.size:
+            pos = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        info[name] = {"shape": shape, "elements_written": int(keep)}
+    return info
+
+
 def timed(ring, nbatches, steps, warmup, barrier):
     """-> (wall seconds of the timed region, seconds the host spent enqueueing it, CPU seconds of this PROCESS inside it:
     time.process_time() = user + system time of every thread, the submitting thread and the library's helper thread alike)"""
@@ -786,9 +842,16 @@ def main():
         # (8: the runtime multiplexes streams onto 4 hardware queues -- 4 / 6 / 10 streams measured 12.2 - 12.7 k frames/s, 8 / 12 / 16
         # 13.6 - 13.75 k; GPU_MAX_HW_QUEUES=8 is slower)
         args.streams = 8 if args.launch == "path" else 3
+    if args.dump_outputs and not (wl == "train" and args.launch == "path"):
+        raise SystemExit("bench.py: --dump-outputs reads the training path's driver: --workload train --launch path only (here: %s, %s)"
+                         % (wl, args.launch))
     streams = [torch.cuda.Stream() for _ in range(max(1, min(args.streams, 3) if args.launch == "path" else args.streams))]
     ring = Ring(args, rank, wl, batch, ring_n, streams)
     dt, t_enq, cpu_s = timed(ring, nb, args.steps, args.warmup, barrier)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        k_last, arrays = ring.driver.path_outputs()
+        dumped = {"dir": os.path.abspath(args.dump_outputs), "batch": k_last, "arrays": write_outputs(arrays, args.dump_outputs)}
     host_draws = ring.driver.path.host_seconds if ring.driver is not None else (0.0, 0.0)      # (helper thread: waited, drew) since set-up
     red_dev = "cuda" if args.dist_backend == "nccl" else "cpu"
     dt = sharding.max_over_ranks(dt, dist, device=red_dev)
@@ -825,6 +888,8 @@ def main():
                                       "pinned": host_plan["cores"], "plan": host_plan["note"]}},
         }
         res["config"]["pmc_signature"] = signature
+        if dumped is not None:
+            res["dump_outputs"] = dumped
         # one batch alone on one stream: the latency of the path
         torch.cuda.synchronize()
         t1 = time.perf_counter()

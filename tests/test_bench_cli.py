@@ -100,6 +100,51 @@ def test_bench_line_contract_on_the_gpu():
     assert len(nms) == 2 and all("error" not in e and 0 < e["frac"] <= 1 and e["blocks_visited"] <= e["blocks_total"] for e in nms)
 
 
+def test_dump_outputs_stay_in_budget_and_repeat(bench, tmp_path):
+    """--dump-outputs' writer: float32 stays float32, other types become float64, the data fits the budget, small arrays are written
+    whole, a large one as a sample of its own elements, and the same arrays give the same files"""
+    r = np.random.RandomState(0)
+    arrays = {"labels": np.arange(12, dtype=np.int32).reshape(6, 2), "rois": r.rand(6, 5).astype(np.float32),
+              "top": r.rand(40, 7, 7, 8).astype(np.float32), "bottom_diff": r.rand(2, 9, 9, 8)}
+    budget = 20000
+    info = bench.write_outputs(arrays, str(tmp_path / "a"), budget=budget)
+    bench.write_outputs(arrays, str(tmp_path / "b"), budget=budget)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert sum(a.nbytes for a in got.values()) <= budget
+    assert got["labels"].dtype == np.float64 and np.array_equal(got["labels"], arrays["labels"])
+    assert got["rois"].dtype == np.float32 and np.array_equal(got["rois"], arrays["rois"])
+    assert got["top"].dtype == np.float32 and 0 < got["top"].size < arrays["top"].size
+    assert np.isin(got["top"], arrays["top"]).all() and info["top"] == {"shape": [40, 7, 7, 8], "elements_written": got["top"].size}
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(str(tmp_path / "b" / (n + ".npy")))), n
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_two_runs_are_identical(tmp_path):
+    """`--dump-outputs DIR`: two runs with the same arguments write the same arrays (seeded inputs, the path's draws on the seeded
+    global generator), float32 / float64 only, <= 64 MB in all, the last batch of the last timed step"""
+    runs = []
+    for name in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ring", "4",
+                              "--batches-per-step", "5", "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(tmp_path / name)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dump_outputs"]["batch"] == (1 + 3) * 5 - 1
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(os.listdir(str(tmp_path / "b"))) and len(files) == len(d["dump_outputs"]["arrays"])
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64e6
+    for f in files:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    rows = d["dump_outputs"]["arrays"]["rois_bev"]["shape"][0]
+    assert rows > 0 and d["dump_outputs"]["arrays"]["top_bev"]["shape"] == [rows, 7, 7, 512]
+    assert np.isfinite(np.load(str(tmp_path / "a" / "bottom_diff_rgb.npy"))).all()
+
+
 @pytest.mark.gpu
 def test_path_driver_depth8_equals_the_oracle(bench):
     """the headline's own driver (bench.PathDriver, depth 8: eight batches in flight on eight streams, argument structs at capacity
