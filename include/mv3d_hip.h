@@ -207,10 +207,9 @@ int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_view *views,
  *                   value to the pixel its code names; a unit is written out whole (no index, no fill, no scratch memory).  The
  *                   views must be the forward's (same order, shapes, scale, ROIs) with the argmax buffers it wrote.  (For a
  *                   foreign argmax plane use mv3d_roi_pool_backward_views: int32 argmax.)
- *   workspace       optional and unused by the pair's own kernels since round 6 (the one-launch backward needs no scratch memory;
- *                   measured against the round-5 index + gather structure behind a workspace: level alone, 3 - 7 % more frames/s
- *                   with eight batches in flight); checked for alignment, handed on to mv3d_roi_pool_backward_views for shapes
- *                   outside the pair's kernels.
+ *   workspace       optional (NULL, 0: none); the pair's own kernels never read it.  Checked for alignment and handed on to
+ *                   mv3d_roi_pool_backward_views for shapes outside the pair's kernels: the plain layout, so
+ *                   mv3d_roi_pool_pair_workspace_bytes returns exactly mv3d_roi_pool_backward_workspace_bytes.
  *   cold_maps       != 0: as mv3d_roi_pool_forward_views_cold.
  * Shapes outside the pair's kernels (C not in {256, 512} / not the same for all views, pooled sizes > 15, a map of more than 65534
  * pixels, an empty view) take the plain forward (int32 argmax) and mv3d_roi_pool_backward_views behind the same entries.

@@ -131,11 +131,10 @@ __device__ __forceinline__ void upd4max(const float4 x, float4 &mv)
 //   bins of <= 255 pixels (every bin of a ROI smaller than ~100 x 100 feature pixels): ONE BYTE per pooled value, 0xFF = "none"
 //       (the reference's -1), in the byte plane at the front of the caller's argmax buffer, [0, N), N = R * PH * PW * C;
 //   larger bins (ROIs far larger than the map): 16-bit codes, 0xFFFF = none, in the escape plane behind it, bytes [N, 3 N).
-// Which plane a bin uses follows from its geometry alone, so the gradient's index knows it (RPC_BIG in a list entry).  3 / 8 of the
-// pair's record bytes (8 -> 5 B per pooled value) are neither written here nor read by the gradient; the index carries the code each
-// candidate pixel has inside each of its bins, so the test `argmax == this pixel` (roi_pooling_op.cc:433) is one compare.
+// Which plane a bin uses follows from its geometry alone, so the gradient (roi_grad_tiles.hip) knows it too.  3 / 8 of the pair's
+// record bytes (8 -> 5 B per pooled value) are neither written here nor read by the gradient; a code names the pixel inside its
+// bin, so the gradient finds the pixel a value goes to (roi_pooling_op.cc:433) without the reference's flat index.
 // mv3d_roi_pool_argmax_decode gives the reference's plane back (tests, bench).
-#define RPC_BIG 0x10000              // list entry: the bin has more than 255 pixels -- its codes are in the 16-bit escape plane
 // the rectangle of bin (ph, pw) of the ROI row rr[5] as roi_pooling_op.cc:139-162 computes it
 __device__ __forceinline__ BinGeom fwd_bin_rect(const float rr[5], const int ph, const int pw, const float scale, const int B, const int H, const int W,
                                                 const int PH, const int PW)
@@ -931,9 +930,7 @@ __global__ __launch_bounds__(256) void roi_bwd_index_kernel(RoiGradPack p, RoiGr
 // lane in flight
 template <int CPL> struct BwdVec;
 template <> struct BwdVec<1> { typedef unsigned int T; static __device__ __forceinline__ T ld(__amdgpu_buffer_rsrc_t r, int v, int s) { return __builtin_amdgcn_raw_buffer_load_b32(r, v, s, 0); } };
-template <> struct BwdVec<2> { typedef unsigned int T __attribute__((ext_vector_type(2))); static __device__ __forceinline__ T ld(__amdgpu_buffer_rsrc_t r, int v, int s) { return __builtin_amdgcn_raw_buffer_load_b64(r, v, s, 0); } };
-template <> struct BwdVec<4> { typedef unsigned int T __attribute__((ext_vector_type(4))); static __device__ __forceinline__ T ld(__amdgpu_buffer_rsrc_t r, int v, int s) { return __builtin_amdgcn_raw_buffer_load_b128(r, v, s, 0); } };
-template <int CPL> __device__ __forceinline__ unsigned bwd_elem(const typename BwdVec<CPL>::T &x, int j) { return x[j]; }
+template <int CPL> __device__ __forceinline__ unsigned bwd_elem(const typename BwdVec<CPL>::T &x, int j);
 template <> __device__ __forceinline__ unsigned bwd_elem<1>(const unsigned int &x, int) { return x; }
 
 template <int CPL, int W, bool MASKED>
@@ -958,14 +955,16 @@ __device__ __forceinline__ void bwd_drain_lanes(const int cur, const int u0, con
 
 // A persistent grid; wave = (item, slice of 64 CPL channels).  XCD x (= blockIdx % 8) works on slice x % nsl of the items of
 // part x / nsl (the item list is in pixel order: a part is a band of rows / frames), so that every record slice is pulled
-// into ONE private L2.  CPL > 1 makes the pieces a slice reads from a record larger (64 CPL x 4 B: 256 B at CPL = 1, 1 KB at
-// CPL = 4): cold HBM reads of 256-B pieces scattered at 2 KB stride run at ~3 TB/s (DRAM row misses), the same bytes in
-// larger pieces do not.  A wave walks its items i, i + stride, ... software-pipelined: while item n's records are in flight,
+// into ONE private L2.  A wave walks its items i, i + stride, ... software-pipelined: while item n's records are in flight,
 // the offsets of item n + 1 and the header of item n + 2 are already requested.
+// CPL = 1 only: 64-channel slices, 256-B pieces of a record per wave.  Wider pieces (2 / 4 channels per lane, 512 B / 1 KB) were
+// measured slower on the training batch, 82 / 105 us against 75 for the three launches: the walk is bound by its dependent round
+// trips, and a lane with more channels holds fewer records in flight.
 template <int CPL>
 __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const RoiGradIdxPack &ix, const int nsl, const unsigned vblock,
                                                      const unsigned vgrid)
 {
+    static_assert(CPL == 1, "one channel per lane: the loads, the window W and the store below are that width's");
     const int lane = threadIdx.x & 63;
     const int xcd = (int)(vblock & 7);
     const int slice = xcd % nsl, part = xcd / nsl, nparts = 8 / nsl;
@@ -988,7 +987,7 @@ __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const
     int idx = ix.pool[it.y + min(lane, it.z - 1)];
     if (tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) tr[2] = (long long)__builtin_readcyclecounter(); }
     const int voff = lane * 4 * CPL;
-    constexpr int W = CPL == 1 ? 32 : (CPL == 2 ? 16 : 8);
+    constexpr int W = 32;
     for (; i < i_end; i += stride) {
         const int pix = __builtin_amdgcn_readfirstlane(it.x), off = __builtin_amdgcn_readfirstlane(it.y);
         const int cnt = __builtin_amdgcn_readfirstlane(it.z), k = __builtin_amdgcn_readfirstlane(it.w);
@@ -1017,16 +1016,13 @@ __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const
             const int m = min(64, cnt - t0);
             int u0 = 0;
             for (; u0 + W <= m; u0 += W) bwd_drain_lanes<CPL, W, false>(cur, u0, m, ra, rt, voff, want, a);
-            if (W > 8 && u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
-            if (W > 16 && u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
-            if (W > 16 && u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
             if (u0 + 4 <= m) { bwd_drain_lanes<CPL, 4, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 4; }
             if (u0 < m) bwd_drain_lanes<CPL, 4, true>(cur, u0, m, ra, rt, voff, want, a);
         }
-        float *out = v.bottom_diff + (long long)pix * C + c;
-        if (CPL == 1) __builtin_nontemporal_store(a[0], out);
-        else if (CPL == 2) { typedef float f2v __attribute__((ext_vector_type(2))); const f2v av = {a[0], a[1 % CPL]}; __builtin_nontemporal_store(av, reinterpret_cast<f2v *>(out)); }
-        else { typedef float f4v __attribute__((ext_vector_type(4))); const f4v av = {a[0], a[1 % CPL], a[2 % CPL], a[3 % CPL]}; __builtin_nontemporal_store(av, reinterpret_cast<f4v *>(out)); }
+        __builtin_nontemporal_store(a[0], v.bottom_diff + (long long)pix * C + c);
         it = nxt; idx = idx1;
         if (tr) { if (n_done == 0) t_first = (long long)__builtin_readcyclecounter(); ++n_done; n_cand += cnt; }
     }
@@ -1043,427 +1039,9 @@ __global__ __launch_bounds__(256) void roi_bwd_gather_kernel(RoiGradPack p, RoiG
 // The PAIR (mv3d_roi_pool_forward_views_pair / mv3d_roi_pool_backward_views_pair): RoiPool and its gradient with a private
 // argmax plane of one-byte codes between them (16-bit codes for bins of more than 255 pixels: COMPACT above).
 //
-//   forward          the XCD-sliced pooling kernels above with COMPACT codes: 5 instead of 8 bytes per pooled value are written.
-//   backward, launches 1 + 2  one workgroup per 16-pixel segment of a map row, as the plain indexed RoiPoolGrad above: SIZES
-//                    (filter the ROIs by frame, row, column span; an upper bound of every pixel's list: all bins the reference's
-//                    test lets through), then LISTS (slab offsets = plain sums over the preceding segments' sizes -- the sizing
-//                    launch is complete -- items, and the candidate lists themselves); the LISTS launch zero-fills the pixels
-//                    WITHOUT an item under its latency chain (the ROI and size loads are issued BEFORE the fill's stores: a load's wait would
-//                    otherwise wait for every older store as well).  No atomics, no state that has to be zero on entry.
-//   candidate lists  entries {record byte offset into top_diff, code of THIS pixel inside THAT bin} in the reference's order
-//                    roi -> ph -> pw; only bins whose forward rectangle [hstart, hend) x [wstart, wend) (roi_pooling_op.cc:153-162)
-//                    contains the pixel are listed: the forward scans nothing else, so a bin outside of which the pixel lies can
-//                    never name it (roi_pooling_op.cc:433 is false for it whatever top_diff holds) -- and a bin that covers the
-//                    pixel without passing the reference's candidate test (:401-431: the test uses the UNCLAMPED rounded ROI, a
-//                    last bin's ceil() may reach one pixel past it) stays out, as the reference leaves it out.
-//   backward, launch 3  the gather sums each candidate pixel's records in list order (= the reference's f32 summation order): per
-//                    record one code byte + one f32 per lane, `code == this pixel's code ? top_diff : +0`, and writes the pixel.
-// Bit-identical to the plain entries (tests/test_roi_pair.py).  Measured and dropped in round 5 (tools/experiments/
-// roi_pair_index_in_forward_r05.hip.txt, profiles/r05_c_*, r05_d_*): the index built by workgroups INSIDE the forward launch
-// (forward 39 -> 56 us: latency-bound workgroups under a write-saturated memory system), and a single-pass index with a look-back
-// over agent-scope words (38 - 49 us for the launch: 1744 workgroups x ~870 predecessor words through the memory side).
-// header words of the workspace (ints): [1] number of items
-struct RoiPairIdx {
-    int4 *items; int2 *pool; int *header; int *seg_tot, *seg_mask;
-    unsigned first_block[MV3D_MAX_ROI_VIEWS]; int gpr[MV3D_MAX_ROI_VIEWS];
-    unsigned nseg;
-    int nslots;                                      // item slots (one per pixel of every view)
-    int dbg;                                         // experiment builds (MV3D_TUNING): parts of the index launches switched off, 0 otherwise
-    long long *trace;                                // experiment builds: 8 cycle stamps per workgroup of the lists launch (tools/roi_idx_trace.py)
-};
-
-struct RoiPairShared {
-    int red[8];
-    int roi[BW_CHUNK], rsw[BW_CHUNK], rew[BW_CHUNK], rsh[BW_CHUNK], prow[BW_CHUNK];
-    float bw[BW_CHUNK], bh[BW_CHUNK];
-    unsigned char nb[BW_CHUNK][BWI_PIX], xr[BW_CHUNK][BWI_PIX];
-    int wcnt[4], cnt[BWI_PIX], base[BWI_PIX], run[BWI_PIX];
-    int part[16][BWI_PIX];
-    int last;
-};
-
-// The forward's rectangle of a bin is a product of a row range and a column range (roi_pooling_op.cc:153-162), and so is the
-// reference's candidate set of a pixel (:423-431), so the listed bins of pixel (h, w) under one ROI are [pa, pb) x [qa, qb): the
-// bins ph of the reference's range whose rows hstart(ph) <= h < hend(ph) contain the pixel's row -- a contiguous run, the bins being
-// ordered -- times the same for the columns.  The row run is found once per (ROI, segment) by the thread that filters the ROI, the
-// column run once per (ROI, pixel); a bin's code is then (h - hstart(ph)) * (wend(pw) - wstart(pw)) + (w - wstart(pw)).
-__device__ __forceinline__ int roi_pair_lo(const int p, const float bin, const int start, const int limit)
-{
-    return min(max((int)floorf(__fmul_rn((float)p, bin)) + start, 0), limit);        // hstart / wstart as roi_pool_fwd_xcd_block computes them
-}
-__device__ __forceinline__ int roi_pair_hi(const int p, const float bin, const int start, const int limit)
-{
-    return min(max((int)ceilf(__fmul_rn((float)(p + 1), bin)) + start, 0), limit);    // hend / wend
-}
-// the run [a, b) of bins of [p0, p1) whose extent contains coordinate x; packed a | b << 8 (a == b: none)
-__device__ __forceinline__ int roi_pair_run(const int p0, const int p1, const float bin, const int start, const int limit, const int x)
-{
-    int a = p1, b = p1;
-    for (int p = p0; p < p1; ++p) {
-        const bool in = x >= roi_pair_lo(p, bin, start, limit) && x < roi_pair_hi(p, bin, start, limit);
-        if (in && a == p1) a = p;
-        if (!in && a != p1) { b = p; break; }
-    }
-    return a | (b << 8);
-}
-
-// FILL = false: sizes -- the UNPRUNED number of candidate bins of every pixel (an upper bound of its list, cheap: no per-bin
-// arithmetic) and the mask of pixels that have any; FILL = true: offsets, items, the pruned lists with their codes.
-template <bool FILL>
-__device__ __forceinline__ void roi_pair_index_block(RoiPairShared &S, const RoiGradPack &p, const RoiPairIdx &ix, const unsigned block)
-{
-    const unsigned nblocks = ix.nseg;
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && block >= ix.first_block[j]) k = j;
-    const RoiGradViewDev &v = p.v[k];
-    const int PH = p.PH, PW = p.PW, H = v.H, W = v.W, R = v.R, C = v.C;
-    const unsigned g = block - ix.first_block[k];
-    const int gpr = ix.gpr[k];
-    const int w0 = (int)(g % (unsigned)gpr) * BWI_PIX;
-    const int npx = min(BWI_PIX, W - w0);
-    const unsigned gh = g / (unsigned)gpr;
-    const int h = (int)(gh % (unsigned)H), n = (int)(gh / (unsigned)H);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = threadIdx.x & (BWI_PIX - 1), q = threadIdx.x / BWI_PIX;      // pixel of the segment, entry stripe
-    const int npass = (R + BW_CHUNK - 1) / BW_CHUNK;
-    const long long pix0 = ((long long)n * H + h) * W + w0;
-    long long *tr = (FILL && ix.trace) ? ix.trace + 8 * (long long)block : nullptr;
-#define RPI_STAMP(K) do { if (tr && threadIdx.x == 0) tr[K] = (long long)__builtin_readcyclecounter(); } while (0)
-    RPI_STAMP(0);
-    // (lists) the pixels the sizing launch gave an item (upper bound > 0): the FIRST request of the workgroup -- the fill below skips
-    // those pixels and should not have to wait for the younger requests as well
-    unsigned my_mask = 0;
-    if (FILL) my_mask = (unsigned)ix.seg_mask[block];
-    // the first pass's ROI of this thread: requested BEFORE the fill's stores (a wait for a load also waits for every older store)
-    float r0[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if ((int)threadIdx.x < R) {
-        const float *roi = v.rois + 5 * (long long)threadIdx.x;
-#pragma unroll
-        for (int u = 0; u < 5; ++u) r0[u] = roi[u];
-    }
-    // (lists) the segment's slab and item offsets = sums over the preceding segments' sizes: requested before the fill as well
-    int a = 0, b = 0;
-    if (FILL) {
-        // (seg_tot holds candidates << 5 | pixels with any; eight words per thread requested together: summed one word at a time the
-        // loop was a chain of dependent round trips -- ~2 us each -- at the head of every workgroup)
-        for (int t0 = 0; t0 < ((ix.dbg & 2) ? 0 : (int)block); t0 += 256 * 8) {
-            int pk[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = t0 + u * 256 + (int)threadIdx.x;
-                pk[u] = t < (int)block ? ix.seg_tot[t] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { a += pk[u] >> 5; b += pk[u] & 31; }
-        }
-    }
-    if (FILL && !(ix.dbg & 1)) {    // the pixels of the segment WITHOUT an item become zeros here (every item's pixel is written by the
-        // gather, an empty pruned list as +0): the list launch is a ~15 us chain of barriers, LDS round trips and little memory traffic,
-        // the ~40 MB of streaming stores ride under it (the sizing launch is short and stays short without them).  npx * C floats
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        const f4v z = {0.0f, 0.0f, 0.0f, 0.0f};
-        f4v *dst = reinterpret_cast<f4v *>(v.bottom_diff + pix0 * C);
-        const int n4 = npx * (C / 4), psh = C == 512 ? 7 : 6;          // (the pair takes C = 256 | 512: roi_pair_shapes)
-        const unsigned skip = (ix.dbg & 16) ? 0u : my_mask;            // (dbg 16, experiment builds: zero every pixel as before)
-        for (int t = threadIdx.x; t < n4; t += 256)
-            if (!((skip >> (t >> psh)) & 1u)) __builtin_nontemporal_store(z, dst + t);
-    }
-    if (threadIdx.x < BWI_PIX) { S.cnt[threadIdx.x] = 0; S.run[threadIdx.x] = 0; }
-    int nlist = 0;
-
-    // filter one pass of ROIs into the ordered LDS list (roi_pooling_op.cc:392-403, :423-426 for the rows), then count every
-    // (entry, pixel) pair's bins: all the reference's test lets through (sizes), or the ones the lists will hold (lists)
-    auto build = [&](const int pass) -> int {
-        __syncthreads();
-        const int r = pass * BW_CHUNK + (int)threadIdx.x;
-        bool ok = false;
-        int rsw = 0, rew = 0, rsh = 0, prow = 0;
-        float bw = 1.0f, bh = 1.0f;
-        if (r < R) {
-            float rr[5];
-            if (pass == 0) {
-#pragma unroll
-                for (int u = 0; u < 5; ++u) rr[u] = r0[u];
-            } else {
-                const float *roi = v.rois + 5 * (long long)r;
-#pragma unroll
-                for (int u = 0; u < 5; ++u) rr[u] = roi[u];
-            }
-            const RoiGeom t = roi_geom(rr, v.scale);
-            ok = ((int)rr[0] == n) && h >= t.rsh && h <= t.reh && t.rew >= w0 && t.rsw < w0 + npx;
-            if (ok) {
-                const int rh = max(t.reh - t.rsh + 1, 1), rw = max(t.rew - t.rsw + 1, 1);
-                bh = (float)rh / (float)PH;
-                int phs = (int)floorf((float)(h - t.rsh) / bh), phe = (int)ceilf((float)(h - t.rsh + 1) / bh);
-                phs = min(max(phs, 0), PH); phe = min(max(phe, 0), PH);
-                ok = phe > phs;
-                rsw = t.rsw; rew = t.rew; rsh = t.rsh; prow = phs | (phe << 8);
-                bw = (float)rw / (float)PW;
-                if (FILL && ok && !(ix.dbg & 8)) { // the lists hold only the bins whose forward rows contain h
-                    prow = roi_pair_run(phs, phe, bh, rsh, H, h);
-                    ok = (prow >> 8) > (prow & 255);
-                }
-            }
-        }
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) S.wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int pos = __popcll(bal & ((1ull << lane) - 1ull));
-        int nl = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { const int cw = S.wcnt[t]; if (t < wave) pos += cw; nl += cw; }
-        if (ok) { S.roi[pos] = r; S.rsw[pos] = rsw; S.rew[pos] = rew; S.rsh[pos] = rsh; S.prow[pos] = prow; S.bw[pos] = bw; S.bh[pos] = bh; }
-        __syncthreads();
-        int local = 0;
-        const int w = w0 + j;
-        for (int e = q; e < nl; e += 256 / BWI_PIX) {
-            int nb = 0, xr = 0;
-            const int xs = S.rsw[e], xe = S.rew[e];
-            if (j < npx && w >= xs && w <= xe) {
-                const float fbw = S.bw[e];
-                int x0 = (int)floorf((float)(w - xs) / fbw), x1 = (int)ceilf((float)(w - xs + 1) / fbw);      // :425-426
-                x0 = min(max(x0, 0), PW); x1 = min(max(x1, 0), PW);
-                if (x1 > x0) {
-                    const int pr = S.prow[e];
-                    if (FILL && !(ix.dbg & 8)) {    // ... and whose forward columns contain w
-                        const int run = roi_pair_run(x0, x1, fbw, xs, W, w);
-                        x0 = run & 255; x1 = run >> 8;
-                    }
-                    nb = ((pr >> 8) - (pr & 255)) * (x1 - x0);
-                    xr = x0 | (x1 << 4);
-                }
-            }
-            if (FILL) { S.nb[e][j] = (unsigned char)nb; S.xr[e][j] = (unsigned char)xr; }
-            local += nb;
-        }
-        if (local) atomicAdd(&S.cnt[j], local);
-        return nl;
-    };
-
-    if (!FILL) {
-        for (int pass = 0; pass < npass; ++pass) nlist = build(pass);
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int c = (lane < BWI_PIX) ? S.cnt[lane] : 0;
-            int tot = c;
-#pragma unroll
-            for (int m = 1; m < BWI_PIX; m <<= 1) tot += __shfl_xor(tot, m);
-            const unsigned mask = (unsigned)(__ballot(c > 0) & 0xffffull);
-            if (lane == 0) { ix.seg_tot[block] = (tot << 5) | __popc(mask); ix.seg_mask[block] = (int)mask; }
-        }
-        return;
-    }
-    // ---- lists
-    RPI_STAMP(1);
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) { a += __shfl_xor(a, m); b += __shfl_xor(b, m); }
-    RPI_STAMP(2);                                     // (the prefix words have arrived)
-    if (lane == 0) { S.red[wave] = a; S.red[4 + wave] = b; }
-    // the pruned counts of every pass: a pixel's list is written pass after pass, its length is known after the last one
-    if (npass == 1) nlist = build(0);
-    else {
-        // (R > 256: the pixel counts of all passes first, then the passes again for the lists -- rare on this path)
-        for (int pass = 0; pass < npass; ++pass) nlist = build(pass);
-    }
-    __syncthreads();
-    if (npass == 1 && nlist == 0 && my_mask == 0u) {  // no ROI touches the segment (half of them): no item, nothing to list
-        if (threadIdx.x == 0 && block == nblocks - 1) {
-            int bt = 0;
-            for (int u = 0; u < 4; ++u) bt += S.red[4 + u];
-            ix.header[1] = bt;                        // (the sizing launch gave this segment no item either)
-        }
-        return;
-    }
-    RPI_STAMP(3);                                     // (filter + counts done)
-    if (tr && threadIdx.x == 0) tr[7] = nlist;
-    if (threadIdx.x < 64) {                      // upper-bound slab offsets of the segment's pixels come from the SIZES launch's rule
-        const int base0 = S.red[0] + S.red[1] + S.red[2] + S.red[3], ibase = S.red[4] + S.red[5] + S.red[6] + S.red[7];
-        // this pixel's slab: the unpruned counts are not kept, so the pixels share the segment's slab in pixel order by their PRUNED
-        // counts (pruned <= unpruned, pixel by pixel: the slab is never overrun)
-        const int c = (lane < BWI_PIX) ? S.cnt[lane] : 0;
-        int inc = c;
-#pragma unroll
-        for (int m = 1; m < BWI_PIX; m <<= 1) { const int t = __shfl_up(inc, m); if (lane >= m) inc += t; }
-        const bool has = lane < BWI_PIX && ((my_mask >> lane) & 1u);
-        const unsigned long long ne = __ballot(has);
-        if (lane < BWI_PIX) S.base[lane] = base0 + inc - c;
-        // an item per pixel the sizing launch counted (its list may turn out empty: count 0, the gather then writes the zero again)
-        // (dbg 32 / 64, experiment builds: lists cut to 32 / 8 entries -- wrong sums, the gather's time without its long items)
-        const int cc = (ix.dbg & 32) ? min(c, 32) : ((ix.dbg & 64) ? min(c, 8) : c);
-        if (has) ix.items[ibase + __popcll(ne & ((1ull << lane) - 1ull))] = make_int4((int)(pix0 + lane), base0 + inc - c, cc, k);
-        if (lane == 0 && block == nblocks - 1) ix.header[1] = ibase + __popcll(ne);        // number of items of the launch
-    }
-    __syncthreads();
-    for (int pass = 0; pass < npass; ++pass) {
-        if (npass > 1) { nlist = build(pass); }
-        __syncthreads();
-        // per pixel: where each entry's bins go = an exclusive prefix of nb over the entries: 16 stripes of consecutive entries per
-        // pixel (thread = (stripe, pixel)), stripe sums, a prefix over the stripes, then the thread walks its own entries
-        const int sp = threadIdx.x & (BWI_PIX - 1), st = threadIdx.x / BWI_PIX;       // pixel, stripe
-        const int L = (nlist + 15) / 16, e0 = st * L, e1 = min(nlist, e0 + L);
-        int sum = 0;
-        for (int e = e0; e < e1; ++e) sum += S.nb[e][sp];
-        S.part[st][sp] = sum;
-        __syncthreads();
-        int run = S.run[sp];
-        for (int t = 0; t < st; ++t) run += S.part[t][sp];
-        int2 *dst = ix.pool + S.base[sp] + run;
-        for (int e = e0; e < ((ix.dbg & 4) ? e0 : e1); ++e) {
-            if (S.nb[e][sp] == 0) continue;
-            const int xr = S.xr[e][sp], pr = S.prow[e], ys = S.rsh[e], xs = S.rsw[e];
-            const float fbh = S.bh[e], fbw = S.bw[e];
-            const int rec0 = S.roi[e] * PH * PW, w = w0 + sp;
-            const int qa = xr & 15, ncols = (xr >> 4) - qa;
-            // (a tiny ROI -- far objects on the 8 x 64 front-view map -- puts all PH x PW bins on one pixel: up to 49 entries per (ROI,
-            // pixel), and such segments are the launch's long pole.  The columns' start / width are the same for every row of bins:
-            // up to eight of them are kept in registers, so that an entry costs a multiply-add and a store)
-            if (ncols <= 8) {
-                int cw[8], cd[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int pw = min(qa + u, PW - 1);
-                    const int ws = roi_pair_lo(pw, fbw, xs, W);
-                    cw[u] = roi_pair_hi(pw, fbw, xs, W) - ws;
-                    cd[u] = w - ws;
-                }
-                for (int ph = pr & 255; ph < (pr >> 8); ++ph) {
-                    const int hs = roi_pair_lo(ph, fbh, ys, H), bhgt = roi_pair_hi(ph, fbh, ys, H) - hs;
-                    const int dh = h - hs, rb = (rec0 + ph * PW + qa) * C * 4;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (u < ncols) dst[u] = make_int2(rb + u * C * 4, (dh * cw[u] + cd[u]) | (bhgt * cw[u] > 255 ? RPC_BIG : 0));
-                    dst += ncols;
-                }
-            } else {
-                for (int ph = pr & 255; ph < (pr >> 8); ++ph) {
-                    const int hs = roi_pair_lo(ph, fbh, ys, H), bhgt = roi_pair_hi(ph, fbh, ys, H) - hs, dh = h - hs;
-                    for (int pw = qa; pw < qa + ncols; ++pw) {
-                        const int ws = roi_pair_lo(pw, fbw, xs, W), we = roi_pair_hi(pw, fbw, xs, W);
-                        *dst++ = make_int2((rec0 + ph * PW + pw) * C * 4, (dh * (we - ws) + (w - ws)) | (bhgt * (we - ws) > 255 ? RPC_BIG : 0));
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (st == 15) S.run[sp] = run + sum;                         // (the last stripe ends at the pass's total)
-    }
-    RPI_STAMP(4);
-#undef RPI_STAMP
-}
-
-// the gather of the pair: wave = (item, 64-channel slice) as roi_bwd_gather_block; per record one code byte and one f32 per lane
-template <int W, bool MASKED>
-__device__ __forceinline__ void roi_pair_drain(const int cur_o, const int cur_k, const int u0, const int m, const __amdgpu_buffer_rsrc_t rc,
-                                               const __amdgpu_buffer_rsrc_t rt, const int lane, float &a)
-{
-    unsigned char cd[W];
-    float td[W];
-    int sk[W];
-#pragma unroll
-    for (int u = 0; u < W; ++u) {
-        const int l = MASKED ? min(u0 + u, 63) : u0 + u;
-        const int so = __builtin_amdgcn_readlane(cur_o, l);
-        sk[u] = __builtin_amdgcn_readlane(cur_k, l);
-        cd[u] = __builtin_amdgcn_raw_buffer_load_b8(rc, lane, so >> 2, 0);
-        td[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rt, lane * 4, so, 0));
-    }
-#pragma unroll
-    for (int u = 0; u < W; ++u)
-        if (!MASKED || u0 + u < m) a += ((int)cd[u] == sk[u]) ? td[u] : 0.0f;
-}
-// a batch of entries with bins of more than 255 pixels among them (ROIs far larger than the map: rare): entry by entry, each from
-// its own plane, in the same order
-__device__ __forceinline__ void roi_pair_drain_mixed(const int cur_o, const int cur_k, const int m, const __amdgpu_buffer_rsrc_t rc,
-                                                     const __amdgpu_buffer_rsrc_t rc16, const __amdgpu_buffer_rsrc_t rt, const int lane, float &a)
-{
-    for (int u = 0; u < m; ++u) {
-        const int so = __builtin_amdgcn_readlane(cur_o, u), k = __builtin_amdgcn_readlane(cur_k, u);
-        const int code = (k & RPC_BIG) ? (int)__builtin_amdgcn_raw_buffer_load_b16(rc16, lane * 2, so >> 1, 0)
-                                       : (int)__builtin_amdgcn_raw_buffer_load_b8(rc, lane, so >> 2, 0);
-        const float td = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rt, lane * 4, so, 0));
-        a += (code == (k & 0xffff)) ? td : 0.0f;
-    }
-}
-
-// (Round 5, measured and dropped -- profiles/r05_z_gather_whole_ab.txt: the eight waves of a 512-thread workgroup taking ONE item and a
-// slice each, any workgroup any item -- a record's 2 KB requested by one CU at one time instead of as 256-byte pieces by eight XCDs:
-// RoiPoolGrad 79 - 103 us for grids of 4096 - 512 workgroups against 68 us.  The slices stay on their XCDs.)
-__device__ __forceinline__ void roi_pair_gather_block(const RoiGradPack &p, const RoiPairIdx &ix, const int nsl, const unsigned vblock,
-                                                      const unsigned vgrid)
-{
-    const int lane = threadIdx.x & 63;
-    const int xcd = (int)(vblock & 7);
-    const int slice = xcd % nsl, part = xcd / nsl, nparts = 8 / nsl;
-    const int stride = (int)(vgrid >> 3) * 4;
-    const int i0 = (int)(vblock >> 3) * 4 + (int)(threadIdx.x >> 6);
-    // (eight slices: this wave's first item does not depend on the number of items -- its header is requested together with that
-    // number, one dependent round trip less at the head of every wave; the item array has a slot per pixel, so the read is in bounds)
-    int4 it = make_int4(0, 0, 0, 0);
-    if (nparts == 1) it = ix.items[i0];
-    const int n_all = __builtin_amdgcn_readfirstlane(ix.header[1]);
-    const int per = (n_all + nparts - 1) / nparts;
-    const int i_end = min(n_all, (part + 1) * per);                     // this part's items: [part * per, i_end)
-    int i = part * per + i0;
-    if (i >= i_end) return;
-    const int4 zero4 = make_int4(0, 0, 0, 0);
-    if (nparts != 1) it = ix.items[i];
-    int4 it1 = (i + stride < i_end) ? ix.items[i + stride] : zero4;
-    int2 idx = ix.pool[it.y + max(min(lane, it.z - 1), 0)];       // (a list may be empty: every bin of the pixel pruned)
-    constexpr int W = 32;
-    for (; i < i_end; i += stride) {
-        const int pix = __builtin_amdgcn_readfirstlane(it.x), off = __builtin_amdgcn_readfirstlane(it.y);
-        const int cnt = __builtin_amdgcn_readfirstlane(it.z), k = __builtin_amdgcn_readfirstlane(it.w);
-        const bool more = i + stride < i_end;                              // wave-uniform
-        const int4 nxt = it1;
-        if (i + 2 * stride < i_end) it1 = ix.items[i + 2 * stride];
-        int2 idx1 = make_int2(0, 0);
-        if (more) idx1 = ix.pool[__builtin_amdgcn_readfirstlane(nxt.y) + max(min(lane, __builtin_amdgcn_readfirstlane(nxt.z) - 1), 0)];
-        const RoiGradViewDev &v = p.v[k];
-        const int C = v.C;
-        const int c = slice * 64 + lane;
-        const int2 *cand = ix.pool + off;
-        // the slice lives in the (wave-uniform) base address, the lane in the vector offset, the record's byte offset is the scalar
-        // offset of the load (a quarter of it for the byte plane, half for the escape plane: both in the caller's argmax buffer)
-        const unsigned char *const plane8 = (const unsigned char *)v.argmax;
-        const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void *)(plane8 + slice * 64), 0, 0x7fffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rc16 = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)((const unsigned short *)(plane8 + (long long)v.R * p.PH * p.PW * C) + slice * 64), 0, 0x7fffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)(v.top_diff + slice * 64), 0, 0x7fffffff, 0x00020000);
-        float a = 0.0f;
-        for (int t0 = 0; t0 < cnt; t0 += 64) {
-            const int2 cur = idx;
-            if (t0 + 64 < cnt) idx = cand[min(t0 + 64 + lane, cnt - 1)];
-            const int m = min(64, cnt - t0);
-            if (__ballot((cur.y & RPC_BIG) != 0 && lane < m) != 0ull) {      // (wave-uniform; never taken on the proposal path's ROIs)
-                roi_pair_drain_mixed(cur.x, cur.y, m, rc, rc16, rt, lane, a);
-                continue;
-            }
-            int u0 = 0;
-            for (; u0 + W <= m; u0 += W) roi_pair_drain<W, false>(cur.x, cur.y, u0, m, rc, rt, lane, a);
-            if (u0 + 16 <= m) { roi_pair_drain<16, false>(cur.x, cur.y, u0, m, rc, rt, lane, a); u0 += 16; }
-            if (u0 + 8 <= m) { roi_pair_drain<8, false>(cur.x, cur.y, u0, m, rc, rt, lane, a); u0 += 8; }
-            if (u0 + 4 <= m) { roi_pair_drain<4, false>(cur.x, cur.y, u0, m, rc, rt, lane, a); u0 += 4; }
-            if (u0 < m) roi_pair_drain<4, true>(cur.x, cur.y, u0, m, rc, rt, lane, a);
-        }
-        __builtin_nontemporal_store(a, v.bottom_diff + (long long)pix * C + c);
-        it = nxt; idx = idx1;
-    }
-}
-
-template <bool FILL>
-__global__ __launch_bounds__(256) void roi_pair_index_kernel(RoiGradPack p, RoiPairIdx ix)
-{
-    __shared__ RoiPairShared S;
-    roi_pair_index_block<FILL>(S, p, ix, blockIdx.x);
-}
-
-__global__ __launch_bounds__(256) void roi_pair_gather_kernel(RoiGradPack p, RoiPairIdx ix, int nsl)
-{
-    roi_pair_gather_block(p, ix, nsl, blockIdx.x, gridDim.x);
-}
-
+//   forward   the XCD-sliced pooling kernels above with COMPACT codes: 5 instead of 8 bytes per pooled value are written.
+//   backward  ONE launch of LDS map tiles over the work list the forward launch plans (roi_grad_tiles.hip, roi_grad_plan.h).
+// Bit-identical to the plain entries (tests/test_roi_pair.py).
 
 // the pair's forward: the multi-view pooling kernels with COMPACT argmax codes.  The first eight workgroups of the grid belong to the
 // PLAN of the pair's backward launch (roi_grad_plan.h; eight so that the workgroup -> XCD slice mapping of the pooling workgroups is kept):
@@ -1863,64 +1441,6 @@ static int bwd_index_plan(int num_views, const mv3d_roi_grad_view *views, int PH
     return MV3D_OK;
 }
 
-// the pair's workspace: header | upper-bound sizes per segment | masks per segment | items | pool of {record offset, code} entries
-static size_t roi_pair_workspace_bytes(int num_views, const mv3d_roi_grad_view *views, int PH, int PW)
-{
-    size_t total = MV3D_ALIGN, nseg = 0;
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_grad_view &w = views[k];
-        total += mv3d_align_up((size_t)w.batch_size * w.height * w.width * sizeof(int4));
-        total += mv3d_align_up(bwd_pool_entries(w, PH, PW) * sizeof(int2));
-        nseg += bwd_segments(w);
-    }
-    return total + 2 * mv3d_align_up(nseg * sizeof(int)) + MV3D_ALIGN;
-}
-
-struct RoiPairPlan { RoiGradPack p; RoiPairIdx ix; };
-static int roi_pair_plan(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, void *workspace, RoiPairPlan &pl)
-{
-    BwdOrder o;
-    bwd_order(num_views, views, PH, PW, o);
-    if (o.pool_entries > 0x7fffffffull) return MV3D_ERR_INVALID_ARG;
-    pl.p = o.p;
-    RoiPairIdx &ix = pl.ix;
-    ix = RoiPairIdx{};
-    for (int k = 0; k < MV3D_MAX_ROI_VIEWS; ++k) { ix.first_block[k] = o.first_block[k]; ix.gpr[k] = o.gpr[k]; }
-    char *ws = (char *)workspace;
-    size_t off = MV3D_ALIGN;
-    ix.header = (int *)ws;
-    ix.seg_tot = (int *)(ws + off); off += mv3d_align_up((size_t)o.iblocks * sizeof(int));
-    ix.seg_mask = (int *)(ws + off); off += mv3d_align_up((size_t)o.iblocks * sizeof(int));
-    ix.items = (int4 *)(ws + off); off += mv3d_align_up(o.n_items * sizeof(int4));
-    ix.pool = (int2 *)(ws + off);
-    ix.nseg = o.iblocks;
-    ix.nslots = (int)o.n_items;
-    ix.dbg = 0;
-    ix.trace = nullptr;
-#ifdef MV3D_TUNING
-    ix.dbg = getenv("MV3D_IDX_DBG") ? atoi(getenv("MV3D_IDX_DBG")) : 0;
-    ix.trace = getenv("MV3D_IDX_TRACE") ? (long long *)strtoull(getenv("MV3D_IDX_TRACE"), nullptr, 10) : nullptr;
-#endif
-    return MV3D_OK;
-}
-
-// channels per lane of the gather: 1 (64-channel slices, 256-B pieces of a record per wave) measured best on the training batch:
-// 75 us for the three launches vs 82 (2 channels, 512-B pieces) and 105 (4 channels, 1-KB pieces, 8 records in flight): the
-// walk is bound by its dependent round trips, and a lane with more channels holds fewer records in flight
-static int bwd_gather_cpl(int channels)
-{
-#ifdef MV3D_TUNING                                                     // tuning hooks, experiment builds only
-    static const int cpl_env = getenv("MV3D_BWG_CPL") ? atoi(getenv("MV3D_BWG_CPL")) : 0;
-#else
-    const int cpl_env = 0;
-#endif
-    int cpl = 1;
-    if (cpl_env == 2 && channels % 128 == 0) cpl = 2;
-    if (cpl_env == 4 && channels % 256 == 0) cpl = 4;
-    if (8 % (channels / (64 * cpl)) != 0 || channels / (64 * cpl) > 8) cpl = 0;     // (C = 64 k, k not a divisor of 8)
-    return cpl;
-}
-
 static int bwd_gather_groups()
 {
 #ifdef MV3D_TUNING
@@ -1968,17 +1488,15 @@ extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_v
     const bool indexed = workspace && bwd_index_eligible(num_views, views, pooled_height, pooled_width) &&
                          workspace_bytes >= mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);
     if (indexed) {
+        // the gather's 64-channel slices, one per XCD or XCD group: the slice count divides 8 (C = 64, 128, 256 or 512)
+        const int nsl = views[0].channels / 64;
+        if (nsl > 8 || 8 % nsl != 0) return MV3D_ERR_INVALID_ARG;
         BwdIndexPlan pl;
         const int rc = bwd_index_plan(num_views, views, pooled_height, pooled_width, workspace, pl);
         if (rc != MV3D_OK) return rc;
         hipLaunchKernelGGL(roi_bwd_index_kernel<false>, dim3(pl.iblocks), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
         hipLaunchKernelGGL(roi_bwd_index_kernel<true>, dim3(pl.iblocks), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
-        const int cpl = bwd_gather_cpl(views[0].channels);
-        const dim3 gg((unsigned)(bwd_gather_groups() * 8));
-        if (cpl == 4) hipLaunchKernelGGL(roi_bwd_gather_kernel<4>, gg, dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix, views[0].channels / 256);
-        else if (cpl == 2) hipLaunchKernelGGL(roi_bwd_gather_kernel<2>, gg, dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix, views[0].channels / 128);
-        else if (cpl == 1) hipLaunchKernelGGL(roi_bwd_gather_kernel<1>, gg, dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix, views[0].channels / 64);
-        else return MV3D_ERR_INVALID_ARG;
+        hipLaunchKernelGGL(roi_bwd_gather_kernel<1>, dim3((unsigned)(bwd_gather_groups() * 8)), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix, nsl);
         return mv3d_launch_status();
     }
     RoiGradPack p;
@@ -2009,7 +1527,7 @@ extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_v
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The pair: RoiPool with a private compact argmax plane, RoiPoolGrad = index + zero fill (one launch) and gather (one launch).
+// The pair: RoiPool with a private compact argmax plane, RoiPoolGrad = one launch of LDS map tiles (roi_grad_tiles.hip).
 static void grad_views_of(int num_views, const mv3d_roi_view *views, mv3d_roi_grad_view *g)
 {
     for (int k = 0; k < num_views; ++k) {
@@ -2034,12 +1552,10 @@ static bool roi_pair_shapes(int num_views, const mv3d_roi_grad_view *g, int PH, 
     return true;
 }
 
+// the pair's own kernels use no workspace; shapes outside them hand it on to mv3d_roi_pool_backward_views (the plain layout)
 extern "C" size_t mv3d_roi_pool_pair_workspace_bytes(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width)
 {
-    const size_t plain = mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);      // (validates)
-    if (plain == 0) return 0;
-    const size_t pair = roi_pair_workspace_bytes(num_views, views, pooled_height, pooled_width);
-    return pair > plain ? pair : plain;                   // (shapes outside the pair's kernels use the plain layout in the same buffer)
+    return mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);
 }
 
 extern "C" int mv3d_roi_pool_forward_views_pair(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
@@ -2112,26 +1628,9 @@ extern "C" int mv3d_roi_pool_backward_views_pair(int num_views, const mv3d_roi_g
         return mv3d_roi_pool_backward_views(num_views, views, pooled_height, pooled_width, workspace, workspace_bytes, stream);
     for (int k = 0; k < num_views; ++k)
         if (!aligned16(views[k].bottom_diff) || !aligned16(views[k].top_diff) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
-#ifdef MV3D_TUNING
-    static const int tiles_env = getenv("MV3D_PAIR_TILES") ? atoi(getenv("MV3D_PAIR_TILES")) : -1;
-#else
-    const int tiles_env = -1;
-#endif
-    // ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip) -- with or without a workspace: the round-5
-    // structure behind a workspace (index + zero fill, gather: three launches) is level alone and 3 - 7 % slower in the path, and a
-    // planning launch that cuts the hot tiles costs what it saves (profiles/r06_g).  (Experiment builds, MV3D_PAIR_TILES=0: index + gather.)
-    if (tiles_env != 0)
-        return mv3d_launch_roi_pair_tiles(num_views, views, pooled_height, pooled_width, (hipStream_t)stream);
-    if (!workspace) return MV3D_ERR_WORKSPACE;
-    if (workspace_bytes < roi_pair_workspace_bytes(num_views, views, pooled_height, pooled_width)) return MV3D_ERR_WORKSPACE;
-    RoiPairPlan pl;
-    const int rc = roi_pair_plan(num_views, views, pooled_height, pooled_width, workspace, pl);
-    if (rc != MV3D_OK) return rc;
-    hipLaunchKernelGGL(roi_pair_index_kernel<false>, dim3(pl.ix.nseg), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
-    hipLaunchKernelGGL(roi_pair_index_kernel<true>, dim3(pl.ix.nseg), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
-    hipLaunchKernelGGL(roi_pair_gather_kernel, dim3((unsigned)(bwd_gather_groups() * 8)), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix,
-                       views[0].channels / 64);
-    return mv3d_launch_status();
+    // ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip): the round-5 structure it replaced (index +
+    // zero fill, gather: three launches) was level alone and 3 - 7 % slower in the path (profiles/r06_g)
+    return mv3d_launch_roi_pair_tiles(num_views, views, pooled_height, pooled_width, (hipStream_t)stream);
 }
 
 // The argmax plane a forward of the pair left in `argmax_data` -> the reference's int32 plane (num_rois, PH, PW, C) in `argmax_out`

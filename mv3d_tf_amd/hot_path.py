@@ -265,8 +265,8 @@ class TrainPathBatch:
             self.tops[v], self.top_diff[v], self.bottom_diff[v] = (top, am), td, bd
             fwd[k] = RoiView(m.data_ptr(), self.rois[v].data_ptr(), top.data_ptr(), am.data_ptr(), 0.125, Bm, St, Hm, Wm, Cm)
             bwd[k] = RoiGradView(bd.data_ptr(), self.rois[v].data_ptr(), td.data_ptr(), am.data_ptr(), 0.125, Bm, St, Hm, Wm, Cm)
-        # the RoiPool pair: forward with the private compact argmax plane, backward WITHOUT a workspace = one launch of LDS map tiles
-        # (mv3d_roi_pool_*_views_pair; with a workspace the same entry runs index + zero fill, gather: same bits)
+        # the RoiPool pair: forward with the private compact argmax plane, backward = one launch of LDS map tiles, no workspace
+        # (mv3d_roi_pool_*_views_pair)
         af = (len(self.views), fwd, 7, 7, 1 if self.cold_maps else 0, st)
         ab = (len(self.views), bwd, 7, 7, None, C.c_size_t(0), st)
         self.fwd_fn = L.mv3d_roi_pool_forward_views_pair

@@ -5,7 +5,7 @@ by a small executor, with the hot-path layers bound to libmv3d_hip.so:
     anchor_target_layer + proposal_target_layer_3d (TRAIN)                mv3d_tf_amd.train_path.TrainPathStream: the batched
                                                                           C entries, ONE host round trip per step for the draws
     roi_pool of every view (+ gradient)                                   roi_pooling_layer.roi_pool_views: the library's RoiPool pair
-                                                                          (one launch forward, index + gather backward)
+                                                                          (one launch forward, one launch backward)
     proposal_transform                                                    tuple element 0 ('bv') / 1 ('img')
 
 `forward(feed)` takes B >= 1 frames (B > 1: lists of per-frame ground-truth arrays, im_info (B,3), calib (B,4,12)); the ROI

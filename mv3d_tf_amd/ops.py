@@ -355,29 +355,7 @@ def roi_pool_backward_views(views, pooled_height, pooled_width, outs=None):
     return res
 
 
-# ---- the RoiPool pair of a training step: private compact argmax plane, index + fill and gather behind one backward call
-_PAIR_WS_FREE = {}                 # (device, bytes, stream) -> workspaces whose last user was enqueued on that stream
-
-
-def _stream_key():
-    return int(torch.cuda.current_stream().cuda_stream)
-
-
-def roi_pair_workspace(nbytes, device):
-    """A workspace for mv3d_roi_pool_backward_views_pair (no initialisation needed), recycled through release_roi_pair_workspace.
-    The pool is per STREAM: a released workspace is handed out again only to a call enqueued on the stream its last launches
-    run on (stream order is what makes the reuse safe; another stream could start while they are still running)."""
-    free = _PAIR_WS_FREE.setdefault((str(device), int(nbytes), _stream_key()), [])
-    return free.pop() if free else torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-
-
-def release_roi_pair_workspace(ws):
-    """ws goes back to the pool of the CURRENT stream (call it on the stream the workspace's launches were enqueued on)."""
-    free = _PAIR_WS_FREE.setdefault((str(ws.device), int(ws.numel()), _stream_key()), [])
-    if len(free) < 4:
-        free.append(ws)
-
-
+# ---- the RoiPool pair of a training step: private compact argmax plane, one launch forward, one launch backward
 def roi_pool_forward_views_pair(views, pooled_height, pooled_width, outs=None, cold_maps=False):
     """views as roi_pool_forward_views; one launch.  Returns [(top, argmax_private), ...]: the second tensor is the pair's PRIVATE
     argmax plane (one-byte codes, 16-bit for bins of > 255 pixels, in an int32-shaped buffer for the shapes the pair's kernels take) -- hand it to
@@ -415,9 +393,10 @@ def roi_pool_argmax_decode(views, res, pooled_height, pooled_width):
 
 def roi_pool_backward_views_pair(views, pooled_height, pooled_width, outs=None, workspace=None):
     """views as roi_pool_backward_views, of a roi_pool_forward_views_pair call (the argmax tensors it returned): RoiPoolGrad of all of
-    them behind one call.  workspace = None: a recycled workspace (index + zero fill, gather); a uint8 tensor: that workspace;
-    False: NO workspace -- the entry's single-launch path (map tiles in LDS, csrc/roi_grad_tiles.hip), same results.
-    Returns [bottom_diff, ...]."""
+    them behind one call -- ONE launch of LDS map tiles (csrc/roi_grad_tiles.hip) that needs no workspace.  workspace = None (or
+    False, which callers written against the earlier signature pass): none; a uint8 tensor of mv3d_roi_pool_pair_workspace_bytes
+    bytes: handed to the entry as is, which passes it on to the plain indexed RoiPoolGrad for shapes outside the pair's kernels (same
+    results either way).  Returns [bottom_diff, ...]."""
     arr = (RoiGradView * len(views))()
     res = []
     for k, (top_diff, rois, argmax, shape, scale) in enumerate(views):
@@ -426,17 +405,9 @@ def roi_pool_backward_views_pair(views, pooled_height, pooled_width, outs=None, 
         arr[k] = RoiGradView(out.data_ptr(), rois.data_ptr(), top_diff.data_ptr(), argmax.data_ptr(), float(scale), B,
                              rois.shape[0], H, W, Cc)
         res.append(out)
-    if workspace is False:
-        check(lib().mv3d_roi_pool_backward_views_pair(len(views), arr, pooled_height, pooled_width, None, 0, _stream()),
-              "mv3d_roi_pool_backward_views_pair")
-        return res
-    ws = workspace
-    if ws is None:
-        ws = roi_pair_workspace(lib().mv3d_roi_pool_pair_workspace_bytes(len(views), arr, pooled_height, pooled_width), views[0][0].device)
-    check(lib().mv3d_roi_pool_backward_views_pair(len(views), arr, pooled_height, pooled_width, _ptr(ws), ws.numel(), _stream()),
+    wp, wn = (None, 0) if workspace is None or workspace is False else (_ptr(workspace), workspace.numel())
+    check(lib().mv3d_roi_pool_backward_views_pair(len(views), arr, pooled_height, pooled_width, wp, wn, _stream()),
           "mv3d_roi_pool_backward_views_pair")
-    if workspace is None:
-        release_roi_pair_workspace(ws)        # (stream-ordered reuse: the next call on this stream runs behind these launches)
     return res
 
 

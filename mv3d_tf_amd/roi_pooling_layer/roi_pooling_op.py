@@ -61,7 +61,7 @@ class RoiPoolViewsFunction(torch.autograd.Function):
             if g is None:
                 g = torch.zeros((rois[k].shape[0], ph, pw, shapes[k][3]), dtype=torch.float32, device=rois[k].device)
             views.append((g.contiguous(), rois[k], argmax[k], shapes[k], scale))
-        outs = ops.roi_pool_backward_views_pair(views, ph, pw, workspace=False)   # (one launch, no scratch memory)
+        outs = ops.roi_pool_backward_views_pair(views, ph, pw)   # (one launch, no scratch memory)
         ret = [None, None, None]
         for k in range(n):
             ret += [outs[k], None]

@@ -32,9 +32,19 @@ def gpu():
     return torch, ops
 
 
-# RoiPoolGrad of the pair called with a workspace and without one: since round 6 the same ONE launch of map tiles either way
-# (csrc/roi_grad_tiles.hip; the entry ignores the workspace) -- both call forms stay covered, on garbage-filled scratch memory
+# RoiPoolGrad of the pair called with a garbage-filled workspace and without one: the pair's own kernels (csrc/roi_grad_tiles.hip)
+# never read it; shapes outside them hand it on to the plain backward -- the indexed one with a workspace, the sliced one without
 WS = pytest.mark.parametrize("no_ws", [False, True], ids=["workspace", "no-workspace"])
+
+
+def _pair_workspace(torch, no_ws, shapes, rows):
+    """None for the no-workspace leg; otherwise mv3d_roi_pool_pair_workspace_bytes bytes for maps `shapes` (B, H, W, C) with `rows`
+    ROIs each (7 x 7 bins), filled with garbage"""
+    if no_ws:
+        return None
+    from mv3d_tf_amd._lib import RoiGradView, lib
+    arr = (RoiGradView * len(shapes))(*[RoiGradView(0, 0, 0, 0, 0.125, B, R, H, W, C) for (B, H, W, C), R in zip(shapes, rows)])
+    return torch.randint(0, 255, (lib().mv3d_roi_pool_pair_workspace_bytes(len(shapes), arr, 7, 7),), dtype=torch.uint8, device="cuda")
 
 
 @WS
@@ -46,7 +56,7 @@ def test_config2_pair_equals_plain_entries_and_oracle(gpu, oracle, cold, no_ws):
     B, per = 2, 128
     maps = {k: synth.feature_map(170 + i, H, W, 512, B) for i, (k, (H, W)) in enumerate(VIEWS.items())}
     d_maps = {k: dev(torch, v) for k, v in maps.items()}
-    ws = None
+    ws = _pair_workspace(torch, no_ws, [m.shape for m in maps.values()], [2 * per] * len(maps))
     for it in range(5):
         rois = three_view_rois(oracle, B, per if it != 3 else 37, 900 + 10 * it)          # (one batch with fewer rows)
         d_rois = {k: dev(torch, v) for k, v in rois.items()}
@@ -61,12 +71,6 @@ def test_config2_pair_equals_plain_entries_and_oracle(gpu, oracle, cold, no_ws):
                 o_top, o_am = oracle.roi_pool(maps[k], rois[k], 7, 7, 0.125)
                 assert np.array_equal(top.cpu().numpy(), o_top) and np.array_equal(am.cpu().numpy(), o_am), k
             grads[k] = dev(torch, np.random.RandomState(31 + it).uniform(-1, 1, tuple(top.shape)).astype(np.float32))
-        if no_ws:
-            ws = False
-        elif ws is None:
-            from mv3d_tf_amd._lib import RoiGradView, lib
-            arr = (RoiGradView * 3)(*[RoiGradView(0, 0, 0, 0, 0.125, B, 2 * per, H, W, 512) for H, W in VIEWS.values()])
-            ws = torch.randint(0, 255, (lib().mv3d_roi_pool_pair_workspace_bytes(3, arr, 7, 7),), dtype=torch.uint8, device="cuda")
         got = ops.roi_pool_backward_views_pair([(grads[k], d_rois[k], am, maps[k].shape, 0.125) for k, (_, am) in zip(VIEWS, outs)], 7, 7, workspace=ws)
         want = ops.roi_pool_backward_views([(grads[k], d_rois[k], pam, maps[k].shape, 0.125) for k, (_, pam) in zip(VIEWS, plain)], 7, 7)
         for k, a, b, (_, pam) in zip(VIEWS, got, want, plain):
@@ -87,7 +91,8 @@ def test_pair_on_the_pinned_fixtures(gpu, name, no_ws):
     res = ops.roi_pool_forward_views_pair([(d, r, 0.125)], 7, 7)
     top, am = res[0]
     dec, = ops.roi_pool_argmax_decode([(d, r, 0.125)], res, 7, 7)
-    bd, = ops.roi_pool_backward_views_pair([(dev(torch, grad), r, am, data.shape, 0.125)], 7, 7, workspace=False if no_ws else None)
+    bd, = ops.roi_pool_backward_views_pair([(dev(torch, grad), r, am, data.shape, 0.125)], 7, 7,
+                                           workspace=_pair_workspace(torch, no_ws, [data.shape], [rois.shape[0]]))
     check_outputs(g, top.cpu().numpy(), dec.cpu().numpy(), bd.cpu().numpy())
 
 
@@ -95,8 +100,8 @@ def test_pair_on_the_pinned_fixtures(gpu, name, no_ws):
 @pytest.mark.parametrize("C", [64, 256, 320, 512, 1024])
 @pytest.mark.parametrize("R", [40, 700])
 def test_pair_other_widths_and_many_rois(gpu, oracle, C, R, no_ws):
-    """256 / 512 channels: the pair's kernels (R = 700: three passes of the index's 256-ROI filter); 64 / 320 / 1024: the plain forward
-    and the plain indexed / sliced / generic backward behind the same two entries"""
+    """256 / 512 channels: the pair's kernels (R = 700: three rounds of the tile kernel's 256-ROI filter); 64 / 320 / 1024: the plain
+    forward and the plain indexed / sliced / generic backward behind the same two entries"""
     torch, ops = gpu
     rs = np.random.RandomState(C + R)
     B = 2
@@ -116,7 +121,7 @@ def test_pair_other_widths_and_many_rois(gpu, oracle, C, R, no_ws):
         assert np.array_equal(top.cpu().numpy(), o_top) and np.array_equal(am.cpu().numpy(), o_am)
         grads.append(rs.uniform(-1, 1, o_top.shape).astype(np.float32)); ams.append(o_am)
     bds = ops.roi_pool_backward_views_pair([(dev(torch, g), r, am, m.shape, 0.125) for g, r, (_, am), m in zip(grads, d_rois, outs, maps)], 7, 7,
-                                           workspace=False if no_ws else None)
+                                           workspace=_pair_workspace(torch, no_ws, [m.shape for m in maps], [R] * len(maps)))
     for m, r, o_am, g, bd in zip(maps, rois, ams, grads, bds):
         assert np.array_equal(bd.cpu().numpy(), oracle.roi_pool_grad(m, r, o_am, g, 7, 7, 0.125))
 
@@ -144,7 +149,8 @@ def test_pair_huge_rois_ties_and_nan(gpu, oracle, no_ws):
     o_top, o_am = oracle.roi_pool(m, rois, 7, 7, 0.125)
     assert np.array_equal(res[0][0].cpu().numpy(), o_top, equal_nan=True) and np.array_equal(dec.cpu().numpy(), o_am)
     g = rs.uniform(-1, 1, o_top.shape).astype(np.float32)
-    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7, workspace=False if no_ws else None)
+    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7,
+                                           workspace=_pair_workspace(torch, no_ws, [m.shape], [rois.shape[0]]))
     assert np.array_equal(bd.cpu().numpy(), oracle.roi_pool_grad(m, rois, o_am, g, 7, 7, 0.125))
 
 
@@ -154,7 +160,7 @@ def test_pair_malformed_and_overhanging_rois(gpu, oracle, C, no_ws):
     """The reference's backward lets a gradient through only inside the rounded ROI (roi_pooling_op.cc:401-404).  (a) A ROI whose end lies
     before its start is pooled by the forward as a forced 1 x 1 region and gets NO gradient; (b) extents 57, 114, 121 (f32: 7 * (57 / 7) >
     57): the last bin of the forward reaches one column / row past the ROI, what lands there is dropped; (c) a ROI of more than 2048 map
-    pixels (the tile kernel evaluates the reference's per-pixel expressions there).  Both RoiPoolGrad structures against the oracle."""
+    pixels (the tile kernel evaluates the reference's per-pixel expressions there).  Both call forms against the oracle."""
     torch, ops = gpu
     rs = np.random.RandomState(C)
     B, H, W = 2, 70, 130
@@ -181,7 +187,8 @@ def test_pair_malformed_and_overhanging_rois(gpu, oracle, C, no_ws):
     assert ((o_am[0] // C) % W == 57).any()
     g = rs.uniform(-1, 1, o_top.shape).astype(np.float32)
     want = oracle.roi_pool_grad(m, rois, o_am, g, 7, 7, 0.125)
-    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7, workspace=False if no_ws else None)
+    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7,
+                                           workspace=_pair_workspace(torch, no_ws, [m.shape], [rois.shape[0]]))
     assert np.array_equal(bd.cpu().numpy(), want)
 
 
@@ -196,7 +203,7 @@ def _pair_against_oracle(torch, ops, oracle, m, rois, seed):
     g = np.random.RandomState(seed).uniform(-1, 1, o_top.shape).astype(np.float32)
     want = oracle.roi_pool_grad(m, rois, o_am, g, 7, 7, 0.125)
     for _ in range(2):                                               # (the list is read again by a second backward of the same forward)
-        bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7, workspace=False)
+        bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7)
         assert np.array_equal(bd.cpu().numpy(), want)
     return res
 
@@ -290,7 +297,7 @@ def test_autograd_views_function_uses_the_pair(gpu, oracle):
     rois = [np.stack([rs.randint(0, 2, 30), rs.randint(0, 60, 30), rs.randint(0, 40, 30), rs.randint(60, 150, 30), rs.randint(40, 90, 30)], 1).astype(np.float32)
             for _ in maps]
     xs = [dev(torch, m).requires_grad_(True) for m in maps]
-    for rep in range(3):                                               # (the workspace goes back to the pool and is reused)
+    for rep in range(3):                                               # (three steps on the same tensors)
         for x in xs:
             x.grad = None
         tops = roi_pool_views([(x, dev(torch, r)) for x, r in zip(xs, rois)], 7, 7, 0.125)

@@ -35,7 +35,7 @@ def run(sel):
     o_top, o_am = oracle.roi_pool(m, r, 7, 7, 0.125)
     g = G_TEST[sel] if os.environ.get("G_TEST", "1") == "1" else np.random.RandomState(1).uniform(-1, 1, o_top.shape).astype(np.float32)
     want = oracle.roi_pool_grad(m, r, o_am, g, 7, 7, 0.125)
-    got = ops.roi_pool_backward_views_pair([(dev(g), rr, res[0][1], m.shape, 0.125)], 7, 7, workspace=False)[0].cpu().numpy()
+    got = ops.roi_pool_backward_views_pair([(dev(g), rr, res[0][1], m.shape, 0.125)], 7, 7)[0].cpu().numpy()
     return got, want
 
 

@@ -8,7 +8,7 @@ from test_gpu_configs import dev
 build.build()
 
 
-def case(C, no_ws):
+def case(C):
     rs = np.random.RandomState(C)
     B, H, W = 2, 70, 130
     m = rs.uniform(-1, 1, (B, H, W, C)).astype(np.float32)
@@ -27,10 +27,10 @@ def case(C, no_ws):
     print("fwd equal", np.array_equal(res[0][0].cpu().numpy(), o_top), np.array_equal(dec.cpu().numpy(), o_am))
     g = rs.uniform(-1, 1, o_top.shape).astype(np.float32)
     want = oracle.roi_pool_grad(m, rois, o_am, g, 7, 7, 0.125)
-    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7, workspace=False if no_ws else None)
+    bd, = ops.roi_pool_backward_views_pair([(dev(torch, g), r, res[0][1], m.shape, 0.125)], 7, 7)
     got = bd.cpu().numpy()
     bad = np.argwhere(got != want)
-    print("C", C, "no_ws", no_ws, "differ", len(bad), "nan in got", int(np.isnan(got).sum()))
+    print("C", C, "differ", len(bad), "nan in got", int(np.isnan(got).sum()))
     if len(bad):
         px = np.unique(bad[:, :3], axis=0)
         print("   pixels:", len(px), px[:12].tolist(), "channels:", np.unique(bad[:, 3])[:16].tolist(), len(np.unique(bad[:, 3])))
@@ -45,5 +45,4 @@ def case(C, no_ws):
 
 
 for C in (256, 512):
-    for no_ws in (False, True):
-        case(C, no_ws)
+    case(C)

@@ -3,7 +3,8 @@
 views), kernel-only, cycling over NB resident batches (distinct maps / records, so consecutive launches are cold):
 
     plain    mv3d_roi_pool_forward_views_cold + mv3d_roi_pool_backward_views (workspace: index x 2 launches + gather)
-    pair     mv3d_roi_pool_forward_views_pair (cold; 16-bit argmax codes) + mv3d_roi_pool_backward_views_pair (index + fill, gather)
+    pair     mv3d_roi_pool_forward_views_pair (cold; one-byte argmax codes) + mv3d_roi_pool_backward_views_pair (one launch of LDS map
+             tiles; the workspace is handed over and not read)
 
 forward and backward are timed alternating (fwd b0, bwd b0, fwd b1, ...) -- the order a step runs them in -- with HIP events
 around every call, and back to back per kind."""
@@ -47,7 +48,7 @@ def calls(bt, indexed):
                              bt.num_rois, H, W, Cc)
     ws = torch.zeros(L.mv3d_roi_pool_pair_workspace_bytes(3, bwd, 7, 7), dtype=torch.uint8, device=dev)
     wp, wn = C.c_void_p(ws.data_ptr()), ws.numel()
-    if os.environ.get("PAIR_NO_WS"):            # the one-launch tile RoiPoolGrad (what the path runs)
+    if os.environ.get("PAIR_NO_WS"):            # no workspace: the plain leg's sliced RoiPoolGrad (the pair's never reads one)
         wp, wn = None, 0
     keep = (fwd, bwd, ws)
     if indexed:
@@ -94,6 +95,6 @@ for name, indexed in ORDER:
     snap = [batches[0].bottom_diff[v].clone() for v in VIEWS] + [batches[0].tops[v][0].clone() for v in VIEWS]
     if want is None:
         want = snap
-    elif not os.environ.get("MV3D_IDX_DBG"):
+    else:
         assert all(torch.equal(a, b_) for a, b_ in zip(want, snap)), "plain and pair outputs differ"
 print("outputs of both pairs bit-identical on batch 0")

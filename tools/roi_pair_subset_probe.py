@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""RoiPoolGrad of the pair on SUBSETS of the bench's three views (bev, rgb, fv), with a workspace (index + gather) and without one
-(the one-launch tile kernel): which view costs what in which structure.  Kernel-only, cold batches, HIP events around the call."""
+"""RoiPoolGrad of the pair (the one-launch tile kernel) on SUBSETS of the bench's three views (bev, rgb, fv): which view costs what.
+Kernel-only, cold batches, HIP events around the call."""
 import ctypes as C
 import os
 import sys
@@ -46,22 +46,19 @@ for f, _ in all_fwd:                                   # the pair's codes for ev
     check(L.mv3d_roi_pool_forward_views_pair(3, f, 7, 7, 1, st), "fwd")
 torch.cuda.synchronize()
 for names in (("bev", "rgb", "fv"), ("bev", "rgb"), ("fv",), ("bev",), ("rgb",), ("rgb", "bev")):
-    for no_ws in (False, True):
-        cs = [views_of(b, names)[1] for b in batches]
-        ws = torch.zeros(L.mv3d_roi_pool_pair_workspace_bytes(len(names), cs[0], 7, 7), dtype=torch.uint8, device=dev)
-        wp, wn = (None, 0) if no_ws else (C.c_void_p(ws.data_ptr()), ws.numel())
-        call = lambda a: check(L.mv3d_roi_pool_backward_views_pair(len(names), a, 7, 7, wp, wn, st), "bwd")
+    cs = [views_of(b, names)[1] for b in batches]
+    call = lambda a: check(L.mv3d_roi_pool_backward_views_pair(len(names), a, 7, 7, None, 0, st), "bwd")
+    for a in cs:
+        call(a)
+    torch.cuda.synchronize()
+    tot, n = 0.0, 0
+    for _ in range(ROUNDS):
+        evs = []
         for a in cs:
-            call(a)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); call(a); e1.record()
+            evs.append((e0, e1))
         torch.cuda.synchronize()
-        tot, n = 0.0, 0
-        for _ in range(ROUNDS):
-            evs = []
-            for a in cs:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); call(a); e1.record()
-                evs.append((e0, e1))
-            torch.cuda.synchronize()
-            for e0, e1 in evs:
-                tot += e0.elapsed_time(e1); n += 1
-        print("%-14s %-22s %6.1f us" % ("+".join(names), "tiles (no workspace)" if no_ws else "index + gather", tot / n * 1e3), flush=True)
+        for e0, e1 in evs:
+            tot += e0.elapsed_time(e1); n += 1
+    print("%-14s %6.1f us" % ("+".join(names), tot / n * 1e3), flush=True)
