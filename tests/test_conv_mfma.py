@@ -4,7 +4,10 @@ a plain PyTorch fp32 convolution of the SAME f16-rounded operands.
 Tolerance: the kernel multiplies f16 operands exactly and accumulates in f32 (MFMA), so against the fp32 reference it differs by
 the f32 accumulation order (~1e-6 relative) plus, for f16 outputs, one rounding to f16 (2^-11 relative): |got - want| <=
 2e-3 * max|want| for f16 maps, 2e-5 * max|want| for f32 maps.  Operands are asymmetric random values, so a transposed
-fragment / tap / channel mapping cannot pass."""
+fragment / tap / channel mapping cannot pass.
+
+These small maps reach the "few tiles" 64 x 128, the 256 x 64 and the input-layer tiles; the paths that larger launches select
+(conv3x3_pp_kernel, 128 x 128, f32 output, gated, f32 128 x 128) are pinned exactly in tests/test_conv_paths.py."""
 import numpy as np
 import pytest
 
@@ -644,7 +647,9 @@ _VIEW_SIZES = [(2, 19, 23), (1, 37, 50), (2, 8, 64)]            # three "trunks"
 @pytest.mark.parametrize("dt,cin,cout", [("f16", 64, 64), ("bf16", 128, 256), ("f32", 64, 128), ("bf16", 512, 512)])
 def test_grouped_views_equal_the_single_view_entries(gpu, dt, cin, cout):
     """mv3d_conv3x3_views_* / maxpool2x2[_bwd]_views_* / conv3x3_wgrad_views_*: one launch for several maps of one layer shape gives,
-    per view, the bits of the single-view entry (same kernels, same tiles -- a view's workgroups only start at another block index)"""
+    per view, the bits of the single-view entry.  At these sizes the grouped launch runs the same kernel and tiles (a view's workgroups
+    only start at another block index); the kernel is chosen by the tile count of ALL views, so larger views can move a grouped launch to
+    a bigger tile than each view alone would get -- tests/test_conv_paths.py covers those, the bits stay the same."""
     torch = gpu
     from mv3d_tf_amd import ops
     T = {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[dt]
