@@ -683,6 +683,43 @@ int mv3d_adam_step(const mv3d_adam_tensor *tensors_dev, const int32_t *chunk_ten
                    double lr, double beta1, double beta2, double eps, int step, int lowp_dtype /* of param_lowp: 0 none, 1 f16, 2 bf16 */,
                    void *stream);
 
+/* ------------------------------------------------------------------ KITTI evaluation (csrc/kitti_eval.hip)
+ * Bird's-eye-view and 3D average precision of LIDAR-corner detections over a whole split (new here: the reference writes
+ * result files for the KITTI devkit binary, lib/datasets/kitti_mv3d.py:321-352, and never runs it).  Frames are CSR ranges:
+ * frame f owns detections det_off[f] .. det_off[f+1]-1, objects gt_off[f] .. gt_off[f+1]-1, and the D_f x G_f row-major
+ * pair block pair_off[f] .. pair_off[f] + D_f G_f - 1, pair_off[0] = 0, pair_off[f+1] = pair_off[f] + D_f G_f.
+ * det_off / gt_off are HOST arrays, validated before any device call (start at 0, monotone, end at num_dets / num_gts, at
+ * most MV3D_KITTI_MAX_DETS detections per frame, sum of D_f G_f == num_pairs < 2^31); offsets_dev holds the same det_off,
+ * gt_off and the pair_off above on the device.  Conventions, operation order and launch shapes: DESIGN.md §3.12.
+ *   det_cnr_dev    (num_dets, 24) f32 LIDAR corners (x0..x7, y0..y7, z0..z7), det_score_dev (num_dets) f32
+ *   calib_dev      (num_frames, 4, 12) f32 calibration tables (P2 | P3 | R0 | Tr_velo_to_cam), for the detections' image height
+ *   gt_cnr_dev     (num_gts, 24) f32 LIDAR corners, gt_cls_dev (num_gts) int32 class codes (the caller's numbering),
+ *   gt_attr_dev    (num_gts, 4) f32: truncation, occlusion, y1, y2 of the label's image box
+ *   img_height     rows of the image the detections' projected boxes are clipped to */
+#define MV3D_KITTI_MAX_DETS 2048
+#define MV3D_KITTI_NUM_SAMPLE_PTS 41
+typedef struct {
+    int32_t num_frames, num_dets, num_gts, img_height;
+    const int32_t *det_off, *gt_off;     /* host, (num_frames + 1) each */
+    const int32_t *offsets_dev;          /* device (3, num_frames + 1): det_off | gt_off | pair_off */
+    const float *det_cnr_dev, *det_score_dev, *calib_dev, *gt_cnr_dev;
+    const int32_t *gt_cls_dev;
+    const float *gt_attr_dev;
+} mv3d_kitti_split;
+/* iou_dev (2, num_pairs) f64: iou_bev | iou_3d; det_height_dev (num_dets) f64: height of the projected, clipped image box. */
+int mv3d_kitti_eval_overlaps(const mv3d_kitti_split *split, long long num_pairs, double *iou_dev, double *det_height_dev,
+                             void *stream);
+/* Pass 1 of the devkit's statistics (no false positives): matched_dev (2 metrics, 3 difficulties, num_gts) f32 = the score of
+ * the detection matched to that object as a true positive, -inf otherwise.  Objects of class eval_class are evaluated, those
+ * of neighbor_class ignored, all others skipped; min_overlap >= 0. */
+int mv3d_kitti_eval_match(const mv3d_kitti_split *split, long long num_pairs, const double *iou_dev, const double *det_height_dev,
+                          int eval_class, int neighbor_class, double min_overlap, float *matched_dev, void *stream);
+/* Pass 2: thresholds_dev (2, 3, MV3D_KITTI_NUM_SAMPLE_PTS) f32 score thresholds, num_thresholds_dev (2, 3) int32 (<= 41 used);
+ * counts_dev (2, 3, MV3D_KITTI_NUM_SAMPLE_PTS, 3) int32 tp | fp | fn, zeroed by the call, then summed over frames. */
+int mv3d_kitti_eval_count(const mv3d_kitti_split *split, long long num_pairs, const double *iou_dev, const double *det_height_dev,
+                          int eval_class, int neighbor_class, double min_overlap, const float *thresholds_dev,
+                          const int32_t *num_thresholds_dev, int32_t *counts_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,14 @@ class AdamTensor(C.Structure):
                 ("param_lowp", C.c_void_p)]
 
 
+class KittiSplit(C.Structure):
+    """mv3d_kitti_split"""
+    _fields_ = [("num_frames", C.c_int32), ("num_dets", C.c_int32), ("num_gts", C.c_int32), ("img_height", C.c_int32),
+                ("det_off", C.c_void_p), ("gt_off", C.c_void_p), ("offsets_dev", C.c_void_p), ("det_cnr_dev", C.c_void_p),
+                ("det_score_dev", C.c_void_p), ("calib_dev", C.c_void_p), ("gt_cnr_dev", C.c_void_p), ("gt_cls_dev", C.c_void_p),
+                ("gt_attr_dev", C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mv3d_version": (C.c_int, []),
@@ -212,6 +220,9 @@ _SIGS = {
     "mv3d_softmax_rows": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P]),
     "mv3d_adam_chunk_elements": (C.c_int, []),
     "mv3d_adam_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _P]),
+    "mv3d_kitti_eval_overlaps": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, _P]),
+    "mv3d_kitti_eval_match": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
+    "mv3d_kitti_eval_count": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

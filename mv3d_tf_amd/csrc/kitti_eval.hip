@@ -1,0 +1,401 @@
+// KITTI object evaluation on the device: bird's-eye-view and 3D average precision of LIDAR-frame corner detections
+// (DESIGN.md §3.12).  Three launches over a whole split, frames as CSR ranges (det_off / gt_off / pair_off):
+//
+//   kitti_overlap_kernel   one 64-lane workgroup per frame: iou_bev / iou_3d of every (det, gt) pair of the frame, stored as
+//                          the frame's D x G row-major block at pair_off[f] (two planes: bev | 3d), plus every detection's
+//                          image-box height.
+//   kitti_match_kernel     pass 1 (no false positives): one wave per (frame, metric, difficulty); one slot per GT receives the
+//                          score of the detection matched to it as a true positive, or -inf.
+//   kitti_count_kernel     pass 2: one 256-lane workgroup per (frame, metric, difficulty), its four waves take the score
+//                          thresholds round robin; integer tp / fp / fn per (metric, difficulty, threshold) by atomics.
+//
+// Operation order of the overlap (all f64 from the f32 corners; tests/kitti_eval_restatement.py follows it line by line):
+//   box  (x0..x7, y0..y7, z0..z7) f32.  Any non-finite value in either box -> both IoUs 0.
+//   footprint  v_k = (x_k, y_k), k = 0..3.  s = 0; for k = 0..3: s = s + (x_k * y_n - x_n * y_k), n = (k + 1) % 4; A = 0.5 * s.
+//              if A < 0: vertices reversed (v3, v2, v1, v0) and A = -A.
+//   height     lo = z0, hi = z0; for k = 1..7: if z_k < lo: lo = z_k; if z_k > hi: hi = z_k.
+//   clip       P = footprint of a; for each edge i = 0..3 of b in order (b0 = w_i, b1 = w_{(i+1)%4}): ex = b1x - b0x,
+//              ey = b1y - b0y; Q = []; for j = 0..n-1 (p = P_j, q = P_{(j+1)%n}): cp = ex * (py - b0y) - ey * (px - b0x),
+//              cq likewise for q; if cp >= 0: Q += p; if (cp >= 0) != (cq >= 0): t = cp / (cp - cq),
+//              Q += (px + t * (qx - px), py + t * (qy - py)).  P = Q.
+//   I          shoelace of the final P (sequential k = 0..n-1, same term as the footprint, 0 for n = 0) times 0.5;
+//              if !(I > 0): I = 0.
+//   iou_bev    U = (A_a + A_b) - I;  U > 0 ? I / U : 0.
+//   iou_3d     h = min(hi_a, hi_b) - max(lo_a, lo_b); if h < 0: h = 0.  VI = I * h; V = A * (hi - lo);
+//              U = (V_a + V_b) - VI;  U > 0 ? VI / U : 0.
+// A convex 4-gon clipped by 4 half-planes keeps at most 1.5 n vertices per stage (4 -> 6 -> 9 -> 13 -> 19); the three stored
+// stages fit 16 slots, the last stage is never stored: its shoelace is accumulated as the vertices come out.
+//
+// Detection image height: the 8 corners through proj_matrix / image_point (geometry.h, the proposal layer's projection),
+// lo / hi of the 8 image rows as above, both clipped to [0, img_height - 1], height = hi - lo; 0 if anything is non-finite.
+//
+// Matching (KITTI object devkit rules, restated; difficulty e / m / h): MIN_HEIGHT 40 / 25 / 25, MAX_OCCLUSION 0 / 1 / 2,
+// MAX_TRUNCATION 0.15f / 0.30f / 0.50f (compared in f32, the label's decimal value).  GT flag: the evaluated class ->
+// (occ > MAX_OCC || trunc > MAX_TRUNC || y2 - y1 <= MIN_HEIGHT) ? 1 : 0; the neighbouring class -> 1; anything else -> -1
+// (skipped).  Detection flag: height < MIN_HEIGHT ? 1 : 0.  For each GT in order, over the unassigned detections with
+// iou > min_overlap:
+//   pass 1   the highest score (first index on a tie; only scores > -1e7, as the devkit's NO_DETECTION start value).
+//   pass 2   detections with score < t are not candidates; the flag-0 detection with the largest IoU (first index on a
+//            tie), else the first flag-1 one.
+//   no match and GT flag 0 -> fn; a match with GT flag 1 or detection flag 1 -> the detection is consumed, nothing counted;
+//   any other match -> tp (pass 1: the GT's slot = the detection's score).  Pass 2 then counts every unassigned flag-0
+//   detection with !(score < t) as fp.
+// Lanes hold detections j = 64 c + lane (c < 32: at most MV3D_KITTI_MAX_DETS detections per frame); the argmax / first-index
+// reductions across lanes give exactly the sequential scan's pick.
+#include "geometry.h"
+
+#define KE_MAXV 16
+#define KE_OVERLAP_THREADS 64
+#define KE_COUNT_WAVES 4
+#define KE_LDS_IOU 4096     // doubles of one frame's IoU block staged in LDS by the count kernel (32 KiB)
+
+__constant__ int c_min_height[3] = {40, 25, 25};
+__constant__ int c_max_occ[3] = {0, 1, 2};
+__constant__ float c_max_trunc[3] = {0.15f, 0.30f, 0.50f};
+
+struct KeBox {
+    double x[4], y[4], area, lo, hi;
+};
+
+__device__ __forceinline__ bool ke_load(const float *__restrict__ c, KeBox &b)
+{
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 24; ++k) fin = fin && isfinite(c[k]);
+    double x[4], y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { x[k] = (double)c[k]; y[k] = (double)c[8 + k]; }
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int n = (k + 1) & 3;
+        s = s + (x[k] * y[n] - x[n] * y[k]);
+    }
+    double a = 0.5 * s;
+    const bool rev = a < 0.0;
+    if (rev) a = -a;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { b.x[k] = rev ? x[3 - k] : x[k]; b.y[k] = rev ? y[3 - k] : y[k]; }
+    b.area = a;
+    double lo = (double)c[16], hi = lo;
+#pragma unroll
+    for (int k = 1; k < 8; ++k) {
+        const double z = (double)c[16 + k];
+        if (z < lo) lo = z;
+        if (z > hi) hi = z;
+    }
+    b.lo = lo; b.hi = hi;
+    return fin;
+}
+
+// this lane's vertex v of polygon buffer `buf` (LDS, [buf][vertex][x|y][lane])
+#define KE_V(buf, v, comp) poly[(((buf) * KE_MAXV + (v)) * 2 + (comp)) * KE_OVERLAP_THREADS + lane]
+
+__device__ __forceinline__ void ke_iou(const KeBox &a, const KeBox &b, double *poly, int lane, double &iou_bev, double &iou_3d)
+{
+    int n = 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { KE_V(0, k, 0) = a.x[k]; KE_V(0, k, 1) = a.y[k]; }
+    double s = 0.0, fx = 0.0, fy = 0.0, lx = 0.0, ly = 0.0;
+    int cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int src = i & 1, dst = src ^ 1;
+        const double b0x = b.x[i], b0y = b.y[i], ex = b.x[(i + 1) & 3] - b0x, ey = b.y[(i + 1) & 3] - b0y;
+        int m = 0;
+        for (int j = 0; j < n; ++j) {
+            const int jn = (j + 1 == n) ? 0 : j + 1;
+            const double px = KE_V(src, j, 0), py = KE_V(src, j, 1), qx = KE_V(src, jn, 0), qy = KE_V(src, jn, 1);
+            const double cp = ex * (py - b0y) - ey * (px - b0x);
+            const double cq = ex * (qy - b0y) - ey * (qx - b0x);
+            auto emit = [&](double vx, double vy) {
+                if (i < 3) {
+                    if (m < KE_MAXV) { KE_V(dst, m, 0) = vx; KE_V(dst, m, 1) = vy; }
+                    ++m;
+                } else {                                   // last stage: shoelace as the vertices come out
+                    if (cnt == 0) { fx = vx; fy = vy; }
+                    else s = s + (lx * vy - vx * ly);
+                    lx = vx; ly = vy;
+                    ++cnt;
+                }
+            };
+            if (cp >= 0.0) emit(px, py);
+            if ((cp >= 0.0) != (cq >= 0.0)) {
+                const double t = cp / (cp - cq);
+                emit(px + t * (qx - px), py + t * (qy - py));
+            }
+        }
+        n = m < KE_MAXV ? m : KE_MAXV;
+    }
+    if (cnt > 0) s = s + (lx * fy - fx * ly);
+    double inter = 0.5 * s;
+    if (!(inter > 0.0)) inter = 0.0;
+    const double u = (a.area + b.area) - inter;
+    iou_bev = u > 0.0 ? inter / u : 0.0;
+    const double top = a.hi < b.hi ? a.hi : b.hi, bot = a.lo > b.lo ? a.lo : b.lo;
+    double h = top - bot;
+    if (h < 0.0) h = 0.0;
+    const double vi = inter * h;
+    const double u3 = (a.area * (a.hi - a.lo) + b.area * (b.hi - b.lo)) - vi;
+    iou_3d = u3 > 0.0 ? vi / u3 : 0.0;
+}
+
+__global__ __launch_bounds__(KE_OVERLAP_THREADS) void kitti_overlap_kernel(
+    int F, const int32_t *__restrict__ offs, const float *__restrict__ det_cnr, const float *__restrict__ calib,
+    const float *__restrict__ gt_cnr, double img_hmax, double *__restrict__ iou, long long P, double *__restrict__ det_height)
+{
+    __shared__ double poly[2 * KE_MAXV * 2 * KE_OVERLAP_THREADS];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const int32_t *det_off = offs, *gt_off = offs + (F + 1), *pair_off = offs + 2 * (F + 1);
+    const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
+    const long long p0 = pair_off[f];
+    for (int p = lane; p < D * G; p += KE_OVERLAP_THREADS) {
+        const int d = p / G, g = p - d * G;
+        KeBox a, b;
+        const bool fa = ke_load(det_cnr + 24 * (long long)(d0 + d), a);
+        const bool fb = ke_load(gt_cnr + 24 * (long long)(g0 + g), b);
+        double ib = 0.0, i3 = 0.0;
+        if (fa && fb) ke_iou(a, b, poly, lane, ib, i3);
+        iou[p0 + p] = ib;
+        iou[P + p0 + p] = i3;
+    }
+    float M[12];
+    proj_matrix(calib + 48 * (long long)f, M);
+    for (int d = lane; d < D; d += KE_OVERLAP_THREADS) {
+        const float *c = det_cnr + 24 * (long long)(d0 + d);
+        bool fin = true;
+        double lo = 0.0, hi = 0.0;
+        for (int k = 0; k < 8; ++k) {
+            fin = fin && isfinite(c[k]) && isfinite(c[8 + k]) && isfinite(c[16 + k]);
+            double px, py;
+            image_point(M, c[k], c[8 + k], c[16 + k], px, py);
+            fin = fin && isfinite(py);
+            if (k == 0) { lo = hi = py; }
+            else {
+                if (py < lo) lo = py;
+                if (py > hi) hi = py;
+            }
+        }
+        double h = 0.0;
+        if (fin) {
+            lo = lo < 0.0 ? 0.0 : (lo > img_hmax ? img_hmax : lo);
+            hi = hi < 0.0 ? 0.0 : (hi > img_hmax ? img_hmax : hi);
+            h = hi - lo;
+        }
+        det_height[d0 + d] = h;
+    }
+}
+
+// GT flag of object g for difficulty `diff`: 0 counted, 1 ignored, -1 skipped
+__device__ __forceinline__ int ke_gt_flag(const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr, int g, int diff,
+                                          int eval_class, int neighbor_class)
+{
+    const int cls = gt_cls[g];
+    if (cls == eval_class) {
+        const float *a = gt_attr + 4 * (long long)g;
+        const double height = (double)a[3] - (double)a[2];
+        return (a[1] > (float)c_max_occ[diff] || a[0] > c_max_trunc[diff] || height <= (double)c_min_height[diff]) ? 1 : 0;
+    }
+    return cls == neighbor_class ? 1 : -1;
+}
+
+__device__ __forceinline__ void ke_argmax(double &key, int &idx)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double k2 = __shfl_xor(key, o);
+        const int i2 = __shfl_xor(idx, o);
+        if (k2 > key || (k2 == key && i2 < idx)) { key = k2; idx = i2; }
+    }
+}
+
+__device__ __forceinline__ int ke_min(int v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int v2 = __shfl_xor(v, o);
+        v = v2 < v ? v2 : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void kitti_match_kernel(
+    int F, const int32_t *__restrict__ offs, const double *__restrict__ iou, long long P, const float *__restrict__ det_score,
+    const double *__restrict__ det_height, const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr, int Gtot,
+    int eval_class, int neighbor_class, double min_overlap, float *__restrict__ matched)
+{
+    const int task = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (task >= F * 6) return;
+    const int f = task / 6, metric = (task / 3) % 2, diff = task % 3;
+    const int32_t *det_off = offs, *gt_off = offs + (F + 1), *pair_off = offs + 2 * (F + 1);
+    const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
+    const double *blk = iou + metric * P + pair_off[f];
+    float *out = matched + (long long)(metric * 3 + diff) * Gtot + g0;
+    const int nch = (D + 63) >> 6;
+    const double min_h = (double)c_min_height[diff];
+    uint32_t assigned = 0u;
+    for (int g = 0; g < G; ++g) {
+        const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
+        float slot = -INFINITY;
+        if (flag >= 0) {
+            double best = -INFINITY;
+            int bi = INT32_MAX;
+            for (int c = 0; c < nch; ++c) {
+                const int j = 64 * c + lane;
+                if (j < D && !((assigned >> c) & 1u) && blk[(long long)j * G + g] > min_overlap) {
+                    const double sc = (double)det_score[d0 + j];
+                    if (sc > -10000000.0 && sc > best) { best = sc; bi = j; }
+                }
+            }
+            ke_argmax(best, bi);
+            if (bi != INT32_MAX) {
+                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+                const bool ign_det = det_height[d0 + bi] < min_h;
+                if (flag == 0 && !ign_det) slot = det_score[d0 + bi];
+            }
+        }
+        if (lane == 0) out[g] = slot;
+    }
+}
+
+__global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_kernel(
+    int F, const int32_t *__restrict__ offs, const double *__restrict__ iou, long long P, const float *__restrict__ det_score,
+    const double *__restrict__ det_height, const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr,
+    int eval_class, int neighbor_class, double min_overlap, const float *__restrict__ thresholds, const int32_t *__restrict__ num_thr,
+    int32_t *__restrict__ counts)
+{
+    __shared__ double s_iou[KE_LDS_IOU];
+    const int task = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = task / 6, metric = (task / 3) % 2, diff = task % 3, md = metric * 3 + diff;
+    const int32_t *det_off = offs, *gt_off = offs + (F + 1), *pair_off = offs + 2 * (F + 1);
+    const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
+    int T = num_thr[md];
+    T = T < 0 ? 0 : (T > MV3D_KITTI_NUM_SAMPLE_PTS ? MV3D_KITTI_NUM_SAMPLE_PTS : T);
+    if (D == 0 && G == 0) return;
+    const double *gblk = iou + metric * P + pair_off[f];
+    const double *blk = gblk;
+    if ((long long)D * G <= KE_LDS_IOU) {              // (workgroup-uniform) stage the frame's block in LDS
+        for (int p = threadIdx.x; p < D * G; p += 64 * KE_COUNT_WAVES) s_iou[p] = gblk[p];
+        __syncthreads();
+        blk = s_iou;
+    }
+    const int nch = (D + 63) >> 6;
+    const double min_h = (double)c_min_height[diff];
+    uint32_t ign = 0u;
+    for (int c = 0; c < nch; ++c) {
+        const int j = 64 * c + lane;
+        if (j < D && det_height[d0 + j] < min_h) ign |= 1u << c;
+    }
+    for (int ti = wave; ti < T; ti += KE_COUNT_WAVES) {
+        const float t = thresholds[md * MV3D_KITTI_NUM_SAMPLE_PTS + ti];
+        uint32_t cand = 0u, assigned = 0u;
+        for (int c = 0; c < nch; ++c) {
+            const int j = 64 * c + lane;
+            if (j < D && !(det_score[d0 + j] < t)) cand |= 1u << c;
+        }
+        int tp = 0, fn = 0;
+        for (int g = 0; g < G; ++g) {
+            const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
+            if (flag < 0) continue;
+            double best = -INFINITY;
+            int bi = INT32_MAX, first_ign = INT32_MAX;
+            for (int c = 0; c < nch; ++c) {
+                if (!(((cand & ~assigned) >> c) & 1u)) continue;
+                const int j = 64 * c + lane;
+                const double o = blk[(long long)j * G + g];
+                if (!(o > min_overlap)) continue;
+                if ((ign >> c) & 1u) {
+                    if (first_ign == INT32_MAX) first_ign = j;
+                } else if (o > best) {
+                    best = o; bi = j;
+                }
+            }
+            ke_argmax(best, bi);
+            if (bi == INT32_MAX) bi = ke_min(first_ign);
+            if (bi == INT32_MAX) {
+                if (flag == 0) ++fn;
+            } else {
+                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+                if (flag == 0 && !(det_height[d0 + bi] < min_h)) ++tp;
+            }
+        }
+        int fp = 0;
+        for (int c = 0; c < nch; ++c) fp += __popcll(__ballot((((cand & ~assigned & ~ign) >> c) & 1u) != 0u));
+        if (lane == 0) {
+            int32_t *o = counts + 3 * (md * MV3D_KITTI_NUM_SAMPLE_PTS + ti);
+            if (tp) atomicAdd(o, tp);
+            if (fp) atomicAdd(o + 1, fp);
+            if (fn) atomicAdd(o + 2, fn);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ C-ABI
+static int ke_validate(const mv3d_kitti_split *s, long long num_pairs)
+{
+    if (!s || s->num_frames < 0 || s->num_dets < 0 || s->num_gts < 0 || !s->det_off || !s->gt_off) return MV3D_ERR_INVALID_ARG;
+    const int F = s->num_frames;
+    if (s->det_off[0] != 0 || s->gt_off[0] != 0 || s->det_off[F] != s->num_dets || s->gt_off[F] != s->num_gts) return MV3D_ERR_INVALID_ARG;
+    long long pairs = 0;
+    for (int f = 0; f < F; ++f) {
+        const long long D = (long long)s->det_off[f + 1] - s->det_off[f], G = (long long)s->gt_off[f + 1] - s->gt_off[f];
+        if (D < 0 || G < 0 || D > MV3D_KITTI_MAX_DETS) return MV3D_ERR_INVALID_ARG;
+        pairs += D * G;
+    }
+    if (pairs != num_pairs || pairs > INT32_MAX) return MV3D_ERR_INVALID_ARG;
+    if (F > 0 && !s->offsets_dev) return MV3D_ERR_INVALID_ARG;
+    if (s->num_dets > 0 && (!s->det_cnr_dev || !s->det_score_dev)) return MV3D_ERR_INVALID_ARG;
+    if (s->num_gts > 0 && (!s->gt_cnr_dev || !s->gt_cls_dev || !s->gt_attr_dev)) return MV3D_ERR_INVALID_ARG;
+    if (F > 0 && !s->calib_dev) return MV3D_ERR_INVALID_ARG;
+    return MV3D_OK;
+}
+
+extern "C" int mv3d_kitti_eval_overlaps(const mv3d_kitti_split *split, long long num_pairs, double *iou_dev, double *det_height_dev,
+                                        void *stream)
+{
+    const int rc = ke_validate(split, num_pairs);
+    if (rc != MV3D_OK) return rc;
+    if (split->img_height < 1) return MV3D_ERR_INVALID_ARG;
+    if ((num_pairs > 0 && !iou_dev) || (split->num_dets > 0 && !det_height_dev)) return MV3D_ERR_INVALID_ARG;
+    if (split->num_frames == 0) return MV3D_OK;
+    hipLaunchKernelGGL(kitti_overlap_kernel, dim3(split->num_frames), dim3(KE_OVERLAP_THREADS), 0, (hipStream_t)stream,
+                       split->num_frames, split->offsets_dev, split->det_cnr_dev, split->calib_dev, split->gt_cnr_dev,
+                       (double)(split->img_height - 1), iou_dev, num_pairs, det_height_dev);
+    return mv3d_launch_status();
+}
+
+extern "C" int mv3d_kitti_eval_match(const mv3d_kitti_split *split, long long num_pairs, const double *iou_dev,
+                                     const double *det_height_dev, int eval_class, int neighbor_class, double min_overlap,
+                                     float *matched_dev, void *stream)
+{
+    const int rc = ke_validate(split, num_pairs);
+    if (rc != MV3D_OK) return rc;
+    if (!(min_overlap >= 0.0) || (num_pairs > 0 && !iou_dev) || (split->num_dets > 0 && !det_height_dev) ||
+        (split->num_gts > 0 && !matched_dev))
+        return MV3D_ERR_INVALID_ARG;
+    if (split->num_frames == 0 || split->num_gts == 0) return MV3D_OK;
+    const int tasks = split->num_frames * 6;
+    hipLaunchKernelGGL(kitti_match_kernel, dim3((tasks + 3) / 4), dim3(256), 0, (hipStream_t)stream, split->num_frames,
+                       split->offsets_dev, iou_dev, num_pairs, split->det_score_dev, det_height_dev, split->gt_cls_dev,
+                       split->gt_attr_dev, split->num_gts, eval_class, neighbor_class, min_overlap, matched_dev);
+    return mv3d_launch_status();
+}
+
+extern "C" int mv3d_kitti_eval_count(const mv3d_kitti_split *split, long long num_pairs, const double *iou_dev,
+                                     const double *det_height_dev, int eval_class, int neighbor_class, double min_overlap,
+                                     const float *thresholds_dev, const int32_t *num_thresholds_dev, int32_t *counts_dev,
+                                     void *stream)
+{
+    const int rc = ke_validate(split, num_pairs);
+    if (rc != MV3D_OK) return rc;
+    if (!(min_overlap >= 0.0) || (num_pairs > 0 && !iou_dev) || (split->num_dets > 0 && !det_height_dev) || !thresholds_dev ||
+        !num_thresholds_dev || !counts_dev)
+        return MV3D_ERR_INVALID_ARG;
+    MV3D_HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int32_t) * 6 * MV3D_KITTI_NUM_SAMPLE_PTS * 3, (hipStream_t)stream));
+    if (split->num_frames == 0) return MV3D_OK;
+    hipLaunchKernelGGL(kitti_count_kernel, dim3(split->num_frames * 6), dim3(64 * KE_COUNT_WAVES), 0, (hipStream_t)stream,
+                       split->num_frames, split->offsets_dev, iou_dev, num_pairs, split->det_score_dev, det_height_dev,
+                       split->gt_cls_dev, split->gt_attr_dev, eval_class, neighbor_class, min_overlap, thresholds_dev,
+                       num_thresholds_dev, counts_dev);
+    return mv3d_launch_status();
+}

@@ -12,8 +12,9 @@ lib/roi_data_layer/minibatch_mv3d.py:47-75.
 How it is done here: a frame's label file is parsed as ONE token table (no per-object Python loop); the numbers of the kept
 objects go to the device in one upload, `mv3d_gt_encode` (csrc/gt_encode.hip) computes camera corners, LIDAR corners, LIDAR
 box and BEV box for all objects at once, and one download brings the four arrays back.  Pinned bit for bit (values and
-dtypes) by tests/golden/kitti_label.npz, which the reference's own loader produced.  Evaluation, caching and the
-proposal-recall statistics of the reference class are out of scope."""
+dtypes) by tests/golden/kitti_label.npz, which the reference's own loader produced.  `evaluate_detections` writes the
+reference's result files and scores the detections on the device (datasets/kitti_eval.py); caching and the proposal-recall
+statistics of the reference class are out of scope."""
 import os
 
 import numpy as np
@@ -148,6 +149,30 @@ class kitti_mv3d(object):
 
     def gt_roidb(self):
         return [self._load_kitti_annotation(index) for index in self._image_index]
+
+    def _write_kitti_results_file(self, all_boxes, path):
+        """One <path>/<index>.txt per frame in the reference's line format (lib/datasets/kitti_mv3d.py:345-351): class name in
+        lower case, alpha 0, the all_boxes box (the BEV pixel box, as the reference writes it), every other field -1."""
+        os.makedirs(path, exist_ok=True)
+        for im_ind, index in enumerate(self.image_index):
+            with open(os.path.join(path, index + '.txt'), 'wt') as f:
+                for cls_ind, cls in enumerate(self.classes):
+                    if cls == '__background__':
+                        continue
+                    dets = all_boxes[cls_ind][im_ind]
+                    for k in range(len(dets)):
+                        f.write('{:s} -1 -1 {:.2f} {:.2f} {:.2f} {:.2f} {:.2f} -1 -1 -1 -1 -1 -1 -1 -1\n'
+                                .format(cls.lower(), 0, dets[k, 0], dets[k, 1], dets[k, 2], dets[k, 3]))
+        return path
+
+    def evaluate_detections(self, all_boxes, all_boxes3D, output_dir):
+        """Writes <output_dir>/results/data/<index>.txt (the reference writes under ROOT_DIR/kitti/results/<timestamp>
+        instead), then scores all_boxes3D (test_net's all_boxes_cnr) against the split's label_2 files: AP_BEV and AP_3D in
+        the three KITTI difficulties, printed, written to <output_dir>/kitti_ap.json and returned
+        ({(class, 'bev' | '3d', 'easy' | 'moderate' | 'hard'): AP in percent}, datasets/kitti_eval.py)."""
+        from .kitti_eval import evaluate_split
+        self._write_kitti_results_file(all_boxes, os.path.join(output_dir, 'results', 'data'))
+        return evaluate_split(self, all_boxes3D, output_dir)
 
     def append_flipped_images(self):
         raise NotImplementedError("cfg.TRAIN.USE_FLIPPED: the reference's flip only mirrors the 2-D image boxes "

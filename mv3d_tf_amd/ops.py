@@ -766,3 +766,55 @@ conv3x3 = conv3x3_f16
 maxpool2x2 = maxpool2x2_f16
 maxpool2x2_bwd = maxpool2x2_bwd_bf16
 conv3x3_wgrad = conv3x3_wgrad_bf16
+
+
+# ------------------------------------------------------------------ KITTI evaluation (csrc/kitti_eval.hip, datasets/kitti_eval.py)
+class KittiEvalSplit:
+    """A split on the device for mv3d_kitti_eval_*: the packed CSR arrays of ONE upload and the C descriptor pointing at them."""
+
+    def __init__(self, det_cnr, det_score, det_off, calib, gt_cnr, gt_off, gt_cls, gt_attr, device, img_height=375):
+        det_off = np.ascontiguousarray(det_off, np.int32)
+        gt_off = np.ascontiguousarray(gt_off, np.int32)
+        F = det_off.size - 1
+        D, G = np.diff(det_off).astype(np.int64), np.diff(gt_off).astype(np.int64)
+        pair_off = np.concatenate([[0], np.cumsum(D * G)])
+        self.num_pairs = int(pair_off[-1])
+        if self.num_pairs > np.iinfo(np.int32).max:
+            raise ValueError("KITTI evaluation: more than 2^31 - 1 (detection, object) pairs in one split")
+        offsets = np.stack([det_off, gt_off, pair_off.astype(np.int32)])
+        self.det_off, self.gt_off = det_off, gt_off        # host copies the C-ABI validates (kept alive with the descriptor)
+        self.dev = upload_packed([offsets, np.reshape(det_cnr, (-1, 24)), np.reshape(det_score, (-1,)), np.reshape(calib, (F, 4, 12)),
+                                  np.reshape(gt_cnr, (-1, 24)), np.asarray(gt_cls, np.int32), np.reshape(gt_attr, (-1, 4))], device)
+        self.device = device
+        self.F, self.N, self.G = F, int(det_off[-1]), int(gt_off[-1])
+        v = self.dev
+        self.split = _lib.KittiSplit(F, self.N, self.G, int(img_height), det_off.ctypes.data, gt_off.ctypes.data, v[0].data_ptr(),
+                                     v[1].data_ptr(), v[2].data_ptr(), v[3].data_ptr(), v[4].data_ptr(), v[5].data_ptr(),
+                                     v[6].data_ptr())
+
+
+def kitti_eval_overlaps(sp):
+    """-> iou (2, P) f64 (bev | 3d, frame f's D x G block at pair_off[f]), det_height (N) f64.  Asynchronous."""
+    iou = torch.empty((2, max(sp.num_pairs, 1)), dtype=torch.float64, device=sp.device)
+    height = torch.empty((max(sp.N, 1),), dtype=torch.float64, device=sp.device)
+    check(lib().mv3d_kitti_eval_overlaps(C.byref(sp.split), sp.num_pairs, _ptr(iou), _ptr(height), _stream()),
+          "mv3d_kitti_eval_overlaps")
+    return iou[:, :sp.num_pairs], height[:sp.N]
+
+
+def kitti_eval_match(sp, iou, height, eval_class, neighbor_class, min_overlap):
+    """Pass 1 -> matched (2, 3, G) f32: the true-positive score of every object, -inf if none.  Asynchronous."""
+    matched = torch.empty((2, 3, max(sp.G, 1)), dtype=torch.float32, device=sp.device)
+    check(lib().mv3d_kitti_eval_match(C.byref(sp.split), sp.num_pairs, _ptr(iou.contiguous()), _ptr(height), int(eval_class),
+                                      int(neighbor_class), float(min_overlap), _ptr(matched), _stream()), "mv3d_kitti_eval_match")
+    return matched[:, :, :sp.G]
+
+
+def kitti_eval_count(sp, iou, height, eval_class, neighbor_class, min_overlap, thresholds, num_thresholds):
+    """Pass 2: thresholds (2, 3, 41) f32 and num_thresholds (2, 3) int32 device tensors -> counts (2, 3, 41, 3) int32
+    (tp | fp | fn).  Asynchronous."""
+    counts = torch.empty((2, 3, 41, 3), dtype=torch.int32, device=sp.device)
+    check(lib().mv3d_kitti_eval_count(C.byref(sp.split), sp.num_pairs, _ptr(iou.contiguous()), _ptr(height), int(eval_class),
+                                      int(neighbor_class), float(min_overlap), _ptr(thresholds), _ptr(num_thresholds), _ptr(counts),
+                                      _stream()), "mv3d_kitti_eval_count")
+    return counts
