@@ -21,13 +21,15 @@ static inline int mv3d_launch_status() { return hipGetLastError() == hipSuccess 
 static inline size_t mv3d_align_up(size_t v) { return (v + MV3D_ALIGN - 1) / MV3D_ALIGN * MV3D_ALIGN; }
 
 // Score -> order-preserving u32 key, larger key = processed earlier.  NaN first (numpy's
-// ascending argsort puts NaN last; the reference reverses it).  Valid keys are >= 1, so
-// 0 can mark "not a candidate".
+// ascending argsort puts NaN last; the reference reverses it).  -0.0 and +0.0 are one score
+// (numpy compares them equal), so both get the key of +0.0 and tie by index.  Valid keys are
+// >= 1, so 0 can mark "not a candidate".
 __host__ __device__ static inline uint32_t mv3d_score_key(float s)
 {
     union { float f; uint32_t u; } c;
     c.f = s;
     if (s != s) return 0xFFFFFFFFu;
+    if (s == 0.0f) return 0x80000000u;
     return (c.u & 0x80000000u) ? ~c.u : (c.u | 0x80000000u);
 }
 

@@ -119,7 +119,12 @@ __device__ __forceinline__ bool tame(float4 b)
 //     e > nc  =>  inter - tf*den > -h*den  =>  q > mid            => suppressed
 //     e < nc  =>  q < mid                                         => not suppressed
 //     e == nc =>  undecided (q within a rounding of mid)          => the tile is redone exactly
-// (RN is monotone, so e > nc cannot come from an exact value <= nc).  Everything is f32 and
+// (RN is monotone, so e > nc cannot come from an exact value <= nc).  The e == nc branch looks
+// unreachable: nc is den scaled by a power of two, so ulp(nc) = h*ulp(den); near nc, inter is close
+// to mid*den and both inter and tf*den are multiples of 2h*ulp(den); and q == mid exactly would
+// need the f32 inter to carry the 25-bit odd factor of mid.  So the exact inter - tf*den differs
+// from nc by a nonzero multiple of ulp(nc) and never rounds onto it.  The branch stays as a guard.
+// Everything is f32 and
 // packed two columns per instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).
 //
 // One 64x64 tile, all 128 boxes valid and tame.  `lb` is the lane's own box, `s_box/s_area` the
@@ -456,7 +461,7 @@ __global__ __launch_bounds__(256) void nms_round_kernel(NmsDev d)
 //        tile(rb,c)[j] & K_rb, consumed as the K_rb are published; parked in an 8-slot LDS ring.
 //   wave 0                the greedy dependency proper: acc_c | the two youngest tiles & K, one compare,
 //        the diagonal fixed point, publish K_c.  ~45 instructions per 64-box block.
-// The stream is cut into epochs that fit the LDS arena ([0,23) and [23,32)); kept positions are
+// The stream is cut into epochs that fit the LDS arena ([0,21), [21,29), [29,32)); kept positions are
 // expanded from the K words by all waves afterwards, and the sorted `order` of the round's boxes is
 // staged in LDS so that the ROI-blob gather at the end is one dependent load deep.
 #define CHL_THREADS 512
