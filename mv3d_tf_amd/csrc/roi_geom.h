@@ -14,3 +14,15 @@ __device__ __forceinline__ RoiGeom roi_geom(const float *roi, float scale)
     g.reh = (int)roundf(__fmul_rn(roi[4], scale));
     return g;
 }
+
+// The view of a multi-view launch that workgroup `blk` belongs to: the last of the n views whose first workgroup, first(j), is <= blk
+// (view 0 starts at workgroup 0).  `first` reads wherever the launch's pack keeps the first workgroups.
+template <typename First>
+__device__ __forceinline__ int roi_view_of(const unsigned blk, const int n, const First &first)
+{
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
+        if (j < n && blk >= first(j)) k = j;
+    return k;
+}

@@ -292,16 +292,6 @@ __device__ __forceinline__ void roi_pool_fwd_xcd_pool(const BinGeom *s_g, const 
     }
 }
 
-template <int FWD_PASSES>
-__global__ __launch_bounds__(256) void roi_pool_fwd_xcd_kernel(const float *__restrict__ data, float scale, int B, int R,
-                                                               int H, int W, int C, int PH, int PW,
-                                                               const float *__restrict__ rois, float *__restrict__ top,
-                                                               int *__restrict__ argmax, int tpb_shift)
-{
-    __shared__ BinGeom s_g[FWD_PASSES * 32];
-    roi_pool_fwd_xcd_block<FWD_PASSES>(s_g, blockIdx.x, data, scale, B, R, H, W, C, PH, PW, rois, top, argmax, tpb_shift);
-}
-
 // Several views (the BEV and RGB maps of one step) in ONE launch: the second view's workgroups fill the
 // machine while the first view drains, and one kernel boundary disappears.
 struct RoiViewDev {
@@ -313,19 +303,6 @@ struct RoiViewDev {
     unsigned first_block;        // first workgroup of this view
 };
 struct RoiViewPack { RoiViewDev v[MV3D_MAX_ROI_VIEWS]; int n, PH, PW; };
-
-template <int FWD_PASSES, bool NOARG = false, int TOPT = 0>
-__global__ __launch_bounds__(256) void roi_pool_fwd_xcd_multi_kernel(RoiViewPack p)
-{
-    __shared__ BinGeom s_g[FWD_PASSES * 32];
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && blockIdx.x >= p.v[j].first_block) k = j;
-    const RoiViewDev &v = p.v[k];
-    roi_pool_fwd_xcd_block<FWD_PASSES, false, NOARG, TOPT>(s_g, blockIdx.x - v.first_block, v.data, v.scale, v.B, v.R, v.H, v.W, v.C, p.PH, p.PW, v.rois,
-                                                     v.top, v.argmax, v.tpb_shift);
-}
 
 // Forward on maps that are NOT cache-resident (mv3d_roi_pool_forward_views_cold).  The forward reads a map in 256-B
 // pieces (one XCD slice of a pixel), every workgroup behind a dependent round trip; when those pieces come from HBM the
@@ -340,10 +317,7 @@ __device__ __forceinline__ void roi_prefetch_block(unsigned *s_mask_p /* LDS, on
                                                    const unsigned block, int *sink)
 {
     unsigned &s_mask = *s_mask_p;
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && block >= pf.first_block[j]) k = j;
+    const int k = roi_view_of(block, p.n, [&](int j) { return pf.first_block[j]; });
     const RoiViewDev &v = p.v[k];
     const unsigned g = block - pf.first_block[k];
     const unsigned gpr = (unsigned)(v.W + PF_PIX - 1) / PF_PIX;
@@ -375,23 +349,51 @@ __device__ __forceinline__ void roi_prefetch_block(unsigned *s_mask_p /* LDS, on
     if (acc == 1.2345678e-30f && sink) sink[0] = 1;               // keeps the loads alive
 }
 
-// forward with the prefetch workgroups at the front of the same grid (pf.blocks is a multiple of 8: the forward's
-// workgroup -> XCD slice mapping is kept)
-template <int FWD_PASSES, bool NOARG = false, int TOPT = 0>
-__global__ __launch_bounds__(256) void roi_pool_fwd_xcd_multi_cold_kernel(RoiViewPack p, RoiPrefetchPack pf, int *sink)
+// The pair's forward (COMPACT, see below) may carry the PLAN of the pair's backward launch (roi_grad_plan.h): the first eight workgroups
+// of its grid (eight so that the workgroup -> XCD slice mapping of the pooling workgroups is kept) -- workgroup 0 estimates every map
+// tile's entry stream from the ROIs and writes the backward's work list, hot tiles cut into sub-tiles, first, into the unused quarter
+// of view 0's argmax buffer, under the pooling workgroups' shadow; the other seven return at once.
+struct RoiPlanArgs { RgtPack lay; int hot_entries, hot_max; };
+#define PAIR_PLAN_BLOCKS 8u
+// LDS of a forward workgroup: its bins' rectangles (16-byte aligned, as an array of them alone is: one wide LDS store per rectangle);
+// with PLAN, in a union with the planner's heat map and scan array (~12 KB, reserved only by the instantiations that plan)
+template <int FWD_PASSES, bool PLAN> union alignas(16) RoiFwdLds { BinGeom g[FWD_PASSES * 32]; };
+template <int FWD_PASSES> union RoiFwdLds<FWD_PASSES, true> {
+    BinGeom g[FWD_PASSES * 32];
+    struct { int heat[RGT_PLAN_TILES]; int scan[RGT_PLAN_SCAN(RGT_PLAN_THREADS)]; } plan;
+};
+
+// Every XCD-sliced forward launch: the grid is [PLAN workgroups][COLD prefetch workgroups (pf.blocks, a multiple of 8: the forward's
+// workgroup -> XCD slice mapping is kept)][the views' pooling workgroups]
+template <int FWD_PASSES, bool COMPACT, bool NOARG, int TOPT, bool COLD, bool PLAN>
+__device__ __forceinline__ void roi_pool_fwd_views(const RoiViewPack &p, const RoiPrefetchPack &pf, int *sink, const RoiPlanArgs &pl)
 {
-    __shared__ BinGeom s_g[FWD_PASSES * 32];
-    __shared__ unsigned s_mask;
-    if (blockIdx.x < pf.blocks) { roi_prefetch_block(&s_mask, p, pf, blockIdx.x, sink); return; }
-    const unsigned blk = blockIdx.x - pf.blocks;
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && blk >= p.v[j].first_block) k = j;
-    const RoiViewDev &v = p.v[k];
-    roi_pool_fwd_xcd_block<FWD_PASSES, false, NOARG, TOPT>(s_g, blk - v.first_block, v.data, v.scale, v.B, v.R, v.H, v.W, v.C, p.PH, p.PW, v.rois, v.top,
-                                                     v.argmax, v.tpb_shift);
+    __shared__ RoiFwdLds<FWD_PASSES, PLAN> lds;
+    unsigned blk = blockIdx.x;
+    if constexpr (PLAN) {
+        if (blk == 0) { rgt_plan_block<RGT_PLAN_THREADS>(pl.lay, const_cast<int4 *>(pl.lay.work), const_cast<int *>(pl.lay.n_work), pl.hot_entries, pl.hot_max, lds.plan.heat, lds.plan.scan); return; }
+        if (blk < PAIR_PLAN_BLOCKS) return;
+        blk -= PAIR_PLAN_BLOCKS;
+    }
+    if constexpr (COLD) {
+        __shared__ unsigned s_mask;
+        if (blk < pf.blocks) { roi_prefetch_block(&s_mask, p, pf, blk, sink); return; }
+        blk -= pf.blocks;
+    }
+    const RoiViewDev &v = p.v[roi_view_of(blk, p.n, [&](int j) { return p.v[j].first_block; })];
+    roi_pool_fwd_xcd_block<FWD_PASSES, COMPACT, NOARG, TOPT>(lds.g, blk - v.first_block, v.data, v.scale, v.B, v.R, v.H, v.W, v.C, p.PH, p.PW, v.rois,
+                                                             v.top, v.argmax, v.tpb_shift);
 }
+
+// the launchable kernels (their names are what profiles and bench.py's roofline entries match on)
+template <int FWD_PASSES, bool NOARG = false, int TOPT = 0>
+__global__ __launch_bounds__(256) void roi_pool_fwd_xcd_multi_kernel(RoiViewPack p) { roi_pool_fwd_views<FWD_PASSES, false, NOARG, TOPT, false, false>(p, {}, nullptr, {}); }
+template <int FWD_PASSES, bool NOARG = false, int TOPT = 0>
+__global__ __launch_bounds__(256) void roi_pool_fwd_xcd_multi_cold_kernel(RoiViewPack p, RoiPrefetchPack pf, int *sink) { roi_pool_fwd_views<FWD_PASSES, false, NOARG, TOPT, true, false>(p, pf, sink, {}); }
+template <int FWD_PASSES, bool PLAN>
+__global__ __launch_bounds__(256) void roi_pool_fwd_pair_kernel(RoiViewPack p, RoiPlanArgs pl) { roi_pool_fwd_views<FWD_PASSES, true, false, 0, false, PLAN>(p, {}, nullptr, pl); }
+template <int FWD_PASSES, bool PLAN>
+__global__ __launch_bounds__(256) void roi_pool_fwd_pair_cold_kernel(RoiViewPack p, RoiPrefetchPack pf, int *sink, RoiPlanArgs pl) { roi_pool_fwd_views<FWD_PASSES, true, false, 0, true, PLAN>(p, pf, sink, pl); }
 
 #define BWD_CHUNK 1024      // ROIs whose geometry is staged in LDS at a time
 #define BWD_PIX 4           // input pixels per workgroup (1 per wave)
@@ -599,11 +601,7 @@ __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGrad
     __shared__ int s_wcnt[4];
     __shared__ int s_cand[4][BW_CAND];
     extern __shared__ float s_carry[];                   // [pxg][64] partial sums between ROI passes (only when R > BW_CHUNK)
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && blockIdx.x >= p.v[j].first_block) k = j;
-    const RoiGradViewDev &v = p.v[k];
+    const RoiGradViewDev &v = p.v[roi_view_of(blockIdx.x, p.n, [&](int j) { return p.v[j].first_block; })];
     const int PH = p.PH, PW = p.PW, H = v.H, W = v.W, C = v.C, R = v.R;
     const unsigned b = blockIdx.x - v.first_block;
     const int slice = (int)(b % (unsigned)v.nsl);
@@ -763,10 +761,7 @@ template <bool FILL>
 __device__ __forceinline__ void roi_bwd_index_block(RoiIdxShared &S, const RoiGradPack &p, const RoiGradIdxPack &ix, const unsigned block,
                                                     const unsigned nblocks)
 {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && block >= ix.first_block[j]) k = j;
+    const int k = roi_view_of(block, p.n, [&](int j) { return ix.first_block[j]; });
     const RoiGradViewDev &v = p.v[k];
     const int PH = p.PH, PW = p.PW, H = v.H, W = v.W, R = v.R, C = v.C;
     const unsigned g = block - ix.first_block[k];
@@ -1043,57 +1038,6 @@ __global__ __launch_bounds__(256) void roi_bwd_gather_kernel(RoiGradPack p, RoiG
 //   backward  ONE launch of LDS map tiles over the work list the forward launch plans (roi_grad_tiles.hip, roi_grad_plan.h).
 // Bit-identical to the plain entries (tests/test_roi_pair.py).
 
-// the pair's forward: the multi-view pooling kernels with COMPACT argmax codes.  The first eight workgroups of the grid belong to the
-// PLAN of the pair's backward launch (roi_grad_plan.h; eight so that the workgroup -> XCD slice mapping of the pooling workgroups is kept):
-// workgroup 0 estimates every map tile's entry stream from the ROIs and writes the backward's work list -- hot tiles cut into sub-tiles,
-// first -- into the unused quarter of view 0's argmax buffer, under the pooling workgroups' shadow; the other seven return at once.
-struct RoiPlanArgs { RgtPack lay; int on, hot_entries, hot_max; };
-#define PAIR_PLAN_BLOCKS 8u
-union PairFwdLds {
-    BinGeom g[4 * 32];
-    struct { int heat[RGT_PLAN_TILES]; int scan[RGT_PLAN_SCAN(RGT_PLAN_THREADS)]; } plan;
-};
-template <int FWD_PASSES>
-__global__ __launch_bounds__(256) void roi_pool_fwd_pair_kernel(RoiViewPack p, RoiPlanArgs pl)
-{
-    __shared__ PairFwdLds lds;
-    unsigned blk = blockIdx.x;
-    if (pl.on) {
-        if (blk == 0) { rgt_plan_block<RGT_PLAN_THREADS>(pl.lay, const_cast<int4 *>(pl.lay.work), const_cast<int *>(pl.lay.n_work), pl.hot_entries, pl.hot_max, lds.plan.heat, lds.plan.scan); return; }
-        if (blk < PAIR_PLAN_BLOCKS) return;
-        blk -= PAIR_PLAN_BLOCKS;
-    }
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && blk >= p.v[j].first_block) k = j;
-    const RoiViewDev &v = p.v[k];
-    roi_pool_fwd_xcd_block<FWD_PASSES, true>(lds.g, blk - v.first_block, v.data, v.scale, v.B, v.R, v.H, v.W, v.C, p.PH, p.PW, v.rois, v.top,
-                                             v.argmax, v.tpb_shift);
-}
-
-template <int FWD_PASSES>
-__global__ __launch_bounds__(256) void roi_pool_fwd_pair_cold_kernel(RoiViewPack p, RoiPrefetchPack pf, int *sink, RoiPlanArgs pl)
-{
-    __shared__ PairFwdLds lds;
-    __shared__ unsigned s_mask;
-    unsigned blk = blockIdx.x;
-    if (pl.on) {
-        if (blk == 0) { rgt_plan_block<RGT_PLAN_THREADS>(pl.lay, const_cast<int4 *>(pl.lay.work), const_cast<int *>(pl.lay.n_work), pl.hot_entries, pl.hot_max, lds.plan.heat, lds.plan.scan); return; }
-        if (blk < PAIR_PLAN_BLOCKS) return;
-        blk -= PAIR_PLAN_BLOCKS;
-    }
-    if (blk < pf.blocks) { roi_prefetch_block(&s_mask, p, pf, blk, sink); return; }
-    blk -= pf.blocks;
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-        if (j < p.n && blk >= p.v[j].first_block) k = j;
-    const RoiViewDev &v = p.v[k];
-    roi_pool_fwd_xcd_block<FWD_PASSES, true>(lds.g, blk - v.first_block, v.data, v.scale, v.B, v.R, v.H, v.W, v.C, p.PH, p.PW, v.rois, v.top,
-                                             v.argmax, v.tpb_shift);
-}
-
 // the pair's private argmax planes (byte codes; 16-bit codes for bins of more than 255 pixels) -> the reference's int32 plane (flat
 // index inside the frame, -1 for none); tests and bench.py's verification only.  One thread per pooled value; the bin geometry as
 // the forward computes it.
@@ -1128,13 +1072,103 @@ __global__ __launch_bounds__(256) void roi_argmax_decode_kernel(const unsigned c
 }
 
 static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-static bool roi_prefetch_plan(int num_views, const mv3d_roi_view *views, RoiPrefetchPack &pf);
-
 
 // Bins per workgroup (passes x bins per pass).  A small job (one frame: 2 x 14 700 bins) wants many
 // workgroups in flight -- 2 passes (4 passes cost 5 % at batch 4); a batch of 16 frames runs ~6 % faster
 // with 4 (interleaved A/B runs; the run-to-run spread at that size is larger than the effect).
 static int fwd_passes(long long total_bins) { return total_bins > 8 * 29400 ? 4 : 2; }
+
+// The XCD-sliced forward's views (C in {256, 512, 1024}): fills p, returns the number of pooling workgroups and, in `passes`, the
+// passes per workgroup (fwd_passes of all the views' bins together)
+static unsigned roi_fwd_pack(int num_views, const mv3d_roi_view *views, int PH, int PW, RoiViewPack &p, int &passes)
+{
+    p.n = num_views; p.PH = PH; p.PW = PW;
+    long long total_bins = 0;
+    for (int k = 0; k < num_views; ++k) total_bins += (long long)views[k].num_rois * PH * PW;
+    passes = fwd_passes(total_bins);
+    unsigned blocks = 0;
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_view &w = views[k];
+        const int cv4 = w.channels / 4;
+        RoiViewDev &v = p.v[k];
+        v.data = w.bottom_data; v.rois = w.bottom_rois; v.top = w.top_data; v.argmax = w.argmax_data; v.scale = w.spatial_scale;
+        v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
+        v.tpb_shift = cv4 == 64 ? 3 : (cv4 == 128 ? 4 : 5);      // threads per bin = cv4 / 8
+        v.first_block = blocks;
+        const long long nbins = (long long)w.num_rois * PH * PW;
+        const long long per_block = (long long)passes * (256 >> v.tpb_shift);
+        blocks += (unsigned)(((nbins + per_block - 1) / per_block) * 8);
+    }
+    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
+    return blocks;
+}
+
+// The prefetch workgroups of a cold forward (a multiple of 8: the forward's workgroup -> XCD slice mapping is kept); false: none
+static bool roi_prefetch_plan(int num_views, const mv3d_roi_view *views, RoiPrefetchPack &pf)
+{
+    unsigned blocks = 0;
+    for (int k = 0; k < MV3D_MAX_ROI_VIEWS; ++k) pf.first_block[k] = 0;
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_view &w = views[k];
+        if (w.channels % 4 != 0 || !aligned16(w.bottom_data)) return false;             // a hint: nothing to do for odd layouts
+        pf.first_block[k] = blocks;
+        if (w.num_rois > 0) blocks += (unsigned)((long long)w.batch_size * w.height * ((w.width + PF_PIX - 1) / PF_PIX));
+    }
+    pf.blocks = (blocks + 7u) & ~7u;
+    return blocks > 0;
+}
+
+// One XCD-sliced forward launch: what it writes besides the maxima, and what runs in front of the pooling workgroups
+enum RoiFwdOut { ROI_OUT_ARGMAX, ROI_OUT_NOARG, ROI_OUT_F16, ROI_OUT_BF16, ROI_OUT_COMPACT };
+struct RoiFwdLaunch {
+    RoiViewPack p; unsigned blocks; int passes;       // roi_fwd_pack
+    RoiFwdOut out;
+    bool cold; RoiPrefetchPack pf;                    // roi_prefetch_plan's workgroups
+    bool plan; RoiPlanArgs pl;                        // (COMPACT only) the pair's backward plan
+};
+
+template <int P, RoiFwdOut OUT, bool COLD, bool PLAN>
+static void launch_roi_fwd_as(const RoiFwdLaunch &a, hipStream_t s)
+{
+    const dim3 grid((PLAN ? PAIR_PLAN_BLOCKS : 0u) + (COLD ? a.pf.blocks : 0u) + a.blocks);
+    constexpr bool NOARG = OUT != ROI_OUT_ARGMAX;
+    constexpr int TOPT = OUT == ROI_OUT_F16 ? 1 : (OUT == ROI_OUT_BF16 ? 2 : 0);
+    if constexpr (OUT == ROI_OUT_COMPACT && COLD)
+        hipLaunchKernelGGL((roi_pool_fwd_pair_cold_kernel<P, PLAN>), grid, dim3(256), 0, s, a.p, a.pf, (int *)nullptr, a.pl);
+    else if constexpr (OUT == ROI_OUT_COMPACT)
+        hipLaunchKernelGGL((roi_pool_fwd_pair_kernel<P, PLAN>), grid, dim3(256), 0, s, a.p, a.pl);
+    else if constexpr (COLD)
+        hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<P, NOARG, TOPT>), grid, dim3(256), 0, s, a.p, a.pf, (int *)nullptr);
+    else
+        hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<P, NOARG, TOPT>), grid, dim3(256), 0, s, a.p);
+}
+
+template <int P, RoiFwdOut OUT>
+static void launch_roi_fwd_out(const RoiFwdLaunch &a, hipStream_t s)
+{
+    if constexpr (OUT == ROI_OUT_COMPACT)                // only the pair plans
+        if (a.plan) return a.cold ? launch_roi_fwd_as<P, OUT, true, true>(a, s) : launch_roi_fwd_as<P, OUT, false, true>(a, s);
+    a.cold ? launch_roi_fwd_as<P, OUT, true, false>(a, s) : launch_roi_fwd_as<P, OUT, false, false>(a, s);
+}
+
+template <int P>
+static void launch_roi_fwd_passes(const RoiFwdLaunch &a, hipStream_t s)
+{
+    switch (a.out) {
+    case ROI_OUT_ARGMAX: return launch_roi_fwd_out<P, ROI_OUT_ARGMAX>(a, s);
+    case ROI_OUT_NOARG: return launch_roi_fwd_out<P, ROI_OUT_NOARG>(a, s);
+    case ROI_OUT_F16: return launch_roi_fwd_out<P, ROI_OUT_F16>(a, s);
+    case ROI_OUT_BF16: return launch_roi_fwd_out<P, ROI_OUT_BF16>(a, s);
+    case ROI_OUT_COMPACT: return launch_roi_fwd_out<P, ROI_OUT_COMPACT>(a, s);
+    }
+}
+
+static int launch_roi_fwd(const RoiFwdLaunch &a, void *stream)
+{
+    if (a.passes == 4) launch_roi_fwd_passes<4>(a, (hipStream_t)stream);
+    else launch_roi_fwd_passes<2>(a, (hipStream_t)stream);
+    return mv3d_launch_status();
+}
 
 extern "C" int mv3d_roi_pool_forward(const float *bottom_data, float spatial_scale, int batch_size, int num_rois,
                                      int height, int width, int channels, int pooled_height, int pooled_width,
@@ -1148,27 +1182,18 @@ extern "C" int mv3d_roi_pool_forward(const float *bottom_data, float spatial_sca
     if (num_rois == 0) return MV3D_OK;
     const bool v4 = (channels % 4 == 0) && aligned16(bottom_data) && aligned16(top_data) &&
                     (!argmax_data || aligned16(argmax_data));
+    const int cv4 = channels / 4;
+    if (v4 && (cv4 == 64 || cv4 == 128 || cv4 == 256)) {    // the XCD-sliced kernels, as a one-view launch
+        const mv3d_roi_view w = {bottom_data, bottom_rois, top_data, argmax_data, spatial_scale, batch_size, num_rois, height, width, channels};
+        RoiFwdLaunch a{};
+        a.blocks = roi_fwd_pack(1, &w, pooled_height, pooled_width, a.p, a.passes);
+        a.out = argmax_data ? ROI_OUT_ARGMAX : ROI_OUT_NOARG;
+        return launch_roi_fwd(a, stream);
+    }
     const long long items = (long long)num_rois * pooled_height * pooled_width * (channels / (v4 ? 4 : 1));
     long long blocks = (items + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;            // grid-stride the rest
     hipStream_t s = (hipStream_t)stream;
-    const int cv4 = channels / 4;
-    if (v4 && (cv4 == 64 || cv4 == 128 || cv4 == 256)) {
-        const int tpb_shift = cv4 == 64 ? 3 : (cv4 == 128 ? 4 : 5);      // threads per bin = cv4 / 8
-        const long long nbins = (long long)num_rois * pooled_height * pooled_width;
-        const int passes = fwd_passes(nbins);
-        const long long per_block = (long long)passes * (256 >> tpb_shift);
-        const long long groups = (nbins + per_block - 1) / per_block;
-        if (passes == 4)
-            hipLaunchKernelGGL(roi_pool_fwd_xcd_kernel<4>, dim3((unsigned)(groups * 8)), dim3(256), 0, s, bottom_data,
-                               spatial_scale, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
-                               bottom_rois, top_data, argmax_data, tpb_shift);
-        else
-            hipLaunchKernelGGL(roi_pool_fwd_xcd_kernel<2>, dim3((unsigned)(groups * 8)), dim3(256), 0, s, bottom_data,
-                               spatial_scale, batch_size, num_rois, height, width, channels, pooled_height, pooled_width,
-                               bottom_rois, top_data, argmax_data, tpb_shift);
-        return mv3d_launch_status();
-    }
     if (v4)
         hipLaunchKernelGGL(roi_pool_fwd_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, bottom_data, spatial_scale,
                            batch_size, num_rois, height, width, channels, pooled_height, pooled_width, bottom_rois,
@@ -1212,18 +1237,32 @@ static int roi_pool_backward_generic(const float *top_diff, float spatial_scale,
     return mv3d_launch_status();
 }
 
-static int roi_pool_forward_views_impl(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
-                                       bool cold, void *stream, int top_type = 0)
+// The per-view arguments of the multi-view forward entries.  pooled: the entry pools (the map, and the top when there are ROIs, are
+// required and R * PH * PW must fit an int; the argmax decode reads neither); argmax: the argmax plane is required when there are ROIs
+static int roi_views_check(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width, bool pooled, bool argmax)
 {
     if (num_views <= 0 || num_views > MV3D_MAX_ROI_VIEWS || !views || pooled_height <= 0 || pooled_width <= 0)
         return MV3D_ERR_INVALID_ARG;
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_view &w = views[k];
+        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 ||
+            (w.num_rois > 0 && (!w.bottom_rois || (argmax && !w.argmax_data))))
+            return MV3D_ERR_INVALID_ARG;
+        if (pooled && (!w.bottom_data || (w.num_rois > 0 && !w.top_data) ||
+                       (long long)w.num_rois * pooled_height * pooled_width > 0x7fffffffLL))
+            return MV3D_ERR_INVALID_ARG;
+    }
+    return MV3D_OK;
+}
+
+static int roi_pool_forward_views_impl(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
+                                       bool cold, void *stream, int top_type = 0)
+{
+    const int rc0 = roi_views_check(num_views, views, pooled_height, pooled_width, true, false);
+    if (rc0 != MV3D_OK) return rc0;
     bool fast = true;
     for (int k = 0; k < num_views; ++k) {
         const mv3d_roi_view &w = views[k];
-        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 || !w.bottom_data ||
-            (w.num_rois > 0 && (!w.bottom_rois || !w.top_data)) ||
-            (long long)w.num_rois * pooled_height * pooled_width > 0x7fffffffLL)
-            return MV3D_ERR_INVALID_ARG;
         const int cv4 = w.channels / 4;
         fast = fast && (w.channels % 4 == 0) && (cv4 == 64 || cv4 == 128 || cv4 == 256) && aligned16(w.bottom_data) &&
                aligned16(w.top_data) && (!w.argmax_data || aligned16(w.argmax_data));
@@ -1243,62 +1282,14 @@ static int roi_pool_forward_views_impl(int num_views, const mv3d_roi_view *views
         }
         return MV3D_OK;
     }
-    RoiViewPack p;
-    p.n = num_views; p.PH = pooled_height; p.PW = pooled_width;
-    unsigned blocks = 0;
-    long long total_bins = 0;
-    for (int k = 0; k < num_views; ++k) total_bins += (long long)views[k].num_rois * pooled_height * pooled_width;
-    const int passes = fwd_passes(total_bins);
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_view &w = views[k];
-        const int cv4 = w.channels / 4;
-        RoiViewDev &v = p.v[k];
-        v.data = w.bottom_data; v.rois = w.bottom_rois; v.top = w.top_data; v.argmax = w.argmax_data; v.scale = w.spatial_scale;
-        v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
-        v.tpb_shift = cv4 == 64 ? 3 : (cv4 == 128 ? 4 : 5);
-        v.first_block = blocks;
-        const long long nbins = (long long)w.num_rois * pooled_height * pooled_width;
-        const long long per_block = (long long)passes * (256 >> v.tpb_shift);
-        blocks += (unsigned)(((nbins + per_block - 1) / per_block) * 8);
-    }
-    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
-    if (blocks == 0) return MV3D_OK;
+    RoiFwdLaunch a{};
+    a.blocks = roi_fwd_pack(num_views, views, pooled_height, pooled_width, a.p, a.passes);
+    if (a.blocks == 0) return MV3D_OK;
     bool noarg = true;                                    // inference: no view wants the argmax plane -> the maximum-only scan
     for (int k = 0; k < num_views; ++k) noarg = noarg && !views[k].argmax_data;
-    hipStream_t s = (hipStream_t)stream;
-    RoiPrefetchPack pf;
-    if (cold && roi_prefetch_plan(num_views, views, pf)) {
-        pf.blocks = (pf.blocks + 7u) & ~7u;
-        const dim3 grid(blocks + pf.blocks);
-        if (top_type == 1) {
-            if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<4, true, 1>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-            else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<2, true, 1>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-        } else if (top_type == 2) {
-            if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<4, true, 2>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-            else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<2, true, 2>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-        } else if (noarg) {
-            if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<4, true>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-            else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<2, true>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-        } else {
-            if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<4>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-            else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_cold_kernel<2>), grid, dim3(256), 0, s, p, pf, (int *)nullptr);
-        }
-        return mv3d_launch_status();
-    }
-    if (top_type == 1) {
-        if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<4, true, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<2, true, 1>), dim3(blocks), dim3(256), 0, s, p);
-    } else if (top_type == 2) {
-        if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<4, true, 2>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<2, true, 2>), dim3(blocks), dim3(256), 0, s, p);
-    } else if (noarg) {
-        if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<4, true>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<2, true>), dim3(blocks), dim3(256), 0, s, p);
-    } else {
-        if (passes == 4) hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<4>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((roi_pool_fwd_xcd_multi_kernel<2>), dim3(blocks), dim3(256), 0, s, p);
-    }
-    return mv3d_launch_status();
+    a.out = top_type == 1 ? ROI_OUT_F16 : (top_type == 2 ? ROI_OUT_BF16 : (noarg ? ROI_OUT_NOARG : ROI_OUT_ARGMAX));
+    a.cold = cold && roi_prefetch_plan(num_views, views, a.pf);
+    return launch_roi_fwd(a, stream);
 }
 
 extern "C" int mv3d_roi_pool_forward_views(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
@@ -1318,20 +1309,6 @@ extern "C" int mv3d_roi_pool_forward_views_half(int num_views, const mv3d_roi_vi
 {
     if (top_type != 1 && top_type != 2) return MV3D_ERR_INVALID_ARG;
     return roi_pool_forward_views_impl(num_views, views, pooled_height, pooled_width, cold_maps != 0, stream, top_type);
-}
-
-static bool roi_prefetch_plan(int num_views, const mv3d_roi_view *views, RoiPrefetchPack &pf)
-{
-    unsigned blocks = 0;
-    for (int k = 0; k < MV3D_MAX_ROI_VIEWS; ++k) pf.first_block[k] = 0;
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_view &w = views[k];
-        if (w.channels % 4 != 0 || !aligned16(w.bottom_data)) return false;             // a hint: nothing to do for odd layouts
-        pf.first_block[k] = blocks;
-        if (w.num_rois > 0) blocks += (unsigned)((long long)w.batch_size * w.height * ((w.width + PF_PIX - 1) / PF_PIX));
-    }
-    pf.blocks = blocks;
-    return blocks > 0;
 }
 
 static bool bwd_fast_ok(int channels, int pooled_height, int pooled_width, int height, int width, int batch_size)
@@ -1561,14 +1538,8 @@ extern "C" size_t mv3d_roi_pool_pair_workspace_bytes(int num_views, const mv3d_r
 extern "C" int mv3d_roi_pool_forward_views_pair(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
                                                 int cold_maps, void *stream)
 {
-    if (num_views <= 0 || num_views > MV3D_MAX_ROI_VIEWS || !views || pooled_height <= 0 || pooled_width <= 0) return MV3D_ERR_INVALID_ARG;
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_view &w = views[k];
-        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 || !w.bottom_data ||
-            (w.num_rois > 0 && (!w.bottom_rois || !w.top_data || !w.argmax_data)) ||
-            (long long)w.num_rois * pooled_height * pooled_width > 0x7fffffffLL)
-            return MV3D_ERR_INVALID_ARG;
-    }
+    const int rc0 = roi_views_check(num_views, views, pooled_height, pooled_width, true, true);
+    if (rc0 != MV3D_OK) return rc0;
     mv3d_roi_grad_view g[MV3D_MAX_ROI_VIEWS];
     grad_views_of(num_views, views, g);
     if (!roi_pair_shapes(num_views, g, pooled_height, pooled_width))
@@ -1577,44 +1548,17 @@ extern "C" int mv3d_roi_pool_forward_views_pair(int num_views, const mv3d_roi_vi
         return roi_pool_forward_views_impl(num_views, views, pooled_height, pooled_width, cold_maps != 0, stream);
     for (int k = 0; k < num_views; ++k)                    // (pointer conditions: a caller that misses them gets an error, not a silent other path)
         if (!aligned16(views[k].bottom_data) || !aligned16(views[k].top_data) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
-    RoiViewPack p;
-    p.n = num_views; p.PH = pooled_height; p.PW = pooled_width;
-    unsigned blocks = 0;
-    long long total_bins = 0;
-    for (int k = 0; k < num_views; ++k) total_bins += (long long)views[k].num_rois * pooled_height * pooled_width;
-    const int passes = fwd_passes(total_bins);
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_view &w = views[k];
-        const int cv4 = w.channels / 4;
-        RoiViewDev &v = p.v[k];
-        v.data = w.bottom_data; v.rois = w.bottom_rois; v.top = w.top_data; v.argmax = w.argmax_data; v.scale = w.spatial_scale;
-        v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
-        v.tpb_shift = cv4 == 64 ? 3 : (cv4 == 128 ? 4 : 5);
-        v.first_block = blocks;
-        const long long nbins = (long long)w.num_rois * pooled_height * pooled_width;
-        const long long per_block = (long long)passes * (256 >> v.tpb_shift);
-        blocks += (unsigned)(((nbins + per_block - 1) / per_block) * 8);
-    }
-    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
-    hipStream_t s = (hipStream_t)stream;
+    RoiFwdLaunch a{};
+    a.blocks = roi_fwd_pack(num_views, views, pooled_height, pooled_width, a.p, a.passes);
+    a.out = ROI_OUT_COMPACT;
     // the plan of the pair's backward launch (the decision mv3d_launch_roi_pair_tiles takes from the same shapes)
-    RoiPlanArgs pl;
     for (int k = 0; k < num_views; ++k) g[k].argmax_data = views[k].argmax_data;
     unsigned tile_blocks = 0, plan_blocks = 0;
     bool planned = false;
-    if (!mv3d_rgt_layout(num_views, g, pooled_height, pooled_width, pl.lay, &tile_blocks, &planned, &plan_blocks, &pl.hot_entries, &pl.hot_max)) planned = false;
-    pl.on = planned ? 1 : 0;
-    const unsigned front = planned ? PAIR_PLAN_BLOCKS : 0u;
-    RoiPrefetchPack pf;
-    if (cold_maps && roi_prefetch_plan(num_views, views, pf)) {
-        pf.blocks = (pf.blocks + 7u) & ~7u;
-        if (passes == 4) hipLaunchKernelGGL(roi_pool_fwd_pair_cold_kernel<4>, dim3(front + blocks + pf.blocks), dim3(256), 0, s, p, pf, (int *)nullptr, pl);
-        else hipLaunchKernelGGL(roi_pool_fwd_pair_cold_kernel<2>, dim3(front + blocks + pf.blocks), dim3(256), 0, s, p, pf, (int *)nullptr, pl);
-        return mv3d_launch_status();
-    }
-    if (passes == 4) hipLaunchKernelGGL(roi_pool_fwd_pair_kernel<4>, dim3(front + blocks), dim3(256), 0, s, p, pl);
-    else hipLaunchKernelGGL(roi_pool_fwd_pair_kernel<2>, dim3(front + blocks), dim3(256), 0, s, p, pl);
-    return mv3d_launch_status();
+    if (!mv3d_rgt_layout(num_views, g, pooled_height, pooled_width, a.pl.lay, &tile_blocks, &planned, &plan_blocks, &a.pl.hot_entries, &a.pl.hot_max)) planned = false;
+    a.plan = planned;
+    a.cold = cold_maps && roi_prefetch_plan(num_views, views, a.pf);
+    return launch_roi_fwd(a, stream);
 }
 
 extern "C" int mv3d_roi_pool_backward_views_pair(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
@@ -1639,14 +1583,11 @@ extern "C" int mv3d_roi_pool_backward_views_pair(int num_views, const mv3d_roi_g
 extern "C" int mv3d_roi_pool_argmax_decode(int num_views, const mv3d_roi_view *views, int pooled_height, int pooled_width,
                                            int32_t *const *argmax_out, void *stream)
 {
-    if (num_views <= 0 || num_views > MV3D_MAX_ROI_VIEWS || !views || pooled_height <= 0 || pooled_width <= 0 || !argmax_out)
-        return MV3D_ERR_INVALID_ARG;
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_view &w = views[k];
-        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 ||
-            (w.num_rois > 0 && (!w.bottom_rois || !w.argmax_data || !argmax_out[k])))
-            return MV3D_ERR_INVALID_ARG;
-    }
+    const int rc0 = roi_views_check(num_views, views, pooled_height, pooled_width, false, true);
+    if (rc0 != MV3D_OK) return rc0;
+    if (!argmax_out) return MV3D_ERR_INVALID_ARG;
+    for (int k = 0; k < num_views; ++k)
+        if (views[k].num_rois > 0 && !argmax_out[k]) return MV3D_ERR_INVALID_ARG;
     mv3d_roi_grad_view g[MV3D_MAX_ROI_VIEWS];
     grad_views_of(num_views, views, g);
     const bool pair = roi_pair_shapes(num_views, g, pooled_height, pooled_width);

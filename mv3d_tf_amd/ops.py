@@ -307,6 +307,38 @@ def box_detect_tail(rois_3d, bbox_pred, num_classes):
     return cnr, pr, bv, bvr
 
 
+def _roi_views(views, pooled_height, pooled_width, outs, top_dtype=torch.float32, want_argmax=True):
+    """RoiView array of forward views [(data, rois, scale), ...] and their outputs [(top, argmax or None), ...]: `outs`, or fresh
+    (R,PH,PW,C) tensors (top in top_dtype, argmax i32 when want_argmax)"""
+    arr = (RoiView * len(views))()
+    res = []
+    for k, (data, rois, scale) in enumerate(views):
+        B, H, W, Cc = data.shape
+        R = rois.shape[0]
+        if outs is not None:
+            top, am = outs[k]
+        else:
+            top = torch.empty((R, pooled_height, pooled_width, Cc), dtype=top_dtype, device=data.device)
+            am = torch.empty((R, pooled_height, pooled_width, Cc), dtype=torch.int32, device=data.device) if want_argmax else None
+        arr[k] = RoiView(data.data_ptr(), rois.data_ptr(), top.data_ptr(), am.data_ptr() if am is not None else None, float(scale), B, R, H, W, Cc)
+        res.append((top, am))
+    return arr, res
+
+
+def _roi_grad_views(views, outs):
+    """RoiGradView array of backward views [(top_diff, rois, argmax, data_shape, scale), ...] and their bottom_diff outputs (`outs`
+    or fresh (B,H,W,C) f32)"""
+    arr = (RoiGradView * len(views))()
+    res = []
+    for k, (top_diff, rois, argmax, shape, scale) in enumerate(views):
+        B, H, W, Cc = shape
+        out = outs[k] if outs is not None else torch.empty((B, H, W, Cc), dtype=torch.float32, device=top_diff.device)
+        arr[k] = RoiGradView(out.data_ptr(), rois.data_ptr(), top_diff.data_ptr(), argmax.data_ptr(), float(scale), B,
+                             rois.shape[0], H, W, Cc)
+        res.append(out)
+    return arr, res
+
+
 def roi_pool_forward_views(views, pooled_height, pooled_width, outs=None, cold_maps=False, want_argmax=True, top_dtype=None):
     """views: list of (data (B,H,W,C), rois (R,5), spatial_scale); one launch for all of them.
     Returns [(top, argmax), ...]; pass `outs` (same structure) to reuse output tensors.  cold_maps: the maps are not
@@ -316,18 +348,7 @@ def roi_pool_forward_views(views, pooled_height, pooled_width, outs=None, cold_m
     half = top_dtype in (torch.float16, torch.bfloat16)
     if half and want_argmax:
         raise ValueError("16-bit tops are an inference output: want_argmax=False")
-    arr = (RoiView * len(views))()
-    res = []
-    for k, (data, rois, scale) in enumerate(views):
-        B, H, W, Cc = data.shape
-        R = rois.shape[0]
-        if outs is not None:
-            top, am = outs[k]
-        else:
-            top = torch.empty((R, pooled_height, pooled_width, Cc), dtype=top_dtype if half else torch.float32, device=data.device)
-            am = torch.empty((R, pooled_height, pooled_width, Cc), dtype=torch.int32, device=data.device) if want_argmax else None
-        arr[k] = RoiView(data.data_ptr(), rois.data_ptr(), top.data_ptr(), am.data_ptr() if am is not None else None, float(scale), B, R, H, W, Cc)
-        res.append((top, am))
+    arr, res = _roi_views(views, pooled_height, pooled_width, outs, top_dtype if half else torch.float32, want_argmax)
     if half:
         check(lib().mv3d_roi_pool_forward_views_half(len(views), arr, pooled_height, pooled_width, 1 if top_dtype == torch.float16 else 2,
                                                      1 if cold_maps else 0, _stream()), "mv3d_roi_pool_forward_views_half")
@@ -340,14 +361,7 @@ def roi_pool_forward_views(views, pooled_height, pooled_width, outs=None, cold_m
 def roi_pool_backward_views(views, pooled_height, pooled_width, outs=None):
     """views: list of (top_diff (R,PH,PW,C), rois (R,5), argmax (R,PH,PW,C) i32, data_shape (B,H,W,C), spatial_scale);
     RoiPoolGrad of all of them behind one call.  Returns [bottom_diff, ...]; pass `outs` to reuse output tensors."""
-    arr = (RoiGradView * len(views))()
-    res = []
-    for k, (top_diff, rois, argmax, shape, scale) in enumerate(views):
-        B, H, W, Cc = shape
-        out = outs[k] if outs is not None else torch.empty((B, H, W, Cc), dtype=torch.float32, device=top_diff.device)
-        arr[k] = RoiGradView(out.data_ptr(), rois.data_ptr(), top_diff.data_ptr(), argmax.data_ptr(), float(scale), B,
-                             rois.shape[0], H, W, Cc)
-        res.append(out)
+    arr, res = _roi_grad_views(views, outs)
     nbytes = lib().mv3d_roi_pool_backward_workspace_bytes(len(views), arr, pooled_height, pooled_width)
     ws = _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
     check(lib().mv3d_roi_pool_backward_views(len(views), arr, pooled_height, pooled_width, _ptr(ws), ws.numel(), _stream()),
@@ -360,18 +374,7 @@ def roi_pool_forward_views_pair(views, pooled_height, pooled_width, outs=None, c
     """views as roi_pool_forward_views; one launch.  Returns [(top, argmax_private), ...]: the second tensor is the pair's PRIVATE
     argmax plane (one-byte codes, 16-bit for bins of > 255 pixels, in an int32-shaped buffer for the shapes the pair's kernels take) -- hand it to
     roi_pool_backward_views_pair only; roi_pool_argmax_decode gives the reference's int32 plane."""
-    arr = (RoiView * len(views))()
-    res = []
-    for k, (data, rois, scale) in enumerate(views):
-        B, H, W, Cc = data.shape
-        R = rois.shape[0]
-        if outs is not None:
-            top, am = outs[k]
-        else:
-            top = torch.empty((R, pooled_height, pooled_width, Cc), dtype=torch.float32, device=data.device)
-            am = torch.empty((R, pooled_height, pooled_width, Cc), dtype=torch.int32, device=data.device)
-        arr[k] = RoiView(data.data_ptr(), rois.data_ptr(), top.data_ptr(), am.data_ptr(), float(scale), B, R, H, W, Cc)
-        res.append((top, am))
+    arr, res = _roi_views(views, pooled_height, pooled_width, outs)
     check(lib().mv3d_roi_pool_forward_views_pair(len(views), arr, pooled_height, pooled_width, 1 if cold_maps else 0, _stream()),
           "mv3d_roi_pool_forward_views_pair")
     return res
@@ -380,12 +383,8 @@ def roi_pool_forward_views_pair(views, pooled_height, pooled_width, outs=None, c
 def roi_pool_argmax_decode(views, res, pooled_height, pooled_width):
     """The reference's int32 argmax planes of a roi_pool_forward_views_pair call: views / res as given to / returned by it.  Tests and
     verification only."""
-    arr = (RoiView * len(views))()
-    outs = []
-    for k, ((data, rois, scale), (top, am)) in enumerate(zip(views, res)):
-        B, H, W, Cc = data.shape
-        arr[k] = RoiView(data.data_ptr(), rois.data_ptr(), top.data_ptr(), am.data_ptr(), float(scale), B, rois.shape[0], H, W, Cc)
-        outs.append(torch.empty(tuple(top.shape), dtype=torch.int32, device=data.device))
+    arr, _ = _roi_views(views, pooled_height, pooled_width, res)
+    outs = [torch.empty(tuple(top.shape), dtype=torch.int32, device=top.device) for top, _ in res]
     ptrs = (C.c_void_p * len(views))(*[o.data_ptr() for o in outs])
     check(lib().mv3d_roi_pool_argmax_decode(len(views), arr, pooled_height, pooled_width, ptrs, _stream()), "mv3d_roi_pool_argmax_decode")
     return outs
@@ -397,14 +396,7 @@ def roi_pool_backward_views_pair(views, pooled_height, pooled_width, outs=None, 
     False, which callers written against the earlier signature pass): none; a uint8 tensor of mv3d_roi_pool_pair_workspace_bytes
     bytes: handed to the entry as is, which passes it on to the plain indexed RoiPoolGrad for shapes outside the pair's kernels (same
     results either way).  Returns [bottom_diff, ...]."""
-    arr = (RoiGradView * len(views))()
-    res = []
-    for k, (top_diff, rois, argmax, shape, scale) in enumerate(views):
-        B, H, W, Cc = shape
-        out = outs[k] if outs is not None else torch.empty((B, H, W, Cc), dtype=torch.float32, device=top_diff.device)
-        arr[k] = RoiGradView(out.data_ptr(), rois.data_ptr(), top_diff.data_ptr(), argmax.data_ptr(), float(scale), B,
-                             rois.shape[0], H, W, Cc)
-        res.append(out)
+    arr, res = _roi_grad_views(views, outs)
     wp, wn = (None, 0) if workspace is None or workspace is False else (_ptr(workspace), workspace.numel())
     check(lib().mv3d_roi_pool_backward_views_pair(len(views), arr, pooled_height, pooled_width, wp, wn, _stream()),
           "mv3d_roi_pool_backward_views_pair")
