@@ -29,7 +29,7 @@ How a batch is driven (`--launch`):
       is still taken, for three steps, and reported as `secondary.resident_replay`.
 The VGG16 trunks / FC head are not part of the path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|test] [--ring R] [--batches-per-step M] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload train|test] [--ring R] [--batches-per-step M] [--dump-outputs DIR] [--full]
 
 `--dump-outputs DIR` writes, after the timed steps, what the path returned for the last batch of the last step (PathDriver.path_outputs)
 as DIR/<name>.npy; the inputs are seeded, so two runs (or two builds) with the same arguments can be compared array for array.
@@ -39,9 +39,12 @@ rank per GPU (RCCL); under the driver's own torchrun launch the ranks come from 
 shard across ranks with no data-path collective ("weak" scaling); the bracketing barrier and the max-over-ranks of the
 timed region are the only collectives of the path-only line.
 
-Rank 0 prints ONE JSON line.  `roofline` = the dominant kernel of the step (largest share of GPU time), measured live
-with HIP events on the stream it is launched on; `roofline_kernels` lists the RoiPool forward and backward launches
-separately; `cpu_baseline` = the C oracle on the same workload on the host cores (bounded sample); `secondary` holds
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the headline
+(`value`, `ms_per_step`, `config`) -- nothing else.  `--full` adds, after the timed steps: `roofline` = the dominant kernel of the
+step (largest share of GPU time), measured live with HIP events on the stream it is launched on; `roofline_kernels` lists the
+RoiPool forward and backward launches separately and the greedy NMS against its chain floor; `verified` = more batches through
+the timed driver compared bit for bit with the oracle (a mismatch exits non-zero); `cpu_baseline` = the C oracle on the same
+workload on the host cores (bounded sample); `secondary` holds
 `fresh_inputs` (the same training path on NEW frames every batch: mv3d_tf_amd.train_path.TrainPathStream, host draws in the
 loop, pipelined), the TEST-cfg (configs[4]) line, `config1_latency` (configs[1]: one frame, BEV-only RPN + NMS with the trunk on the
 MFMA convolution) and `with_trunk`, the full training step with the torch VGG16 trunks and
@@ -86,6 +89,9 @@ def parse():
     ap.add_argument("--variant", default="peaky", choices=["peaky", "rand"])
     ap.add_argument("--test-argmax", action="store_true", help="--workload test / secondary.test_cfg: RoiPool writes the op's argmax plane too "
                     "(default: the inference graph's call, top only -- nothing reads argmax without a backward pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the line can report: roofline entries, the oracle check of the timed "
+                         "driver (`verified`), the CPU baseline and the secondary legs (each of them can be left out with --no-*)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=6.0)
     ap.add_argument("--no-secondary", action="store_true")
@@ -890,6 +896,7 @@ def main():
         res["config"]["pmc_signature"] = signature
         if dumped is not None:
             res["dump_outputs"] = dumped
+    if rank == 0 and args.full:
         # one batch alone on one stream: the latency of the path
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -923,7 +930,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(ring, wl, args.cpu_seconds)
     failed_here = False
-    if not args.no_secondary and wl == "train":
+    if args.full and not args.no_secondary and wl == "train":
         sec = {}
         # The secondaries must never cost the line: an exception in one of them (they hold the only RCCL collectives of the bench at
         # N > 1) is recorded in secondary.error, and a watchdog prints the line without the unfinished part and leaves if they hang

@@ -22,9 +22,12 @@ def bench(monkeypatch):
 def test_defaults_match_the_driver_contract(bench, monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.workload, a.launch, a.streams) == (1, "train", "path", 0) and a.steps > 0 and a.warmup >= 0
+    assert a.full is False                                          # a plain run times the headline and nothing else
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"])
     a = bench.parse()
-    assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    assert (a.gpus, a.steps, a.warmup, a.full) == (8, 20, 5, False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.parse().full is True
     assert "3-view" in bench.METRIC and bench.HBM_PEAK_GBS == 8000.0
 
 
@@ -70,9 +73,9 @@ def test_pmc_traffic_only_for_the_profiled_configuration(bench, tmp_path, monkey
 
 @pytest.mark.gpu
 def test_bench_line_contract_on_the_gpu():
-    """a short run of the default workload prints ONE JSON line with the driver's keys, the roofline and the CPU baseline"""
+    """a short --full run of the default workload prints ONE JSON line with the driver's keys, the roofline and the CPU baseline"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--ring", "6",
-                          "--batches-per-step", "6", "--cpu-seconds", "2", "--no-secondary"], capture_output=True, text=True, timeout=900)
+                          "--batches-per-step", "6", "--cpu-seconds", "2", "--no-secondary", "--full"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -122,11 +125,12 @@ def test_dump_outputs_stay_in_budget_and_repeat(bench, tmp_path):
 @pytest.mark.gpu
 def test_dump_outputs_of_two_runs_are_identical(tmp_path):
     """`--dump-outputs DIR`: two runs with the same arguments write the same arrays (seeded inputs, the path's draws on the seeded
-    global generator), float32 / float64 only, <= 64 MB in all, the last batch of the last timed step"""
+    global generator), float32 / float64 only, <= 64 MB in all, the last batch of the last timed step.  Both are plain runs: their
+    line is the headline and its configuration, none of the figures that --full adds"""
     runs = []
     for name in ("a", "b"):
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ring", "4",
-                              "--batches-per-step", "5", "--no-cpu-baseline", "--no-secondary", "--dump-outputs", str(tmp_path / name)],
+                              "--batches-per-step", "5", "--dump-outputs", str(tmp_path / name)],
                              capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -134,6 +138,9 @@ def test_dump_outputs_of_two_runs_are_identical(tmp_path):
         runs.append(json.loads(lines[0]))
     d = runs[0]
     assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dump_outputs"]["batch"] == (1 + 3) * 5 - 1
+    assert (d["unit"], d["higher_is_better"], d["dtype"], d["n_gpus"]) == ("frames/s", True, "f32", 1) and "3-view" in d["metric"]
+    assert abs(d["value"] - 3 * 5 * 2 / (d["ms_per_step"] * 3e-3)) / d["value"] < 0.01            # frames / time
+    assert not {"roofline", "roofline_kernels", "verified", "cpu_baseline", "secondary"} & set(d) and "one_batch_latency_ms" not in d["config"]
     files = sorted(os.listdir(str(tmp_path / "a")))
     assert files == sorted(os.listdir(str(tmp_path / "b"))) and len(files) == len(d["dump_outputs"]["arrays"])
     assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64e6
@@ -184,12 +191,12 @@ def test_path_driver_depth8_equals_the_oracle(bench):
 
 @pytest.mark.gpu
 def test_secondary_lines_and_two_gloo_ranks_with_trunk_on_one_gpu():
-    """`bench.py --gpus 2 --dist-backend gloo` on the 1-GPU box (both ranks share the device): the sharded path-only line, the
+    """`bench.py --gpus 2 --dist-backend gloo --full` on the 1-GPU box (both ranks share the device): the sharded path-only line, the
     fresh-input line and the full training step WITH the trunks -- i.e. the bucketed gradient all-reduce overlapping a real
     backward pass of the 143 M-parameter graph has run (gloo here; RCCL needs one GPU per rank)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                          "--ring", "3", "--batches-per-step", "6", "--no-cpu-baseline", "--secondary-seconds", "0.25"], capture_output=True, text=True, timeout=1500, env=env)
+                          "--ring", "3", "--batches-per-step", "6", "--no-cpu-baseline", "--secondary-seconds", "0.25", "--full"], capture_output=True, text=True, timeout=1500, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
