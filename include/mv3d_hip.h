@@ -720,6 +720,36 @@ int mv3d_kitti_eval_count(const mv3d_kitti_split *split, long long num_pairs, co
                           int eval_class, int neighbor_class, double min_overlap, const float *thresholds_dev,
                           const int32_t *num_thresholds_dev, int32_t *counts_dev, void *stream);
 
+/* 2D detection and orientation (AP_2D, AOS) of the same split, passed next to it: the label's image boxes and alphas, the
+ * frames' DontCare boxes as CSR ranges (frame f owns dc_off[f] .. dc_off[f+1]-1; dc_off is a HOST array, validated like
+ * det_off; dc_off_dev the same on the device) and each frame's image shape.  The entries need no pair blocks: split's
+ * num_pairs is not used.  Conventions and operation order: the header comment of csrc/kitti_eval.hip, DESIGN.md §3.12.
+ *   gt_box_dev       (num_gts, 4) f32 label image box x1, y1, x2, y2; gt_alpha_dev (num_gts) f32 label alpha
+ *   dc_box_dev       (num_dontcare, 4) f32 DontCare image boxes
+ *   image_shape_dev  (num_frames, 2) int32 rows, columns of the image the detections' boxes are clipped to */
+typedef struct {
+    int32_t num_dontcare, reserved0;
+    const int32_t *dc_off;               /* host, (num_frames + 1) */
+    const int32_t *dc_off_dev;           /* device, (num_frames + 1) */
+    const float *gt_box_dev, *gt_alpha_dev, *dc_box_dev;
+    const int32_t *image_shape_dev;
+} mv3d_kitti_image_split;
+/* det_box_dev (num_dets, 4) f64 clipped image box of the LIDAR corners (all zeros when it cannot be formed); det_cam_dev
+ * (num_dets, 8) f64 camera box h, w, l, x, y, z, ry, alpha. */
+int mv3d_kitti_eval_image_boxes(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, double *det_box_dev,
+                                double *det_cam_dev, void *stream);
+/* Pass 1 with the 2D IoU: matched_dev (3 difficulties, num_gts) f32, as mv3d_kitti_eval_match. */
+int mv3d_kitti_eval_match_2d(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, const double *det_box_dev,
+                             int eval_class, int neighbor_class, double min_overlap, float *matched_dev, void *stream);
+/* Pass 2 with the 2D IoU and the DontCare rule: thresholds_dev (3, MV3D_KITTI_NUM_SAMPLE_PTS) f32, num_thresholds_dev (3) int32;
+ * counts_dev (3, MV3D_KITTI_NUM_SAMPLE_PTS, 3) int32 tp | fp | fn summed over frames and similarity_dev (num_frames, 3,
+ * MV3D_KITTI_NUM_SAMPLE_PTS) f64 per-frame sums of (1 + cos(alpha_gt - alpha_det)) / 2 over the true positives, both zeroed by
+ * the call (no float atomics: the caller sums similarity_dev over frames in frame order). */
+int mv3d_kitti_eval_count_2d(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, const double *det_box_dev,
+                             const double *det_cam_dev, int eval_class, int neighbor_class, double min_overlap,
+                             const float *thresholds_dev, const int32_t *num_thresholds_dev, int32_t *counts_dev,
+                             double *similarity_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

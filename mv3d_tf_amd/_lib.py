@@ -119,6 +119,12 @@ class KittiSplit(C.Structure):
                 ("gt_attr_dev", C.c_void_p)]
 
 
+class KittiImageSplit(C.Structure):
+    """mv3d_kitti_image_split"""
+    _fields_ = [("num_dontcare", C.c_int32), ("reserved0", C.c_int32), ("dc_off", C.c_void_p), ("dc_off_dev", C.c_void_p),
+                ("gt_box_dev", C.c_void_p), ("gt_alpha_dev", C.c_void_p), ("dc_box_dev", C.c_void_p), ("image_shape_dev", C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mv3d_version": (C.c_int, []),
@@ -223,6 +229,11 @@ _SIGS = {
     "mv3d_kitti_eval_overlaps": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, _P]),
     "mv3d_kitti_eval_match": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
     "mv3d_kitti_eval_count": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
+    "mv3d_kitti_eval_image_boxes": (C.c_int, [C.POINTER(KittiSplit), C.POINTER(KittiImageSplit), _P, _P, _P]),
+    "mv3d_kitti_eval_match_2d": (C.c_int, [C.POINTER(KittiSplit), C.POINTER(KittiImageSplit), _P, C.c_int, C.c_int, C.c_double, _P,
+                                           _P]),
+    "mv3d_kitti_eval_count_2d": (C.c_int, [C.POINTER(KittiSplit), C.POINTER(KittiImageSplit), _P, _P, C.c_int, C.c_int, C.c_double,
+                                           _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

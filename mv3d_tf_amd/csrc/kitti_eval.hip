@@ -42,6 +42,34 @@
 //   detection with !(score < t) as fp.
 // Lanes hold detections j = 64 c + lane (c < 32: at most MV3D_KITTI_MAX_DETS detections per frame); the argmax / first-index
 // reductions across lanes give exactly the sequential scan's pick.
+//
+// 2D detection and orientation (AP_2D, AOS), three more launches over the same split plus a mv3d_kitti_image_split:
+//
+//   kitti_image_box_kernel  one lane per detection: its image box (x1, y1, x2, y2) and camera box (h, w, l, x, y, z, ry, alpha).
+//   kitti_match_2d_kernel   pass 1 as kitti_match_kernel, one wave per (frame, difficulty), the 2D IoU computed on the fly from
+//                           the frame's boxes (staged in LDS per wave when the frame has <= KE2_MATCH_LDS detections).
+//   kitti_count_2d_kernel   pass 2 as kitti_count_kernel, one 256-lane workgroup per (frame, difficulty), plus the DontCare rule
+//                           and the per-frame orientation similarity sum S_f[t] (no float atomics).
+//
+// Operation order (all f64 from the f32 inputs, no fma; tests/kitti_eval_image_restatement.py follows it line by line):
+//   camera corners  R = Tr_velo_to_cam[:, :3] (calib row 3); c_j = ((R[i][0] * x_j + R[i][1] * y_j) + R[i][2] * z_j), i = 0..2
+//                   (the inverse of mv3d_gt_encode's inv(R), translation dropped as there).
+//   image box       q_r = (((P[r][0] * c0 + P[r][1] * c1) + P[r][2] * c2) + P[r][3]) with P = P2 (calib row 0); u = q0 / q2,
+//                   v = q1 / q2; x1 / x2 = min / max of the 8 u, y1 / y2 of the 8 v (k = 0 first, then strict < / >), each clipped
+//                   to [0, W - 1] / [0, H - 1] (image_shape (H, W) of the frame).  All zeros if any corner, u or v is non-finite
+//                   or any corner has c2 <= 0.
+//   camera box      mean4(a, b, c, d) = ((a + b) + (c + d)) / 4; gt_encode's local corner order: front {0,1,4,5}, back {2,3,6,7},
+//                   +w/2 side {0,3,4,7}, -w/2 side {1,2,5,6}, bottom {0,1,2,3}, top {4,5,6,7}.  (x, y, z) = mean4 of the bottom
+//                   corners; d = mean4(front) - mean4(back), l = sqrt(d.x * d.x + d.z * d.z), ry = atan2(-d.z, d.x);
+//                   e = mean4(+side) - mean4(-side), w = sqrt(e.x * e.x + e.z * e.z); h = mean4(bottom y) - mean4(top y);
+//                   alpha = ry - atan2(x, z), then alpha >= pi: - 2 pi, else alpha < -pi: + 2 pi.
+//   2D overlap      (the devkit's boxoverlap, no +1 pixel) iw = min(x2) - max(x1), ih = min(y2) - max(y1); iw <= 0 or ih <= 0 -> 0;
+//                   inter = iw * ih; A = (x2 - x1) * (y2 - y1); IoU = inter / ((A_det + A_gt) - inter); DontCare overlap =
+//                   inter / A_det.  Object boxes: the label's (x1, y1, x2, y2) in f32.
+//   statistics      the flags and passes above with the 2D IoU; a detection is ignored when y2 - y1 of its image box < MIN_HEIGHT.
+//                   Pass 2 then takes out of fp every counted fp detection whose DontCare overlap with any of the frame's DontCare
+//                   boxes is > min_overlap, and sums, over the true positives in object order, s = s + (1 + cos(a_gt - a_det)) / 2
+//                   (a_gt the label's alpha in f32) into S_f[t].
 #include "geometry.h"
 
 #define KE_MAXV 16
@@ -330,8 +358,236 @@ __global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_kernel(
     }
 }
 
+// ------------------------------------------------------------------ 2D detection and orientation
+#define KE2_MATCH_LDS 384   // detection boxes per wave staged in LDS by the 2D pass 1 (4 doubles each: 12 KiB per wave)
+#define KE2_COUNT_LDS 1024  // detection boxes of one frame staged in LDS by the 2D pass 2 (32 KiB)
+
+__device__ __forceinline__ double ke_mean4(double a, double b, double c, double d) { return ((a + b) + (c + d)) / 4.0; }
+
+__global__ __launch_bounds__(256) void kitti_image_box_kernel(
+    int F, int N, const int32_t *__restrict__ det_off, const float *__restrict__ det_cnr, const float *__restrict__ calib,
+    const int32_t *__restrict__ image_shape, double *__restrict__ det_box, double *__restrict__ det_cam)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    int lo = 0, hi = F;                                 // the frame of detection i: det_off[lo] <= i < det_off[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (det_off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const float *P = calib + 48 * (long long)lo, *Tr = P + 36;
+    const float *c = det_cnr + 24 * (long long)i;
+    double cx[8], cy[8], cz[8];
+    double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float fx = c[k], fy = c[8 + k], fz = c[16 + k];
+        ok = ok && isfinite(fx) && isfinite(fy) && isfinite(fz);
+        const double px = fx, py = fy, pz = fz;
+        cx[k] = ((double)Tr[0] * px + (double)Tr[1] * py) + (double)Tr[2] * pz;
+        cy[k] = ((double)Tr[4] * px + (double)Tr[5] * py) + (double)Tr[6] * pz;
+        cz[k] = ((double)Tr[8] * px + (double)Tr[9] * py) + (double)Tr[10] * pz;
+        const double q0 = (((double)P[0] * cx[k] + (double)P[1] * cy[k]) + (double)P[2] * cz[k]) + (double)P[3];
+        const double q1 = (((double)P[4] * cx[k] + (double)P[5] * cy[k]) + (double)P[6] * cz[k]) + (double)P[7];
+        const double q2 = (((double)P[8] * cx[k] + (double)P[9] * cy[k]) + (double)P[10] * cz[k]) + (double)P[11];
+        const double u = q0 / q2, v = q1 / q2;
+        ok = ok && cz[k] > 0.0 && isfinite(u) && isfinite(v);
+        if (k == 0) { x1 = x2 = u; y1 = y2 = v; }
+        else {
+            if (u < x1) x1 = u;
+            if (u > x2) x2 = u;
+            if (v < y1) y1 = v;
+            if (v > y2) y2 = v;
+        }
+    }
+    double *b = det_box + 4 * (long long)i;
+    if (ok) {
+        const double wm = (double)(image_shape[2 * lo + 1] - 1), hm = (double)(image_shape[2 * lo] - 1);
+        b[0] = x1 < 0.0 ? 0.0 : (x1 > wm ? wm : x1);
+        b[1] = y1 < 0.0 ? 0.0 : (y1 > hm ? hm : y1);
+        b[2] = x2 < 0.0 ? 0.0 : (x2 > wm ? wm : x2);
+        b[3] = y2 < 0.0 ? 0.0 : (y2 > hm ? hm : y2);
+    } else {
+        b[0] = b[1] = b[2] = b[3] = 0.0;
+    }
+    const double x = ke_mean4(cx[0], cx[1], cx[2], cx[3]), y = ke_mean4(cy[0], cy[1], cy[2], cy[3]);
+    const double z = ke_mean4(cz[0], cz[1], cz[2], cz[3]);
+    const double dx = ke_mean4(cx[0], cx[1], cx[4], cx[5]) - ke_mean4(cx[2], cx[3], cx[6], cx[7]);
+    const double dz = ke_mean4(cz[0], cz[1], cz[4], cz[5]) - ke_mean4(cz[2], cz[3], cz[6], cz[7]);
+    const double ex = ke_mean4(cx[0], cx[3], cx[4], cx[7]) - ke_mean4(cx[1], cx[2], cx[5], cx[6]);
+    const double ez = ke_mean4(cz[0], cz[3], cz[4], cz[7]) - ke_mean4(cz[1], cz[2], cz[5], cz[6]);
+    const double ry = atan2(-dz, dx);
+    double alpha = ry - atan2(x, z);
+    if (alpha >= M_PI) alpha -= 2.0 * M_PI;
+    else if (alpha < -M_PI) alpha += 2.0 * M_PI;
+    double *o = det_cam + 8 * (long long)i;
+    o[0] = y - ke_mean4(cy[4], cy[5], cy[6], cy[7]);
+    o[1] = sqrt(ex * ex + ez * ez);
+    o[2] = sqrt(dx * dx + dz * dz);
+    o[3] = x; o[4] = y; o[5] = z; o[6] = ry; o[7] = alpha;
+}
+
+// inter = iw * ih of detection box a (f64) and box (b0..b3) (f32 label values), 0 if they do not overlap
+__device__ __forceinline__ double ke_inter2d(const double *a, double b0, double b1, double b2, double b3)
+{
+    const double iw = (a[2] < b2 ? a[2] : b2) - (a[0] > b0 ? a[0] : b0);
+    const double ih = (a[3] < b3 ? a[3] : b3) - (a[1] > b1 ? a[1] : b1);
+    if (iw <= 0.0 || ih <= 0.0) return 0.0;
+    return iw * ih;
+}
+
+__device__ __forceinline__ double ke_iou2d(const double *a, double b0, double b1, double b2, double b3, double area_b)
+{
+    const double inter = ke_inter2d(a, b0, b1, b2, b3);
+    if (inter == 0.0) return 0.0;
+    return inter / (((a[2] - a[0]) * (a[3] - a[1]) + area_b) - inter);
+}
+
+__global__ __launch_bounds__(256) void kitti_match_2d_kernel(
+    int F, const int32_t *__restrict__ offs, const double *__restrict__ det_box, const float *__restrict__ det_score,
+    const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr, const float *__restrict__ gt_box, int Gtot,
+    int eval_class, int neighbor_class, double min_overlap, float *__restrict__ matched)
+{
+    __shared__ double s_box[4][4 * KE2_MATCH_LDS];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, task = blockIdx.x * 4 + wave;
+    const bool active = task < F * 3;
+    const int f = active ? task / 3 : 0, diff = task % 3;
+    const int32_t *det_off = offs, *gt_off = offs + (F + 1);
+    const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
+    const double *box = det_box + 4 * (long long)d0;
+    if (active && D <= KE2_MATCH_LDS) {
+        for (int p = lane; p < 4 * D; p += 64) s_box[wave][p] = box[p];
+        box = s_box[wave];
+    }
+    __syncthreads();
+    if (!active) return;
+    float *out = matched + (long long)diff * Gtot + g0;
+    const int nch = (D + 63) >> 6;
+    const double min_h = (double)c_min_height[diff];
+    uint32_t assigned = 0u;
+    for (int g = 0; g < G; ++g) {
+        const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
+        float slot = -INFINITY;
+        if (flag >= 0) {
+            const float *gb = gt_box + 4 * (long long)(g0 + g);
+            const double b0 = gb[0], b1 = gb[1], b2 = gb[2], b3 = gb[3], area_b = (b2 - b0) * (b3 - b1);
+            double best = -INFINITY;
+            int bi = INT32_MAX;
+            for (int c = 0; c < nch; ++c) {
+                const int j = 64 * c + lane;
+                if (j < D && !((assigned >> c) & 1u) && ke_iou2d(box + 4 * j, b0, b1, b2, b3, area_b) > min_overlap) {
+                    const double sc = (double)det_score[d0 + j];
+                    if (sc > -10000000.0 && sc > best) { best = sc; bi = j; }
+                }
+            }
+            ke_argmax(best, bi);
+            if (bi != INT32_MAX) {
+                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+                const bool ign_det = box[4 * bi + 3] - box[4 * bi + 1] < min_h;
+                if (flag == 0 && !ign_det) slot = det_score[d0 + bi];
+            }
+        }
+        if (lane == 0) out[g] = slot;
+    }
+}
+
+__global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_2d_kernel(
+    int F, const int32_t *__restrict__ offs, const double *__restrict__ det_box, const double *__restrict__ det_cam,
+    const float *__restrict__ det_score, const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr,
+    const float *__restrict__ gt_box, const float *__restrict__ gt_alpha, const int32_t *__restrict__ dc_off,
+    const float *__restrict__ dc_box, int eval_class, int neighbor_class, double min_overlap, const float *__restrict__ thresholds,
+    const int32_t *__restrict__ num_thr, int32_t *__restrict__ counts, double *__restrict__ sim)
+{
+    __shared__ double s_box[4 * KE2_COUNT_LDS];
+    const int task = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = task / 3, diff = task % 3;
+    const int32_t *det_off = offs, *gt_off = offs + (F + 1);
+    const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
+    const int k0 = dc_off[f], K = dc_off[f + 1] - k0;
+    int T = num_thr[diff];
+    T = T < 0 ? 0 : (T > MV3D_KITTI_NUM_SAMPLE_PTS ? MV3D_KITTI_NUM_SAMPLE_PTS : T);
+    if (D == 0 && G == 0) return;
+    const double *box = det_box + 4 * (long long)d0;
+    if (D <= KE2_COUNT_LDS) {                          // (workgroup-uniform) stage the frame's detection boxes in LDS
+        for (int p = threadIdx.x; p < 4 * D; p += 64 * KE_COUNT_WAVES) s_box[p] = box[p];
+        __syncthreads();
+        box = s_box;
+    }
+    const int nch = (D + 63) >> 6;
+    const double min_h = (double)c_min_height[diff];
+    uint32_t ign = 0u;
+    for (int c = 0; c < nch; ++c) {
+        const int j = 64 * c + lane;
+        if (j < D && box[4 * j + 3] - box[4 * j + 1] < min_h) ign |= 1u << c;
+    }
+    for (int ti = wave; ti < T; ti += KE_COUNT_WAVES) {
+        const float t = thresholds[diff * MV3D_KITTI_NUM_SAMPLE_PTS + ti];
+        uint32_t cand = 0u, assigned = 0u;
+        for (int c = 0; c < nch; ++c) {
+            const int j = 64 * c + lane;
+            if (j < D && !(det_score[d0 + j] < t)) cand |= 1u << c;
+        }
+        int tp = 0, fn = 0;
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) {
+            const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
+            if (flag < 0) continue;
+            const float *gb = gt_box + 4 * (long long)(g0 + g);
+            const double b0 = gb[0], b1 = gb[1], b2 = gb[2], b3 = gb[3], area_b = (b2 - b0) * (b3 - b1);
+            double best = -INFINITY;
+            int bi = INT32_MAX, first_ign = INT32_MAX;
+            for (int c = 0; c < nch; ++c) {
+                if (!(((cand & ~assigned) >> c) & 1u)) continue;
+                const int j = 64 * c + lane;
+                const double o = ke_iou2d(box + 4 * j, b0, b1, b2, b3, area_b);
+                if (!(o > min_overlap)) continue;
+                if ((ign >> c) & 1u) {
+                    if (first_ign == INT32_MAX) first_ign = j;
+                } else if (o > best) {
+                    best = o; bi = j;
+                }
+            }
+            ke_argmax(best, bi);
+            if (bi == INT32_MAX) bi = ke_min(first_ign);
+            if (bi == INT32_MAX) {
+                if (flag == 0) ++fn;
+            } else {
+                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+                if (flag == 0 && !(box[4 * bi + 3] - box[4 * bi + 1] < min_h)) {
+                    ++tp;
+                    s = s + (1.0 + cos((double)gt_alpha[g0 + g] - det_cam[8 * (long long)(d0 + bi) + 7])) / 2.0;
+                }
+            }
+        }
+        int fp = 0;
+        for (int c = 0; c < nch; ++c) {
+            const bool counted = (((cand & ~assigned & ~ign) >> c) & 1u) != 0u;
+            bool stuff = false;
+            if (counted) {                              // the devkit's DontCare ("stuff") rule
+                const double *a = box + 4 * (64 * c + lane);
+                const double area_a = (a[2] - a[0]) * (a[3] - a[1]);
+                for (int k = 0; k < K && !stuff; ++k) {
+                    const float *q = dc_box + 4 * (long long)(k0 + k);
+                    const double inter = ke_inter2d(a, q[0], q[1], q[2], q[3]);
+                    stuff = inter > 0.0 && inter / area_a > min_overlap;
+                }
+            }
+            fp += __popcll(__ballot(counted && !stuff));
+        }
+        if (lane == 0) {
+            int32_t *o = counts + 3 * (diff * MV3D_KITTI_NUM_SAMPLE_PTS + ti);
+            if (tp) atomicAdd(o, tp);
+            if (fp) atomicAdd(o + 1, fp);
+            if (fn) atomicAdd(o + 2, fn);
+            sim[(long long)task * MV3D_KITTI_NUM_SAMPLE_PTS + ti] = s;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ C-ABI
-static int ke_validate(const mv3d_kitti_split *s, long long num_pairs)
+static int ke_validate_split(const mv3d_kitti_split *s, bool check_pairs, long long num_pairs)
 {
     if (!s || s->num_frames < 0 || s->num_dets < 0 || s->num_gts < 0 || !s->det_off || !s->gt_off) return MV3D_ERR_INVALID_ARG;
     const int F = s->num_frames;
@@ -342,13 +598,15 @@ static int ke_validate(const mv3d_kitti_split *s, long long num_pairs)
         if (D < 0 || G < 0 || D > MV3D_KITTI_MAX_DETS) return MV3D_ERR_INVALID_ARG;
         pairs += D * G;
     }
-    if (pairs != num_pairs || pairs > INT32_MAX) return MV3D_ERR_INVALID_ARG;
+    if (check_pairs && (pairs != num_pairs || pairs > INT32_MAX)) return MV3D_ERR_INVALID_ARG;
     if (F > 0 && !s->offsets_dev) return MV3D_ERR_INVALID_ARG;
     if (s->num_dets > 0 && (!s->det_cnr_dev || !s->det_score_dev)) return MV3D_ERR_INVALID_ARG;
     if (s->num_gts > 0 && (!s->gt_cnr_dev || !s->gt_cls_dev || !s->gt_attr_dev)) return MV3D_ERR_INVALID_ARG;
     if (F > 0 && !s->calib_dev) return MV3D_ERR_INVALID_ARG;
     return MV3D_OK;
 }
+
+static int ke_validate(const mv3d_kitti_split *s, long long num_pairs) { return ke_validate_split(s, true, num_pairs); }
 
 extern "C" int mv3d_kitti_eval_overlaps(const mv3d_kitti_split *split, long long num_pairs, double *iou_dev, double *det_height_dev,
                                         void *stream)
@@ -397,5 +655,70 @@ extern "C" int mv3d_kitti_eval_count(const mv3d_kitti_split *split, long long nu
                        split->num_frames, split->offsets_dev, iou_dev, num_pairs, split->det_score_dev, det_height_dev,
                        split->gt_cls_dev, split->gt_attr_dev, eval_class, neighbor_class, min_overlap, thresholds_dev,
                        num_thresholds_dev, counts_dev);
+    return mv3d_launch_status();
+}
+
+// ------------------------------------------------------------------ C-ABI: 2D detection and orientation
+static int ke_validate_image(const mv3d_kitti_split *s, const mv3d_kitti_image_split *im)
+{
+    const int rc = ke_validate_split(s, false, 0);
+    if (rc != MV3D_OK) return rc;
+    if (!im || im->num_dontcare < 0 || !im->dc_off) return MV3D_ERR_INVALID_ARG;
+    const int F = s->num_frames;
+    if (im->dc_off[0] != 0 || im->dc_off[F] != im->num_dontcare) return MV3D_ERR_INVALID_ARG;
+    for (int f = 0; f < F; ++f)
+        if (im->dc_off[f + 1] < im->dc_off[f]) return MV3D_ERR_INVALID_ARG;
+    if (F > 0 && (!im->dc_off_dev || !im->image_shape_dev)) return MV3D_ERR_INVALID_ARG;
+    if (s->num_gts > 0 && (!im->gt_box_dev || !im->gt_alpha_dev)) return MV3D_ERR_INVALID_ARG;
+    if (im->num_dontcare > 0 && !im->dc_box_dev) return MV3D_ERR_INVALID_ARG;
+    return MV3D_OK;
+}
+
+extern "C" int mv3d_kitti_eval_image_boxes(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, double *det_box_dev,
+                                           double *det_cam_dev, void *stream)
+{
+    const int rc = ke_validate_image(split, image);
+    if (rc != MV3D_OK) return rc;
+    if (split->num_dets > 0 && (!det_box_dev || !det_cam_dev)) return MV3D_ERR_INVALID_ARG;
+    if (split->num_dets == 0) return MV3D_OK;
+    hipLaunchKernelGGL(kitti_image_box_kernel, dim3((split->num_dets + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       split->num_frames, split->num_dets, split->offsets_dev, split->det_cnr_dev, split->calib_dev,
+                       image->image_shape_dev, det_box_dev, det_cam_dev);
+    return mv3d_launch_status();
+}
+
+extern "C" int mv3d_kitti_eval_match_2d(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, const double *det_box_dev,
+                                        int eval_class, int neighbor_class, double min_overlap, float *matched_dev, void *stream)
+{
+    const int rc = ke_validate_image(split, image);
+    if (rc != MV3D_OK) return rc;
+    if (!(min_overlap >= 0.0) || (split->num_dets > 0 && !det_box_dev) || (split->num_gts > 0 && !matched_dev))
+        return MV3D_ERR_INVALID_ARG;
+    if (split->num_frames == 0 || split->num_gts == 0) return MV3D_OK;
+    const int tasks = split->num_frames * 3;
+    hipLaunchKernelGGL(kitti_match_2d_kernel, dim3((tasks + 3) / 4), dim3(256), 0, (hipStream_t)stream, split->num_frames,
+                       split->offsets_dev, det_box_dev, split->det_score_dev, split->gt_cls_dev, split->gt_attr_dev,
+                       image->gt_box_dev, split->num_gts, eval_class, neighbor_class, min_overlap, matched_dev);
+    return mv3d_launch_status();
+}
+
+extern "C" int mv3d_kitti_eval_count_2d(const mv3d_kitti_split *split, const mv3d_kitti_image_split *image, const double *det_box_dev,
+                                        const double *det_cam_dev, int eval_class, int neighbor_class, double min_overlap,
+                                        const float *thresholds_dev, const int32_t *num_thresholds_dev, int32_t *counts_dev,
+                                        double *similarity_dev, void *stream)
+{
+    const int rc = ke_validate_image(split, image);
+    if (rc != MV3D_OK) return rc;
+    if (!(min_overlap >= 0.0) || (split->num_dets > 0 && (!det_box_dev || !det_cam_dev)) || !thresholds_dev || !num_thresholds_dev ||
+        !counts_dev || (split->num_frames > 0 && !similarity_dev))
+        return MV3D_ERR_INVALID_ARG;
+    MV3D_HIP_TRY(hipMemsetAsync(counts_dev, 0, sizeof(int32_t) * 3 * MV3D_KITTI_NUM_SAMPLE_PTS * 3, (hipStream_t)stream));
+    if (split->num_frames == 0) return MV3D_OK;
+    MV3D_HIP_TRY(hipMemsetAsync(similarity_dev, 0, sizeof(double) * 3 * MV3D_KITTI_NUM_SAMPLE_PTS * (size_t)split->num_frames,
+                                (hipStream_t)stream));
+    hipLaunchKernelGGL(kitti_count_2d_kernel, dim3(split->num_frames * 3), dim3(64 * KE_COUNT_WAVES), 0, (hipStream_t)stream,
+                       split->num_frames, split->offsets_dev, det_box_dev, det_cam_dev, split->det_score_dev, split->gt_cls_dev,
+                       split->gt_attr_dev, image->gt_box_dev, image->gt_alpha_dev, image->dc_off_dev, image->dc_box_dev, eval_class,
+                       neighbor_class, min_overlap, thresholds_dev, num_thresholds_dev, counts_dev, similarity_dev);
     return mv3d_launch_status();
 }

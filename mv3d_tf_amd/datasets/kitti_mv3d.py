@@ -169,10 +169,11 @@ class kitti_mv3d(object):
         """Writes <output_dir>/results/data/<index>.txt (the reference writes under ROOT_DIR/kitti/results/<timestamp>
         instead), then scores all_boxes3D (test_net's all_boxes_cnr) against the split's label_2 files: AP_BEV and AP_3D in
         the three KITTI difficulties, printed, written to <output_dir>/kitti_ap.json and returned
-        ({(class, 'bev' | '3d', 'easy' | 'moderate' | 'hard'): AP in percent}, datasets/kitti_eval.py)."""
+        ({(class, 'bev' | '3d', 'easy' | 'moderate' | 'hard'): AP in percent}, datasets/kitti_eval.py); the metrics are
+        cfg.TEST.KITTI_EVAL_METRICS ('2d' and 'aos' add AP_2D and AOS)."""
         from .kitti_eval import evaluate_split
         self._write_kitti_results_file(all_boxes, os.path.join(output_dir, 'results', 'data'))
-        return evaluate_split(self, all_boxes3D, output_dir)
+        return evaluate_split(self, all_boxes3D, output_dir, metrics=cfg.TEST.KITTI_EVAL_METRICS)
 
     def append_flipped_images(self):
         raise NotImplementedError("cfg.TRAIN.USE_FLIPPED: the reference's flip only mirrors the 2-D image boxes "

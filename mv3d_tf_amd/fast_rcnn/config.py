@@ -48,7 +48,10 @@ cfg.TEST = _section(
     DEBUG_TIMELINE=False,
     # (not in the reference) test_net serves the 3x3 convolutions through this library's MFMA kernels: MFMA_TRUNK True with
     # PRECISION "fp32" (exact f32, the reference's precision), "fp16" or "bf16" (dense layers autocast as well)
-    MFMA_TRUNK=False, PRECISION="fp32")
+    MFMA_TRUNK=False, PRECISION="fp32",
+    # (not in the reference) what kitti_mv3d.evaluate_detections scores on the device: any of 'bev', '3d' (AP_BEV, AP_3D),
+    # '2d' (AP_2D) and 'aos' (average orientation similarity); datasets/kitti_eval.py
+    KITTI_EVAL_METRICS=('bev', '3d'))
 cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14

@@ -810,3 +810,51 @@ def kitti_eval_count(sp, iou, height, eval_class, neighbor_class, min_overlap, t
                                       int(neighbor_class), float(min_overlap), _ptr(thresholds), _ptr(num_thresholds), _ptr(counts),
                                       _stream()), "mv3d_kitti_eval_count")
     return counts
+
+
+class KittiImageSplit:
+    """The 2D side of a KittiEvalSplit for mv3d_kitti_eval_image_boxes / _match_2d / _count_2d: the label image boxes and
+    alphas, the frames' DontCare boxes (CSR dc_off) and image shapes (H, W), in ONE upload, and the C descriptor."""
+
+    def __init__(self, sp, gt_box, gt_alpha, dc_off, dc_box, image_shape):
+        dc_off = np.ascontiguousarray(dc_off, np.int32)
+        image_shape = np.ascontiguousarray(image_shape, np.int32).reshape(sp.F, 2)
+        if dc_off.size != sp.F + 1:
+            raise ValueError("KITTI evaluation: dc_off needs num_frames + 1 entries")
+        if sp.F and image_shape.min() < 1:
+            raise ValueError("KITTI evaluation: image shapes must be positive")
+        self.dc_off = dc_off                               # host copy the C-ABI validates (kept alive with the descriptor)
+        self.dev = upload_packed([dc_off, np.reshape(gt_box, (-1, 4)), np.reshape(gt_alpha, (-1,)), np.reshape(dc_box, (-1, 4)),
+                                  image_shape], sp.device)
+        self.K = int(dc_off[-1])
+        v = self.dev
+        self.image = _lib.KittiImageSplit(self.K, 0, dc_off.ctypes.data, v[0].data_ptr(), v[1].data_ptr(), v[2].data_ptr(),
+                                          v[3].data_ptr(), v[4].data_ptr())
+
+
+def kitti_eval_image_boxes(sp, im):
+    """-> det_box (N, 4) f64 clipped image box x1 y1 x2 y2, det_cam (N, 8) f64 camera box h w l x y z ry alpha.  Asynchronous."""
+    box = torch.empty((max(sp.N, 1), 4), dtype=torch.float64, device=sp.device)
+    cam = torch.empty((max(sp.N, 1), 8), dtype=torch.float64, device=sp.device)
+    check(lib().mv3d_kitti_eval_image_boxes(C.byref(sp.split), C.byref(im.image), _ptr(box), _ptr(cam), _stream()),
+          "mv3d_kitti_eval_image_boxes")
+    return box[:sp.N], cam[:sp.N]
+
+
+def kitti_eval_match_2d(sp, im, det_box, eval_class, neighbor_class, min_overlap):
+    """2D pass 1 -> matched (3, G) f32: the true-positive score of every object, -inf if none.  Asynchronous."""
+    matched = torch.empty((3, max(sp.G, 1)), dtype=torch.float32, device=sp.device)
+    check(lib().mv3d_kitti_eval_match_2d(C.byref(sp.split), C.byref(im.image), _ptr(det_box.contiguous()), int(eval_class),
+                                         int(neighbor_class), float(min_overlap), _ptr(matched), _stream()), "mv3d_kitti_eval_match_2d")
+    return matched[:, :sp.G]
+
+
+def kitti_eval_count_2d(sp, im, det_box, det_cam, eval_class, neighbor_class, min_overlap, thresholds, num_thresholds):
+    """2D pass 2: thresholds (3, 41) f32 and num_thresholds (3,) int32 device tensors -> counts (3, 41, 3) int32 (tp | fp | fn
+    after the DontCare rule), similarity (F, 3, 41) f64 per-frame orientation similarity sums.  Asynchronous."""
+    counts = torch.empty((3, 41, 3), dtype=torch.int32, device=sp.device)
+    sim = torch.empty((max(sp.F, 1), 3, 41), dtype=torch.float64, device=sp.device)
+    check(lib().mv3d_kitti_eval_count_2d(C.byref(sp.split), C.byref(im.image), _ptr(det_box.contiguous()), _ptr(det_cam.contiguous()),
+                                         int(eval_class), int(neighbor_class), float(min_overlap), _ptr(thresholds),
+                                         _ptr(num_thresholds), _ptr(counts), _ptr(sim), _stream()), "mv3d_kitti_eval_count_2d")
+    return counts, sim[:sp.F]
