@@ -511,6 +511,38 @@ int mv3d_box_detect_tail(const float *rois_3d_dev, const float *bbox_pred_dev, i
                          float *corners_dev, float *pred_cnr_r_dev, float *pred_bv_dev, float *pred_bv_r_dev,
                          void *stream);
 
+/* What test_net does with every frame behind box_detect (lib/fast_rcnn/test_mv.py:420-444, 491-501), for a batch of frames
+ * laid out as the serving step leaves them (frame f owns rows [f * rows_per_frame, (f + 1) * rows_per_frame) of every input):
+ * per foreground class j the rows r < num_rois[f] with cls_prob[r, j] > score_thresh (f32 compare; NaN drops out), in
+ * descending score order (ties by descending row), greedy NMS of pred_bv[r, 4j:4j+4] at nms_thresh (the rule of
+ * mv3d_nms_device, or of _nms if nms_strict_gt), then the cap over all classes: with more than max_per_image kept detections in
+ * the frame, every class keeps its scores >= the max_per_image-th largest kept score (ties may keep more).
+ *   cls_prob_dev (B*cap, K) f32, pred_bv_dev (B*cap, 4K), corners_dev (B*cap, 24) [the unregressed corners, shared by the
+ *   classes], pred_cnr_r_dev (B*cap, 24K) or NULL, num_rois_dev (B) i32 or NULL (= every frame has cap rows)
+ *   -> det_bv_dev (B, K, cap, 5) [x1,y1,x2,y2,score], det_cnr_dev (B, K, cap, 25) [24 corners, score], det_cnr_r_dev
+ *   (B, K, cap, 25) (required iff pred_cnr_r_dev), det_row_dev (B, K, cap) i32 source row inside the frame, det_count_dev (B, K)
+ *   i32 (class 0: 0); rows behind det_count are unspecified.  status_dev (B) i32 flag bits as for the NMS: OR-ed into, so zeroed
+ *   by the caller; bit 0 = a zero union where the reference raises ZeroDivisionError (the pair does not suppress).
+ * Kernel launches only (at most two): no allocation, memset, synchronisation or host read, so the call can be captured in a
+ * graph.  num_classes 2..8, rows_per_frame 1..2048, batch 1..65535; MV3D_ERR_INVALID_ARG otherwise or for a NULL pointer, before
+ * any HIP call.  No global scratch is needed: the workspace query returns 0 and `workspace` may be NULL. */
+typedef struct {
+    int32_t num_classes;     /* K, background class 0 included */
+    int32_t rows_per_frame;  /* cap */
+    int32_t max_per_image;   /* <= 0: no cap */
+    int32_t nms_strict_gt;   /* 0: cpu_nms rule, (double)IoU >= thresh (the parity target); 1: gpu_nms rule, IoU > thresh in f32 */
+    float score_thresh;      /* the callers pass 0.05 (lib/fast_rcnn/test_mv.py:421) */
+    int32_t reserved0;
+    double nms_thresh;       /* cfg.TEST.NMS */
+} mv3d_detect_post_params;
+
+size_t mv3d_detect_post_workspace_bytes(int batch, const mv3d_detect_post_params *p);
+int mv3d_detect_post(const float *cls_prob_dev, const float *pred_bv_dev, const float *corners_dev,
+                     const float *pred_cnr_r_dev, const int32_t *num_rois_dev, int batch,
+                     const mv3d_detect_post_params *p, float *det_bv_dev, float *det_cnr_dev, float *det_cnr_r_dev,
+                     int32_t *det_row_dev, int32_t *det_count_dev, int32_t *status_dev, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
 /* Training losses and their gradients (lib/fast_rcnn/train_mv.py:74-136), fused: losses_dev[0] = mean softmax
  * cross-entropy, losses_dev[1] = mean over rows of sum smooth-L1 (sigma = 3 in the reference) of pred - target;
  * d_*_dev (may be NULL) receive d loss / d logits and d loss / d pred.  A mean over no rows is NaN, as in TF.

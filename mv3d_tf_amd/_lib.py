@@ -24,6 +24,12 @@ class ProposalParams(C.Structure):
                 ("nms_strict_gt", C.c_int32), ("reserved0", C.c_int32), ("nms_thresh", C.c_double), ("min_size", C.c_double)]
 
 
+class DetectPostParams(C.Structure):
+    """mv3d_detect_post_params"""
+    _fields_ = [("num_classes", C.c_int32), ("rows_per_frame", C.c_int32), ("max_per_image", C.c_int32),
+                ("nms_strict_gt", C.c_int32), ("score_thresh", C.c_float), ("reserved0", C.c_int32), ("nms_thresh", C.c_double)]
+
+
 class AnchorTargetParams(C.Structure):
     """mv3d_anchor_target_params"""
     _fields_ = [("feat_stride", C.c_int32), ("clobber_positives", C.c_int32),
@@ -166,6 +172,9 @@ _SIGS = {
     "mv3d_point_cloud_2_top_shape": (C.c_int, [C.c_double] * 8 + [_P]),
     "mv3d_point_cloud_2_top_ranges": (C.c_int, [_P, C.c_int] + [C.c_double] * 8 + [_P, _P, _P]),
     "mv3d_box_detect_tail": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
+    "mv3d_detect_post_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(DetectPostParams)]),
+    "mv3d_detect_post": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(DetectPostParams), _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
+                                   _P]),
     "mv3d_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mv3d_rpn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_rcnn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),

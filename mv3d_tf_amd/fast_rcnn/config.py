@@ -51,7 +51,11 @@ cfg.TEST = _section(
     MFMA_TRUNK=False, PRECISION="fp32",
     # (not in the reference) what kitti_mv3d.evaluate_detections scores on the device: any of 'bev', '3d' (AP_BEV, AP_3D),
     # '2d' (AP_2D) and 'aos' (average orientation similarity); datasets/kitti_eval.py
-    KITTI_EVAL_METRICS=('bev', '3d'))
+    KITTI_EVAL_METRICS=('bev', '3d'),
+    # (not in the reference) frames per forward of fast_rcnn.detect_batch.test_net: 1 = the reference's frame-by-frame loop
+    # (test_mv.test_net); n > 1 groups up to n consecutive frames of equal image / BEV shapes and finishes them on the device
+    # (ops.detect_post), one read-back per group
+    BATCH_SIZE=1)
 cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14

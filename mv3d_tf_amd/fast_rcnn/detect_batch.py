@@ -1,0 +1,147 @@
+"""Test-time entry points that end in FINAL detections on the device: the per-frame tail of test_net (lib/fast_rcnn/test_mv.py:420-444,
+491-501: score cut at 0.05, NMS at cfg.TEST.NMS, cap of max_per_image) runs as ops.detect_post for a whole batch, so a batch costs one
+small read-back instead of a host round trip per frame and class.
+
+`ServeGraph(net, feed, warmup=2, post=None)`: fast_rcnn.test_mv.ServeGraph with `post=dict(max_per_image=...)` capturing ops.detect_post
+behind the box tail in the same graph; `final_detections()` returns the lists.  post=None captures exactly test_mv.ServeGraph's graph.
+`test_net(...)`: fast_rcnn.test_mv.test_net with the key cfg.TEST.BATCH_SIZE: 1 (the default) calls test_mv.test_net itself; n > 1
+serves up to n consecutive frames of equal image / BEV shapes per forward and finishes them on the device.
+fast_rcnn.test_mv keeps the reference's frame-by-frame entry points as they are."""
+import os
+import pickle
+import time
+
+import numpy as np
+import torch
+
+from .. import ops
+from . import test_mv
+from .config import cfg, get_output_dir
+from ..networks.mv3d import n_classes
+
+
+class ServeGraph(test_mv.ServeGraph):
+    """test_mv.ServeGraph whose captured step, with `post=dict(max_per_image=...)`, ends in ops.detect_post: the replay's outputs gain
+    out["post"] = (det_bv, det_cnr, det_cnr_r, det_row, det_count, status), static tensors like the others."""
+
+    def __init__(self, net, feed, warmup=2, post=None):
+        self.post = None if post is None else dict(post)
+        self._post_out = None
+        super().__init__(net, feed, warmup)
+
+    def _step(self):
+        out = super()._step()
+        if self.post is not None:
+            cap = int(out["rois_per_frame"])
+            if self._post_out is None:                          # (the graph's static outputs: allocated once, before the capture)
+                self._post_out = ops.detect_post_outputs(int(out["corners"].shape[0]) // cap, n_classes, cap, out["corners"].device)
+            out["post"] = ops.detect_post(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"], out["num_rois"], cap,
+                                          n_classes, int(self.post.get("max_per_image", 300)), cfg.TEST.NMS, out=self._post_out)
+        return out
+
+    def final_detections(self):
+        """after a replay of a graph built with `post`: per frame (dets, dets_cnr) exactly as class_detections + limit_detections return
+        them (dets[0] == [], class j (N,5) / (N,25) f32) -- the score cut, NMS and cap ran inside the graph; the ONE host round trip is the
+        counts, the status words and the rows in front of the counts"""
+        if self.post is None:
+            raise ValueError("final_detections() needs ServeGraph(..., post=dict(max_per_image=...))")
+        self.stream.synchronize()
+        if int(self.out["status"].max().item()) & 1:
+            raise ZeroDivisionError("float division")
+        return ops.detect_post_lists(self.out["post"])
+
+
+def _load_frame(imdb, i):
+    """(image, BEV map, calib) of frame i of a duck-typed imdb (see test_mv.test_net)"""
+    if hasattr(imdb, "image_at"):
+        im, bv = imdb.image_at(i), imdb.bv_at(i)
+    else:
+        bv = np.load(imdb.lidar_path_at(i))
+        path = imdb.image_path_at(i)
+        if path.endswith(".npy"):
+            im = np.load(path)
+        else:
+            from PIL import Image                               # (the reference uses cv2.imread: BGR)
+            im = np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
+    return im, bv, imdb.calib_at(i)
+
+
+def iter_frame_groups(keys, batch_size):
+    """Groups of CONSECUTIVE frame indices whose keys (the frames' image and BEV shapes) are equal, at most `batch_size` per group:
+    frames are never padded or reordered, a change of shape just ends the group.  Lazy: `keys` may load the frames as it goes."""
+    group, group_key = [], None
+    for i, key in enumerate(keys):
+        if group and (key != group_key or len(group) >= batch_size):
+            yield group
+            group = []
+        group.append(i)
+        group_key = key
+    if group:
+        yield group
+
+
+def group_frames(keys, batch_size):
+    return list(iter_frame_groups(keys, batch_size))
+
+
+def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
+    """test_mv.test_net with cfg.TEST.BATCH_SIZE (not in the reference).  1: test_mv.test_net, untouched.  n > 1: one eager forward
+    with fixed ROI rows per group of equally shaped consecutive frames (`iter_frame_groups`), the box tail and ops.detect_post on the
+    device, ONE read-back of the final detections per group.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
+    group) and the evaluate_detections call are test_mv.test_net's."""
+    batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
+    if batch_size <= 1:
+        return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
+    if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
+        net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
+        net.mfma_trunk = bool(cfg.TEST.get("MFMA_TRUNK", False))
+    num_images = len(imdb.image_index)
+    all_boxes = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
+    all_boxes_cnr = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
+    output_dir = get_output_dir(imdb, weights_filename)
+    pending = {}
+
+    def keys():
+        for i in range(num_images):
+            pending[i] = _load_frame(imdb, i)
+            yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
+
+    t_detect = t_misc = 0.0
+    for group in iter_frame_groups(keys(), batch_size):
+        ims, bvs, calibs = zip(*(pending.pop(i) for i in group))
+        B = len(group)
+        t0 = time.time()
+        im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
+        bv_blob = np.stack([np.asarray(bv, np.float32) for bv in bvs])
+        im_info = np.array([[bv_blob.shape[1], bv_blob.shape[2], 1]] * B, dtype=np.float32)
+        net.fixed_rois = True
+        try:
+            with torch.no_grad():
+                L = net.forward({"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
+                                 "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0})
+                cnr, _, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
+        finally:
+            net.fixed_rois = False
+        torch.cuda.synchronize()                                       # (for the timer only: one per group)
+        t1 = time.time()
+        post = ops.detect_post(L["cls_prob"], pred_bv, cnr, None, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
+                               max_per_image, cfg.TEST.NMS)
+        if int(L["rois_status"].max().item()) & 1:
+            raise ZeroDivisionError("float division")
+        frames = ops.detect_post_lists(post)
+        t2 = time.time()
+        for i, (dets, dets_cnr) in zip(group, frames):
+            for j in range(1, imdb.num_classes):
+                all_boxes[j][i] = dets[j]
+                all_boxes_cnr[j][i] = dets_cnr[j]
+            t_detect += (t1 - t0) / B
+            t_misc += (t2 - t1) / B
+            print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, t_detect / (i + 1), t_misc / (i + 1)))
+    with open(os.path.join(output_dir, 'detections.pkl'), 'wb') as f:
+        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
+    with open(os.path.join(output_dir, 'detections_cnr.pkl'), 'wb') as f:
+        pickle.dump(all_boxes_cnr, f, pickle.HIGHEST_PROTOCOL)
+    print('Evaluating detections')
+    imdb.evaluate_detections(all_boxes, all_boxes_cnr, output_dir)
+    return all_boxes, all_boxes_cnr
+

@@ -307,6 +307,66 @@ def box_detect_tail(rois_3d, bbox_pred, num_classes):
     return cnr, pr, bv, bvr
 
 
+def detect_post_outputs(B, K, cap, dev, with_cnr_r=True):
+    """Caller-owned outputs of detect_post: (det_bv (B,K,cap,5), det_cnr (B,K,cap,25), det_cnr_r (B,K,cap,25) | None, det_row (B,K,cap)
+    i32, det_count (B,K) i32, status (B) i32).  det_count and status are views of ONE buffer (one small read-back)."""
+    tail = torch.zeros((B * K + B,), dtype=torch.int32, device=dev)
+    return (torch.empty((B, K, cap, 5), dtype=torch.float32, device=dev), torch.empty((B, K, cap, 25), dtype=torch.float32, device=dev),
+            torch.empty((B, K, cap, 25), dtype=torch.float32, device=dev) if with_cnr_r else None,
+            torch.empty((B, K, cap), dtype=torch.int32, device=dev), tail[:B * K].view(B, K), tail[B * K:])
+
+
+def detect_post(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame, num_classes, max_per_image, nms_thresh,
+                score_thresh=0.05, use_gpu_nms=None, out=None):
+    """The per-frame tail of test_net (score cut, NMS, cap over all classes; lib/fast_rcnn/test_mv.py:420-444, 491-501) for a batch
+    of B = rows / rows_per_frame frames on the device: mv3d_detect_post.  cls_prob (B*cap, K) (16-bit is widened, exactly),
+    pred_bv (B*cap, 4K), corners (B*cap, 24), pred_cnr_r (B*cap, 24K) or None, num_rois (B) i32 or None.  `use_gpu_nms`
+    (default: cfg.USE_GPU_NMS) selects the NMS rule the way nms_wrapper.py:13-21 does.  Returns `out` =
+    detect_post_outputs(...); status is zeroed here (the kernels OR into it).  Asynchronous: kernel launches only."""
+    if use_gpu_nms is None:
+        from .fast_rcnn.config import cfg
+        use_gpu_nms = bool(cfg.USE_GPU_NMS)
+    K, cap = int(num_classes), int(rows_per_frame)
+    if cap <= 0 or cls_prob.shape[0] % cap:
+        check(_lib.ERR_INVALID_ARG, "detect_post: rows are not a multiple of rows_per_frame")
+    B = cls_prob.shape[0] // cap
+    dev = cls_prob.device
+    cls_prob = cls_prob.float().contiguous()
+    pred_bv, corners = pred_bv.float().contiguous(), corners.float().contiguous()
+    if pred_cnr_r is not None:
+        pred_cnr_r = pred_cnr_r.float().contiguous()
+    if (cls_prob.shape[1], pred_bv.shape, corners.shape) != (K, (B * cap, 4 * K), (B * cap, 24)) or \
+            (pred_cnr_r is not None and pred_cnr_r.shape != (B * cap, 24 * K)) or \
+            (num_rois is not None and (num_rois.dtype != torch.int32 or num_rois.numel() != B)):
+        check(_lib.ERR_INVALID_ARG, "detect_post: input shapes")
+    if out is None:
+        out = detect_post_outputs(B, K, cap, dev, pred_cnr_r is not None)
+    det_bv, det_cnr, det_cnr_r, det_row, det_count, status = out
+    status.zero_()
+    params = _lib.DetectPostParams(K, cap, int(max_per_image), 1 if use_gpu_nms else 0, float(score_thresh), 0, float(nms_thresh))
+    rc = lib().mv3d_detect_post(_ptr(cls_prob), _ptr(pred_bv), _ptr(corners), _ptr(pred_cnr_r), _ptr(num_rois), B, C.byref(params),
+                                _ptr(det_bv), _ptr(det_cnr), _ptr(det_cnr_r if pred_cnr_r is not None else None), _ptr(det_row),
+                                _ptr(det_count), _ptr(status), None, 0, _stream())
+    check(rc, "mv3d_detect_post")
+    return out
+
+
+def detect_post_lists(out, with_cnr_r=False):
+    """The ONE read-back behind detect_post: synchronises, reads det_count | status, raises ZeroDivisionError where the reference's NMS
+    does, copies the rows in front of the counts and returns per frame (dets, dets_cnr[, dets_cnr_r]) as class_detections +
+    limit_detections build them: index 0 an empty list, class j (N,5) / (N,25) f32."""
+    det_bv, det_cnr, det_cnr_r, _, det_count, status = out
+    B, K, cap = det_count.shape[0], det_count.shape[1], det_bv.shape[2]
+    cnt = det_count.cpu().numpy()
+    st = status.cpu().numpy()
+    if int(st.max()) & 1:
+        raise ZeroDivisionError("float division")
+    top = max(int(cnt.max()), 1)                              # rows behind the largest count never travel
+    srcs = [det_bv, det_cnr] + ([det_cnr_r] if with_cnr_r else [])
+    host = [t[:, :, :top].cpu().numpy() for t in srcs]
+    return [tuple([[]] + [h[f, j, :cnt[f, j]].copy() for j in range(1, K)] for h in host) for f in range(B)]
+
+
 def _roi_views(views, pooled_height, pooled_width, outs, top_dtype=torch.float32, want_argmax=True):
     """RoiView array of forward views [(data, rois, scale), ...] and their outputs [(top, argmax or None), ...]: `outs`, or fresh
     (R,PH,PW,C) tensors (top in top_dtype, argmax i32 when want_argmax)"""
