@@ -782,6 +782,39 @@ int mv3d_kitti_eval_count_2d(const mv3d_kitti_split *split, const mv3d_kitti_ima
                              const float *thresholds_dev, const int32_t *num_thresholds_dev, int32_t *counts_dev,
                              double *similarity_dev, void *stream);
 
+/* ------------------------------------------------------------------ proposal recall (csrc/proposal_recall.hip)
+ * lib/datasets/imdb.py:162-196 (evaluate_recall's greedy matching of proposals to objects) over a whole split and several
+ * proposal limits in ONE launch.  Frames are CSR ranges: frame f owns boxes box_off[f] .. box_off[f+1]-1 and objects
+ * gt_off[f] .. gt_off[f+1]-1.  box_off / gt_off are HOST arrays, validated before any device call (start at 0, monotone, end
+ * at num_boxes / num_gts, at most MV3D_RECALL_MAX_GT objects per frame, num_boxes < 2^31); box_off_dev / gt_off_dev hold the
+ * same on the device.  Contract and operation order: the header comment of csrc/proposal_recall.hip, DESIGN.md §3.14.
+ *   boxes_dev       (num_boxes, 4) f32 x1, y1, x2, y2 in the reference's proposal order; gt_dev (num_gts, 4) f32
+ *   limits_dev      (num_limits) int32: only the first limits[l] boxes of every frame are matched, <= 0 means all of them
+ *   thresholds_dev  (num_thresholds) f64 IoU thresholds
+ *   short_mode      a frame with 0 < n < G_f boxes (the reference fails its assert there): MV3D_RECALL_SHORT_ASSERT sets
+ *                   MV3D_RECALL_STATUS_SHORT and records -1.0 for the rounds without a box; MV3D_RECALL_SHORT_ZERO (this
+ *                   library's definition, not the reference's) records 0.0 for them and sets nothing */
+#define MV3D_RECALL_MAX_GT 256
+#define MV3D_RECALL_SHORT_ASSERT 0
+#define MV3D_RECALL_SHORT_ZERO 1
+#define MV3D_RECALL_STATUS_SHORT 1
+#define MV3D_RECALL_STATUS_NONFINITE 2
+typedef struct {
+    int32_t num_frames, num_gts, num_limits, num_thresholds, short_mode, reserved0;
+    long long num_boxes;
+    const int32_t *box_off, *gt_off;           /* host, (num_frames + 1) each */
+    const int32_t *box_off_dev, *gt_off_dev;   /* device, (num_frames + 1) each */
+    const float *boxes_dev, *gt_dev;
+    const int32_t *limits_dev;
+    const double *thresholds_dev;
+} mv3d_recall_split;
+/* gt_overlaps_dev (num_limits, num_gts) f64: frame f's block holds the overlap recorded in round j at position gt_off[f] + j
+ * (-1.0 throughout for a frame without boxes, which the reference skips); counts_dev (num_limits, num_thresholds) int32: the
+ * number of recorded overlaps >= thresholds[t] over the frames that were not skipped, zeroed by the call, integer atomics
+ * only; status_dev (num_frames) int32, zeroed by the call: MV3D_RECALL_STATUS_* bits, over all limits.  Asynchronous. */
+int mv3d_proposal_recall(const mv3d_recall_split *split, double *gt_overlaps_dev, int32_t *counts_dev, int32_t *status_dev,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

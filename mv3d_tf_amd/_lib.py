@@ -131,6 +131,14 @@ class KittiImageSplit(C.Structure):
                 ("gt_box_dev", C.c_void_p), ("gt_alpha_dev", C.c_void_p), ("dc_box_dev", C.c_void_p), ("image_shape_dev", C.c_void_p)]
 
 
+class RecallSplit(C.Structure):
+    """mv3d_recall_split"""
+    _fields_ = [("num_frames", C.c_int32), ("num_gts", C.c_int32), ("num_limits", C.c_int32), ("num_thresholds", C.c_int32),
+                ("short_mode", C.c_int32), ("reserved0", C.c_int32), ("num_boxes", C.c_longlong), ("box_off", C.c_void_p),
+                ("gt_off", C.c_void_p), ("box_off_dev", C.c_void_p), ("gt_off_dev", C.c_void_p), ("boxes_dev", C.c_void_p),
+                ("gt_dev", C.c_void_p), ("limits_dev", C.c_void_p), ("thresholds_dev", C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mv3d_version": (C.c_int, []),
@@ -243,6 +251,7 @@ _SIGS = {
                                            _P]),
     "mv3d_kitti_eval_count_2d": (C.c_int, [C.POINTER(KittiSplit), C.POINTER(KittiImageSplit), _P, _P, C.c_int, C.c_int, C.c_double,
                                            _P, _P, _P, _P, _P]),
+    "mv3d_proposal_recall": (C.c_int, [C.POINTER(RecallSplit), _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

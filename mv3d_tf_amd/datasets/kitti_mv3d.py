@@ -13,8 +13,8 @@ How it is done here: a frame's label file is parsed as ONE token table (no per-o
 objects go to the device in one upload, `mv3d_gt_encode` (csrc/gt_encode.hip) computes camera corners, LIDAR corners, LIDAR
 box and BEV box for all objects at once, and one download brings the four arrays back.  Pinned bit for bit (values and
 dtypes) by tests/golden/kitti_label.npz, which the reference's own loader produced.  `evaluate_detections` writes the
-reference's result files and scores the detections on the device (datasets/kitti_eval.py); caching and the proposal-recall
-statistics of the reference class are out of scope."""
+reference's result files and scores the detections on the device (datasets/kitti_eval.py); `evaluate_recall` is the base
+class's proposal-recall statistics on the device (datasets/proposal_recall.py); caching is out of scope."""
 import os
 
 import numpy as np
@@ -174,6 +174,13 @@ class kitti_mv3d(object):
         from .kitti_eval import evaluate_split
         self._write_kitti_results_file(all_boxes, os.path.join(output_dir, 'results', 'data'))
         return evaluate_split(self, all_boxes3D, output_dir, metrics=cfg.TEST.KITTI_EVAL_METRICS)
+
+    def evaluate_recall(self, candidate_boxes=None, thresholds=None, area='all', limit=None, space='bv'):
+        """lib/datasets/imdb.py:121 on the device (datasets/proposal_recall.py): recall of `candidate_boxes` (per-frame boxes in
+        proposal order, or what rpn_msr.generate.imdb_proposals returns) against this split's objects, in BEV ('bv') or in the
+        image ('image').  candidate_boxes=None takes the roidb's own class-0 boxes as the reference does; this roidb has none."""
+        from .proposal_recall import evaluate_recall
+        return evaluate_recall(self.roidb, candidate_boxes, thresholds=thresholds, area=area, limit=limit, space=space)
 
     def append_flipped_images(self):
         raise NotImplementedError("cfg.TRAIN.USE_FLIPPED: the reference's flip only mirrors the 2-D image boxes "

@@ -918,3 +918,134 @@ def kitti_eval_count_2d(sp, im, det_box, det_cam, eval_class, neighbor_class, mi
                                          int(eval_class), int(neighbor_class), float(min_overlap), _ptr(thresholds),
                                          _ptr(num_thresholds), _ptr(counts), _ptr(sim), _stream()), "mv3d_kitti_eval_count_2d")
     return counts, sim[:sp.F]
+
+
+# ------------------------------------------------------------------ proposal recall (csrc/proposal_recall.hip, datasets/proposal_recall.py)
+def _exact_f32(a, what):
+    """numpy array / tensor -> the same values in f32; another dtype only where the conversion loses nothing."""
+    if isinstance(a, torch.Tensor):
+        if a.dtype == torch.float32:
+            return a
+        b = a.to(torch.float32)
+        same = (b.to(a.dtype) == a) | ((a != a) if a.dtype.is_floating_point else torch.zeros_like(b, dtype=torch.bool))
+        if not bool(same.all()):
+            raise ValueError(f"proposal recall: {what} of dtype {a.dtype} are not exactly representable in float32")
+        return b
+    a = np.asarray(a)
+    if a.dtype == np.float32:
+        return a
+    if a.dtype.kind not in "fiub":
+        raise ValueError(f"proposal recall: {what} of dtype {a.dtype}")
+    b = a.astype(np.float32)
+    if not np.array_equal(b.astype(a.dtype), a, equal_nan=a.dtype.kind == "f"):
+        raise ValueError(f"proposal recall: {what} of dtype {a.dtype} are not exactly representable in float32")
+    return b
+
+
+def _recall_boxes(a, what):
+    """(N, 4) f32 boxes from (N, 4) or (N, 5) rows (a `rois` blob carries the batch index in front)"""
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+    if a.ndim != 2 and a.shape[0] == 0:
+        a = a.reshape(0, 4)
+    if a.ndim != 2 or a.shape[1] not in (4, 5):
+        raise ValueError(f"proposal recall: {what} must be (N, 4) or (N, 5), got {tuple(a.shape)}")
+    return _exact_f32(a[:, 1:5] if a.shape[1] == 5 else a, what)
+
+
+class RecallSplit:
+    """A split on the device for mv3d_proposal_recall: frame f owns boxes box_off[f] .. box_off[f+1]-1 and objects gt_off[f] ..
+    gt_off[f+1]-1.  boxes / gt: numpy arrays or device tensors, f32 (another dtype only if it converts exactly), boxes with or
+    without the leading batch column of a `rois` blob.  Everything that comes from the host goes up in ONE packed upload."""
+
+    def __init__(self, boxes, box_off, gt, gt_off, device):
+        box_off = np.ascontiguousarray(box_off, np.int64)
+        gt_off = np.ascontiguousarray(gt_off, np.int64)
+        if box_off.ndim != 1 or box_off.size < 1 or box_off.shape != gt_off.shape:
+            raise ValueError("proposal recall: box_off and gt_off need num_frames + 1 entries each")
+        if box_off[-1] > np.iinfo(np.int32).max:
+            raise ValueError("proposal recall: more than 2^31 - 1 boxes in one split")
+        boxes, gt = _recall_boxes(boxes, "boxes"), _recall_boxes(gt, "objects")
+        if boxes.shape[0] != box_off[-1] or gt.shape[0] != gt_off[-1]:
+            raise ValueError("proposal recall: the offsets do not end at the number of boxes / objects")
+        self.box_off, self.gt_off = box_off.astype(np.int32), gt_off.astype(np.int32)     # host copies the C-ABI validates
+        self.device = device
+        self.F, self.N, self.G = box_off.size - 1, int(box_off[-1]), int(gt_off[-1])
+        host = [self.box_off, self.gt_off] + [a for a in (boxes, gt) if not isinstance(a, torch.Tensor)]
+        up = upload_packed(host, device)
+        self.box_off_dev, self.gt_off_dev = up[0], up[1]
+        rest = list(up[2:])
+        self.boxes, self.gt = (a.to(device).contiguous() if isinstance(a, torch.Tensor) else rest.pop(0) for a in (boxes, gt))
+
+
+def recall_limits(limits):
+    """limits of evaluate_recall -> int32 array for the device, None -> 0 ("all of the frame's boxes")"""
+    out = []
+    for v in limits:
+        if v is not None and (int(v) != v or int(v) < 1):
+            raise ValueError(f"proposal recall: a limit is None or an integer >= 1, got {v!r}")
+        out.append(0 if v is None else int(v))
+    if not out:
+        raise ValueError("proposal recall: no limit given")
+    return np.array(out, np.int32)
+
+
+def default_recall_thresholds():
+    return np.arange(0.5, 0.95 + 1e-5, 0.05)              # lib/datasets/imdb.py:199-201
+
+
+class _RecallOut(tuple):
+    pack = None                                             # the one buffer the three tensors are views of
+
+
+def proposal_recall(split, limits=(None,), thresholds=None, on_short='raise'):
+    """-> (gt_overlaps (L, G) f64, counts (L, T) int32, status (F) int32), device tensors: the greedy matching of
+    lib/datasets/imdb.py:162-196 for every frame and every limit in one launch (csrc/proposal_recall.hip).  on_short: frames with
+    fewer boxes than objects, 'raise' = the reference's failing assert (status bit MV3D_RECALL_STATUS_SHORT, see
+    `proposal_recall_host`), 'zero' = this library's definition, NOT the reference's: the objects left over record 0.0.
+    Asynchronous."""
+    if on_short not in ('raise', 'zero'):
+        raise ValueError("proposal recall: on_short is 'raise' or 'zero'")
+    lim = recall_limits(limits)
+    thr = np.ascontiguousarray(default_recall_thresholds() if thresholds is None else thresholds, np.float64).reshape(-1)
+    L, T, dev = lim.size, thr.size, split.device
+    d_lim = torch.from_numpy(lim).to(dev)
+    d_thr = torch.from_numpy(thr).to(dev) if T else None
+    nb = [8 * L * split.G, 4 * L * T, 4 * split.F]
+    pack = torch.empty((max(sum(nb), 8),), dtype=torch.uint8, device=dev)
+    ov = pack[:nb[0]].view(torch.float64).view(L, split.G)
+    counts = pack[nb[0]:nb[0] + nb[1]].view(torch.int32).view(L, T)
+    status = pack[nb[0] + nb[1]:sum(nb)].view(torch.int32)
+    desc = _lib.RecallSplit(split.F, split.G, L, T, 1 if on_short == 'zero' else 0, 0, split.N, split.box_off.ctypes.data,
+                            split.gt_off.ctypes.data, split.box_off_dev.data_ptr(), split.gt_off_dev.data_ptr(),
+                            split.boxes.data_ptr() if split.N else None, split.gt.data_ptr() if split.G else None, d_lim.data_ptr(),
+                            d_thr.data_ptr() if T else None)
+    check(lib().mv3d_proposal_recall(C.byref(desc), _ptr(ov) if split.G else None, _ptr(counts) if T else None,
+                                     _ptr(status) if split.F else None, _stream()), "mv3d_proposal_recall")
+    out = _RecallOut((ov, counts, status))
+    out.pack = pack
+    return out
+
+
+def proposal_recall_host(out):
+    """The ONE read-back of proposal_recall's result -> numpy (gt_overlaps, counts, status).  Raises AssertionError if a frame
+    had fewer boxes than objects under on_short='raise' (the reference's `assert(gt_ovr >= 0)`, imdb.py:186) and ValueError if
+    a frame holds a non-finite coordinate."""
+    ov, counts, status = out
+    pack = getattr(out, "pack", None)
+    if pack is None:
+        h_ov, h_counts, h_status = ov.cpu().numpy(), counts.cpu().numpy(), status.cpu().numpy()
+    else:
+        host = pack.cpu().numpy()
+        n0, n1 = 8 * ov.numel(), 4 * counts.numel()
+        h_ov = host[:n0].view(np.float64).reshape(ov.shape)
+        h_counts = host[n0:n0 + n1].view(np.int32).reshape(counts.shape)
+        h_status = host[n0 + n1:n0 + n1 + 4 * status.numel()].view(np.int32)
+    bad = np.flatnonzero(h_status & 2)
+    if bad.size:
+        raise ValueError(f"proposal recall: non-finite box or object coordinate in frame {int(bad[0])} ({bad.size} frames)")
+    short = np.flatnonzero(h_status & 1)
+    if short.size:
+        raise AssertionError(f"proposal recall: frame {int(short[0])} has fewer boxes than objects ({short.size} frames): "
+                             "lib/datasets/imdb.py:186 assert(gt_ovr >= 0); on_short='zero' counts the objects left over as misses")
+    return h_ov, h_counts, h_status

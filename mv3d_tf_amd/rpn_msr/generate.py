@@ -1,0 +1,60 @@
+"""Collect a split's RPN proposals (lib/rpn_msr/generate.py:91 `imdb_proposals`, Caffe code in the reference: it runs `net.forward`
+per image and keeps `rois[:, 1:]`).  Here the network runs over groups of equally shaped consecutive frames
+(fast_rcnn.detect_batch.iter_frame_groups, cfg.TEST.BATCH_SIZE frames per forward, fixed ROI rows), every frame's first num_rois
+rows of rois[0] (BEV) and rois[1] (image) stay on the device until the last forward is queued; only then are they read back.  The result feeds datasets.proposal_recall.evaluate_recall."""
+import os
+import pickle
+
+import numpy as np
+import torch
+
+from ..fast_rcnn.config import cfg, get_output_dir
+from ..fast_rcnn.detect_batch import _load_frame, iter_frame_groups
+
+
+def imdb_proposals(sess, net, imdb):
+    """Generate RPN proposals on all frames of an imdb -> {'bv': [...], 'image': [...]}: per frame the (R, 4) f32 boxes in the
+    proposal layer's order (descending score after NMS), also written to <get_output_dir(imdb)>/proposals.pkl.  `sess` is not
+    used (the reference's TensorFlow session, kept for the call's shape)."""
+    batch_size = max(int(cfg.TEST.get("BATCH_SIZE", 1)), 1)
+    if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
+        net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
+        net.mfma_trunk = bool(cfg.TEST.get("MFMA_TRUNK", False))
+    num_images = len(imdb.image_index)
+    pending = {}
+
+    def keys():
+        for i in range(num_images):
+            pending[i] = _load_frame(imdb, i)
+            yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
+
+    kept = []                                                  # per group: (frames, cap, rois_bv, rois_img, num_rois, status), on the device
+    for group in iter_frame_groups(keys(), batch_size):
+        ims, bvs, calibs = zip(*(pending.pop(i) for i in group))
+        B = len(group)
+        im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
+        bv_blob = np.stack([np.asarray(bv, np.float32) for bv in bvs])
+        im_info = np.array([[bv_blob.shape[1], bv_blob.shape[2], 1]] * B, dtype=np.float32)
+        net.fixed_rois = True
+        try:
+            with torch.no_grad():
+                L = net.forward({"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
+                                 "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0})
+        finally:
+            net.fixed_rois = False
+        kept.append((group, int(L["rois_per_frame"]), L["rois"][0][:, 1:5].clone(), L["rois"][1][:, 1:5].clone(), L["num_rois"].clone(),
+                     L["rois_status"].clone()))
+        print('im_proposals: {:d}/{:d}'.format(group[-1] + 1, num_images))
+    out = {'bv': [None] * num_images, 'image': [None] * num_images}
+    for group, cap, bv, img, num, status in kept:              # the read-back, after the last forward
+        num, status = num.cpu().numpy(), status.cpu().numpy()
+        if int(status.max(initial=0)) & 1:
+            raise ZeroDivisionError("float division")
+        bv, img = bv.cpu().numpy(), img.cpu().numpy()
+        for b, i in enumerate(group):
+            n = min(max(int(num[b]), 0), cap)
+            out['bv'][i] = np.ascontiguousarray(bv[b * cap:b * cap + n])
+            out['image'][i] = np.ascontiguousarray(img[b * cap:b * cap + n])
+    with open(os.path.join(get_output_dir(imdb, None), 'proposals.pkl'), 'wb') as f:
+        pickle.dump(out, f, pickle.HIGHEST_PROTOCOL)
+    return out
