@@ -815,6 +815,46 @@ typedef struct {
 int mv3d_proposal_recall(const mv3d_recall_split *split, double *gt_overlaps_dev, int32_t *counts_dev, int32_t *status_dev,
                          void *stream);
 
+/* ------------------------------------------------------------------ proposal recall by oriented IoU (csrc/proposal_recall_3d.hip)
+ * The same matching with the KITTI evaluator's oriented-box overlap (csrc/box_iou.h) against the objects' LIDAR corners, for the
+ * BEV IoU and the 3D IoU at once: MV3D's 3D-proposal recall.  Frames are CSR ranges as above, plus pair_off: frame f's R_f x G_f
+ * block of the IoU workspace starts at pair_off[f], pair_off[0] = 0, pair_off[f+1] = pair_off[f] + R_f * G_f.  box_off / gt_off /
+ * pair_off are HOST arrays, validated before any device call (start at 0, monotone, end at num_boxes / num_gts / num_pairs, at
+ * most MV3D_RECALL_MAX_GT objects per frame, pair_off consistent with the other two, num_boxes and num_pairs < 2^31); the *_dev
+ * members hold the same on the device.  Contract and operation order: the header comment of csrc/proposal_recall_3d.hip,
+ * DESIGN.md §3.15.
+ *   boxes_dev       MV3D_RECALL3D_BOX6: (num_boxes, 6) f32 x, y, z, l, w, h (rois[2][:, 1:7] of the proposal layer);
+ *                   MV3D_RECALL3D_CNR24: (num_boxes, 24) f32 x0..7, y0..7, z0..7; in proposal order
+ *   gt_cnr_dev      (num_gts, 24) f32 LIDAR corners (the roidb's boxes_corners)
+ *   limits_dev, thresholds_dev, short_mode   as in mv3d_recall_split */
+#define MV3D_RECALL3D_BOX6 0
+#define MV3D_RECALL3D_CNR24 1
+typedef struct {
+    int32_t num_frames, num_gts, num_limits, num_thresholds, short_mode, box_format;
+    long long num_boxes, num_pairs;
+    const int32_t *box_off, *gt_off, *pair_off;
+    const int32_t *box_off_dev, *gt_off_dev, *pair_off_dev;
+    const float *boxes_dev, *gt_cnr_dev;
+    const int32_t *limits_dev;
+    const double *thresholds_dev;
+} mv3d_recall3d_split;
+/* bytes of the IoU workspace of a split with num_pairs (proposal, object) pairs: two f64 planes, 16 * num_pairs */
+size_t mv3d_proposal_recall_3d_workspace_bytes(long long num_pairs);
+/* iou_ws_dev: caller-owned workspace of that many bytes, written in full (no memset needed), plane 0 = BEV IoU, plane 1 = 3D IoU.
+ * gt_overlaps_dev (2, num_limits, num_gts) f64, metric 0 = bev, 1 = 3d: frame f's block holds the overlap recorded in round j at
+ * position gt_off[f] + j (-1.0 throughout for a frame without proposals); counts_dev (2, num_limits, num_thresholds) int32,
+ * zeroed by the call, integer atomics only; status_dev (num_frames) int32, zeroed by the call: MV3D_RECALL_STATUS_* bits, over
+ * all limits and both metrics.  Asynchronous; allocates nothing. */
+int mv3d_proposal_recall_3d(const mv3d_recall3d_split *split, double *iou_ws_dev, double *gt_overlaps_dev, int32_t *counts_dev,
+                            int32_t *status_dev, void *stream);
+/* The two launches of mv3d_proposal_recall_3d on their own, with the same validation (tools/proposal_recall_3d_bench.py times them
+ * separately; another set of limits can be matched against overlaps that are already there).  _overlaps zeroes status_dev and
+ * writes the workspace and the MV3D_RECALL_STATUS_NONFINITE bits; _match zeroes counts_dev, reads both and adds
+ * MV3D_RECALL_STATUS_SHORT bits: it must follow an _overlaps call on the same split, workspace and status, on the same stream. */
+int mv3d_proposal_recall_3d_overlaps(const mv3d_recall3d_split *split, double *iou_ws_dev, int32_t *status_dev, void *stream);
+int mv3d_proposal_recall_3d_match(const mv3d_recall3d_split *split, const double *iou_ws_dev, double *gt_overlaps_dev,
+                                  int32_t *counts_dev, int32_t *status_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

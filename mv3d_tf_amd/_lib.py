@@ -139,6 +139,15 @@ class RecallSplit(C.Structure):
                 ("gt_dev", C.c_void_p), ("limits_dev", C.c_void_p), ("thresholds_dev", C.c_void_p)]
 
 
+class Recall3dSplit(C.Structure):
+    """mv3d_recall3d_split"""
+    _fields_ = [("num_frames", C.c_int32), ("num_gts", C.c_int32), ("num_limits", C.c_int32), ("num_thresholds", C.c_int32),
+                ("short_mode", C.c_int32), ("box_format", C.c_int32), ("num_boxes", C.c_longlong), ("num_pairs", C.c_longlong),
+                ("box_off", C.c_void_p), ("gt_off", C.c_void_p), ("pair_off", C.c_void_p), ("box_off_dev", C.c_void_p),
+                ("gt_off_dev", C.c_void_p), ("pair_off_dev", C.c_void_p), ("boxes_dev", C.c_void_p), ("gt_cnr_dev", C.c_void_p),
+                ("limits_dev", C.c_void_p), ("thresholds_dev", C.c_void_p)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mv3d_version": (C.c_int, []),
@@ -252,6 +261,10 @@ _SIGS = {
     "mv3d_kitti_eval_count_2d": (C.c_int, [C.POINTER(KittiSplit), C.POINTER(KittiImageSplit), _P, _P, C.c_int, C.c_int, C.c_double,
                                            _P, _P, _P, _P, _P]),
     "mv3d_proposal_recall": (C.c_int, [C.POINTER(RecallSplit), _P, _P, _P, _P]),
+    "mv3d_proposal_recall_3d_workspace_bytes": (C.c_size_t, [C.c_longlong]),
+    "mv3d_proposal_recall_3d": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P, _P, _P]),
+    "mv3d_proposal_recall_3d_overlaps": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P]),
+    "mv3d_proposal_recall_3d_match": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P, _P, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -182,6 +182,14 @@ class kitti_mv3d(object):
         from .proposal_recall import evaluate_recall
         return evaluate_recall(self.roidb, candidate_boxes, thresholds=thresholds, area=area, limit=limit, space=space)
 
+    def evaluate_recall_3d(self, candidate_boxes, thresholds=None, area='all', limit=None, metric='3d', on_short='raise'):
+        """Recall of 3D proposals by oriented BEV / 3D IoU against this split's `boxes_corners` (datasets/proposal_recall_3d.py):
+        `candidate_boxes` are per-frame (R, 6) x y z l w h rows or (R, 24) corners in proposal order, or what
+        rpn_msr.generate.imdb_proposals(..., with_3d=True) returns; the objects are those `evaluate_recall(space='bv')` selects."""
+        from .proposal_recall_3d import evaluate_recall_3d
+        return evaluate_recall_3d(self.roidb, candidate_boxes, thresholds=thresholds, area=area, limit=limit, metric=metric,
+                                  on_short=on_short)
+
     def append_flipped_images(self):
         raise NotImplementedError("cfg.TRAIN.USE_FLIPPED: the reference's flip only mirrors the 2-D image boxes "
                                   "(lib/datasets/imdb.py:104-121) and would leave BEV / 3-D ground truth unflipped; not built")

@@ -996,6 +996,7 @@ def default_recall_thresholds():
 
 class _RecallOut(tuple):
     pack = None                                             # the one buffer the three tensors are views of
+    keep = None
 
 
 def proposal_recall(split, limits=(None,), thresholds=None, on_short='raise'):
@@ -1049,3 +1050,101 @@ def proposal_recall_host(out):
         raise AssertionError(f"proposal recall: frame {int(short[0])} has fewer boxes than objects ({short.size} frames): "
                              "lib/datasets/imdb.py:186 assert(gt_ovr >= 0); on_short='zero' counts the objects left over as misses")
     return h_ov, h_counts, h_status
+
+
+# ------------------------------------------------------------------ proposal recall by oriented IoU (csrc/proposal_recall_3d.hip, datasets/proposal_recall_3d.py)
+RECALL3D_METRICS = ('bev', '3d')                           # the planes of gt_overlaps / counts, in this order
+
+
+def _recall3d_boxes(a, what):
+    """(N, 6) x y z l w h (from (N, 6) or the (N, 7) rows of a `rois` blob with the batch index in front) or (N, 24) corners,
+    f32 -> (array, format)"""
+    if not isinstance(a, torch.Tensor):
+        a = np.asarray(a)
+    if a.ndim != 2 and a.shape[0] == 0:
+        a = a.reshape(0, 6)
+    if a.ndim != 2 or a.shape[1] not in (6, 7, 24):
+        raise ValueError(f"proposal recall 3d: {what} must be (N, 6), (N, 7) or (N, 24), got {tuple(a.shape)}")
+    return _exact_f32(a[:, 1:7] if a.shape[1] == 7 else a, what), (1 if a.shape[1] == 24 else 0)
+
+
+class Recall3dSplit:
+    """A split on the device for mv3d_proposal_recall_3d: frame f owns proposals box_off[f] .. box_off[f+1]-1 and objects gt_off[f]
+    .. gt_off[f+1]-1.  boxes: (N, 6) x y z l w h, (N, 7) with the batch column in front, or (N, 24) corners; gt: (G, 24) LIDAR
+    corners; numpy arrays or device tensors, f32 (another dtype only if it converts exactly).  Everything that comes from the
+    host goes up in ONE packed upload."""
+
+    def __init__(self, boxes, box_off, gt, gt_off, device):
+        box_off = np.ascontiguousarray(box_off, np.int64)
+        gt_off = np.ascontiguousarray(gt_off, np.int64)
+        if box_off.ndim != 1 or box_off.size < 1 or box_off.shape != gt_off.shape:
+            raise ValueError("proposal recall 3d: box_off and gt_off need num_frames + 1 entries each")
+        pair_off = np.concatenate([[0], np.cumsum(np.diff(box_off) * np.diff(gt_off))]).astype(np.int64)
+        if box_off[-1] > np.iinfo(np.int32).max or pair_off[-1] > np.iinfo(np.int32).max:
+            raise ValueError("proposal recall 3d: more than 2^31 - 1 boxes or (box, object) pairs in one split")
+        boxes, self.box_format = _recall3d_boxes(boxes, "boxes")
+        if not isinstance(gt, torch.Tensor):
+            gt = np.asarray(gt)
+        if gt.ndim != 2 and gt.shape[0] == 0:
+            gt = gt.reshape(0, 24)
+        if gt.ndim != 2 or gt.shape[1] != 24:
+            raise ValueError(f"proposal recall 3d: objects must be (G, 24) corners, got {tuple(gt.shape)}")
+        gt = _exact_f32(gt, "objects")
+        if boxes.shape[0] != box_off[-1] or gt.shape[0] != gt_off[-1]:
+            raise ValueError("proposal recall 3d: the offsets do not end at the number of boxes / objects")
+        self.box_off, self.gt_off, self.pair_off = (a.astype(np.int32) for a in (box_off, gt_off, pair_off))   # host copies the C-ABI validates
+        self.device = device
+        self.F, self.N, self.G, self.P = box_off.size - 1, int(box_off[-1]), int(gt_off[-1]), int(pair_off[-1])
+        host = [self.box_off, self.gt_off, self.pair_off] + [a for a in (boxes, gt) if not isinstance(a, torch.Tensor)]
+        up = upload_packed(host, device)
+        self.box_off_dev, self.gt_off_dev, self.pair_off_dev = up[0], up[1], up[2]
+        rest = list(up[3:])
+        self.boxes, self.gt = (a.to(device).contiguous() if isinstance(a, torch.Tensor) else rest.pop(0) for a in (boxes, gt))
+
+
+def proposal_recall_3d_workspace_bytes(num_pairs):
+    return int(lib().mv3d_proposal_recall_3d_workspace_bytes(int(num_pairs)))
+
+
+def recall3d_prepare(split, limits=(None,), thresholds=None, on_short='raise'):
+    """-> (descriptor, workspace, result): the mv3d_recall3d_split of one call, its IoU workspace and the packed result tensors
+    (gt_overlaps, counts, status; `.keep` holds the small device arrays the descriptor points to)"""
+    if on_short not in ('raise', 'zero'):
+        raise ValueError("proposal recall 3d: on_short is 'raise' or 'zero'")
+    lim = recall_limits(limits)
+    thr = np.ascontiguousarray(default_recall_thresholds() if thresholds is None else thresholds, np.float64).reshape(-1)
+    L, T, dev = lim.size, thr.size, split.device
+    d_lim = torch.from_numpy(lim).to(dev)
+    d_thr = torch.from_numpy(thr).to(dev) if T else None
+    ws = torch.empty((max(proposal_recall_3d_workspace_bytes(split.P) // 8, 1),), dtype=torch.float64, device=dev)
+    nb = [16 * L * split.G, 8 * L * T, 4 * split.F]
+    pack = torch.empty((max(sum(nb), 8),), dtype=torch.uint8, device=dev)
+    ov = pack[:nb[0]].view(torch.float64).view(2, L, split.G)
+    counts = pack[nb[0]:nb[0] + nb[1]].view(torch.int32).view(2, L, T)
+    status = pack[nb[0] + nb[1]:sum(nb)].view(torch.int32)
+    desc = _lib.Recall3dSplit(split.F, split.G, L, T, 1 if on_short == 'zero' else 0, split.box_format, split.N, split.P,
+                              split.box_off.ctypes.data, split.gt_off.ctypes.data, split.pair_off.ctypes.data,
+                              split.box_off_dev.data_ptr(), split.gt_off_dev.data_ptr(), split.pair_off_dev.data_ptr(),
+                              split.boxes.data_ptr() if split.N else None, split.gt.data_ptr() if split.G else None, d_lim.data_ptr(),
+                              d_thr.data_ptr() if T else None)
+    out = _RecallOut((ov, counts, status))
+    out.pack, out.keep = pack, (split, d_lim, d_thr)
+    return desc, ws, out
+
+
+def proposal_recall_3d(split, limits=(None,), thresholds=None, on_short='raise'):
+    """-> (gt_overlaps (2, L, G) f64, counts (2, L, T) int32, status (F) int32), device tensors, metric 0 = BEV IoU, 1 = 3D IoU
+    (RECALL3D_METRICS): the greedy matching of lib/datasets/imdb.py:162-196 by oriented-box overlap for every frame, every limit
+    and both metrics (csrc/proposal_recall_3d.hip).  on_short as in `proposal_recall`.  Asynchronous."""
+    desc, ws, out = recall3d_prepare(split, limits, thresholds, on_short)
+    ov, counts, status = out
+    check(lib().mv3d_proposal_recall_3d(C.byref(desc), _ptr(ws) if split.P else None, _ptr(ov) if split.G else None,
+                                        _ptr(counts) if counts.numel() else None, _ptr(status) if split.F else None, _stream()),
+          "mv3d_proposal_recall_3d")
+    return out
+
+
+def proposal_recall_3d_host(out):
+    """The ONE read-back of proposal_recall_3d's result -> numpy (gt_overlaps (2, L, G), counts (2, L, T), status (F)); raises as
+    `proposal_recall_host` does."""
+    return proposal_recall_host(out)
