@@ -543,6 +543,30 @@ int mv3d_detect_post(const float *cls_prob_dev, const float *pred_bv_dev, const 
                      int32_t *det_row_dev, int32_t *det_count_dev, int32_t *status_dev, void *workspace,
                      size_t workspace_bytes, void *stream);
 
+/* The same tail with ORIENTED NMS (not in the reference's test_net; the MV3D paper's rule for final detections): candidates,
+ * order, outputs and cap are mv3d_detect_post's, bit for bit; a candidate is suppressed by an earlier kept one by the IoU of
+ * their BEV footprints, computed as the KITTI evaluator computes it (mv3d_kitti_eval_overlaps), all f64 from the f32 corners.
+ *   footprint of row r, class j: 24 f32 [x0..7, y0..7, z0..7]; footprint_source 0 = corners_dev[r] (the proposal's box, shared by
+ *   the classes), 1 = pred_cnr_r_dev[r, 24j : 24j + 24] (the regressed corners; pred_cnr_r_dev is then required).  The polygon is
+ *   vertices 0..3.  It need not be a rectangle or convex: the result is defined by the operation order, as in the evaluator.
+ *   overlap of (earlier a, later b) in processing order: f64 min / max of x and y over vertices 0..3; disjoint extents
+ *   (a.maxx < b.minx || b.maxx < a.minx || a.maxy < b.miny || b.maxy < a.miny) = 0.0; otherwise the evaluator's clip with a as
+ *   the polygon and b as the clipper.  b is suppressed iff iou_bev >= nms_thresh (nms_strict_gt: iou_bev > nms_thresh), compared
+ *   in f64.  A box with a non-finite value among its 24 has IoU 0.0 with everything (it is kept and suppresses nothing) and sets
+ *   MV3D_DETECT_STATUS_NONFINITE in status_dev[frame] if it passed the score cut; bit 0 is never set by this entry.
+ * det_bv_dev still carries the rows' pixel boxes.  Kernel launches only (at most four), so the call can be captured in a graph.
+ * The workspace (mv3d_detect_post_oriented_workspace_bytes: about batch * (K-1) * cap * (cap / 64) * 8 bytes) is
+ * required and need not be initialised; only its base pointer has to be 16-byte aligned (a misaligned one is refused), the parts
+ * inside are carved at 256-byte granularity and the query counts that padding; MV3D_ERR_INVALID_ARG for a NULL or short one, for footprint_source outside {0, 1} and
+ * for everything mv3d_detect_post refuses, before any HIP call.  Same limits as mv3d_detect_post. */
+#define MV3D_DETECT_STATUS_NONFINITE 2
+size_t mv3d_detect_post_oriented_workspace_bytes(int batch, const mv3d_detect_post_params *p);
+int mv3d_detect_post_oriented(const float *cls_prob_dev, const float *pred_bv_dev, const float *corners_dev,
+                              const float *pred_cnr_r_dev, const int32_t *num_rois_dev, int batch,
+                              const mv3d_detect_post_params *p, int footprint_source, float *det_bv_dev, float *det_cnr_dev,
+                              float *det_cnr_r_dev, int32_t *det_row_dev, int32_t *det_count_dev, int32_t *status_dev,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* Training losses and their gradients (lib/fast_rcnn/train_mv.py:74-136), fused: losses_dev[0] = mean softmax
  * cross-entropy, losses_dev[1] = mean over rows of sum smooth-L1 (sigma = 3 in the reference) of pred - target;
  * d_*_dev (may be NULL) receive d loss / d logits and d loss / d pred.  A mean over no rows is NaN, as in TF.

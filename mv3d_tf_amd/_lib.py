@@ -192,6 +192,9 @@ _SIGS = {
     "mv3d_detect_post_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(DetectPostParams)]),
     "mv3d_detect_post": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(DetectPostParams), _P, _P, _P, _P, _P, _P, _P, C.c_size_t,
                                    _P]),
+    "mv3d_detect_post_oriented_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(DetectPostParams)]),
+    "mv3d_detect_post_oriented": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(DetectPostParams), C.c_int, _P, _P, _P, _P, _P, _P,
+                                            _P, C.c_size_t, _P]),
     "mv3d_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mv3d_rpn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_rcnn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -22,22 +22,9 @@
 //      more than max_per_image, every thread takes kept scores v, counts by binary search in each class's (descending)
 //      list how many are > v and >= v; the max_per_image-th largest is the v with #(> v) < max_per_image <= #(>= v).
 //      Every class then keeps its scores >= that value: a prefix, so only det_count shrinks.
-#include "kernels.h"
+// Steps 1-2 (dp_sort_candidates) and 5 (dp_emit) live in detect_post.h: the oriented tail (detect_post_oriented.hip) runs the same code.
+#include "detect_post.h"
 #include "nms_pair.h"
-
-#define DP_MAX_ROWS 2048
-#define DP_MAX_CLASSES 8
-#define DP_THREADS 1024
-#define DP_WAVES (DP_THREADS / 64)
-
-struct DetectPostDev {
-    const float *cls_prob, *pred_bv, *corners, *pred_cnr_r;
-    const int32_t *num_rois;
-    float *det_bv, *det_cnr, *det_cnr_r;
-    int32_t *det_row, *det_count, *status;
-    int K, cap, max_per_image;
-    float score_thresh, tf;
-};
 
 __global__ __launch_bounds__(DP_THREADS) void detect_post_nms_kernel(const DetectPostDev d)
 {
@@ -54,41 +41,10 @@ __global__ __launch_bounds__(DP_THREADS) void detect_post_nms_kernel(const Detec
         if (t == 0) d.det_count[(long long)f * K] = 0;
         return;
     }
-    int n = cap;
-    if (d.num_rois) { const int v = d.num_rois[f]; n = v < n ? v : n; }
-    if (n < 0) n = 0;
-    int ns = 64;                                             // sort size: a power of two >= n
-    while (ns < n) ns <<= 1;
     const long long row0 = (long long)f * cap;
 
-    // 1. keys
-    if (t == 0) s_nc = 0;
-    for (int p = t; p < ns; p += DP_THREADS) {
-        unsigned long long c = 0ull;
-        if (p < n) {
-            const float s = d.cls_prob[(row0 + p) * K + j];
-            if (s > d.score_thresh) c = ((unsigned long long)mv3d_score_key(s) << 32) | (unsigned)p;
-        }
-        s_sort[p] = c;
-    }
-    __syncthreads();
-
-    // 2. bitonic sort, descending
-    for (int k = 2; k <= ns; k <<= 1) {
-        for (int h = k >> 1; h > 0; h >>= 1) {
-            for (int q = t; q < (ns >> 1); q += DP_THREADS) {
-                const int i = ((q & ~(h - 1)) << 1) | (q & (h - 1)), l = i | h;
-                const unsigned long long a = s_sort[i], b = s_sort[l];
-                const bool desc = (i & k) == 0;
-                if (desc ? (a < b) : (a > b)) { s_sort[i] = b; s_sort[l] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int p = t; p < ns; p += DP_THREADS)
-        if (s_sort[p] != 0ull && (p + 1 == ns || s_sort[p + 1] == 0ull)) s_nc = p + 1;
-    __syncthreads();
-    const int nc = s_nc;
+    // 1-2. keys, sort
+    const int nc = dp_sort_candidates(d, j, f, s_sort, &s_nc);
 
     // 3. boxes in processing order
     for (int p = t; p < nc; p += DP_THREADS) {
@@ -158,30 +114,8 @@ __global__ __launch_bounds__(DP_THREADS) void detect_post_nms_kernel(const Detec
     if (__any(zero) && lane == 0) atomicOr(&d.status[f], MV3D_FLAG_ZERO_DIVISION);
     __syncthreads();
 
-    // 5. kept positions, in order
-    int kc = 0;
-    for (int b = 0; b < nblk; ++b) {
-        const unsigned long long km = s_kmask[b];
-        if (wave == b % DP_WAVES && ((km >> lane) & 1ull))
-            s_kpos[kc + __popcll(km & ((1ull << lane) - 1ull))] = (unsigned short)(64 * b + lane);
-        kc += __popcll(km);
-    }
-    __syncthreads();
-    const long long o = ((long long)f * K + j) * cap;
-    if (t == 0) d.det_count[(long long)f * K + j] = kc;
-    for (int e = t; e < kc; e += DP_THREADS) d.det_row[o + e] = (int)(unsigned)s_sort[s_kpos[e]];
-    for (int e = t; e < kc * 5; e += DP_THREADS) {
-        const int slot = e / 5, c = e - slot * 5, p = s_kpos[slot];
-        const int row = (int)(unsigned)s_sort[p];
-        d.det_bv[o * 5 + e] = c < 4 ? reinterpret_cast<const float *>(&s_box[p])[c] : d.cls_prob[(row0 + row) * K + j];
-    }
-    for (int e = t; e < kc * 25; e += DP_THREADS) {
-        const int slot = e / 25, c = e - slot * 25;
-        const int row = (int)(unsigned)s_sort[s_kpos[slot]];
-        const float sc = d.cls_prob[(row0 + row) * K + j];
-        d.det_cnr[o * 25 + e] = c < 24 ? d.corners[(row0 + row) * 24 + c] : sc;
-        if (d.pred_cnr_r) d.det_cnr_r[o * 25 + e] = c < 24 ? d.pred_cnr_r[(row0 + row) * (24 * K) + 24 * j + c] : sc;
-    }
+    // 5. kept positions, in order; outputs
+    dp_emit<DP_THREADS>(d, j, f, nblk, s_kmask, s_kpos, s_sort, s_box);
 }
 
 // number of leading scores of a descending list that are > v (GE: >= v)
@@ -227,10 +161,9 @@ __global__ __launch_bounds__(256) void detect_post_cap_kernel(const DetectPostDe
         d.det_count[(long long)f * K + t] = dp_count_before<true>(lists + (long long)t * d.cap * 5, s_cnt[t], thr);
 }
 
-static bool dp_params_ok(int batch, const mv3d_detect_post_params *p)
+void mv3d_launch_detect_post_cap(const DetectPostDev &d, int batch, hipStream_t stream)
 {
-    return p && batch > 0 && batch <= 65535 && p->num_classes >= 2 && p->num_classes <= DP_MAX_CLASSES &&
-           p->rows_per_frame >= 1 && p->rows_per_frame <= DP_MAX_ROWS;
+    hipLaunchKernelGGL(detect_post_cap_kernel, dim3(batch), dim3(256), 0, stream, d);
 }
 
 extern "C" size_t mv3d_detect_post_workspace_bytes(int batch, const mv3d_detect_post_params *p)
@@ -259,6 +192,6 @@ extern "C" int mv3d_detect_post(const float *cls_prob_dev, const float *pred_bv_
     d.tf = p->nms_strict_gt ? nextafterf((float)p->nms_thresh, INFINITY) : mv3d_ceil_f32(p->nms_thresh);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(detect_post_nms_kernel, dim3(d.K, batch), dim3(DP_THREADS), 0, st, d);
-    if (d.max_per_image > 0) hipLaunchKernelGGL(detect_post_cap_kernel, dim3(batch), dim3(256), 0, st, d);
+    if (d.max_per_image > 0) mv3d_launch_detect_post_cap(d, batch, st);
     return mv3d_launch_status();
 }

@@ -55,7 +55,13 @@ cfg.TEST = _section(
     # (not in the reference) frames per forward of fast_rcnn.detect_batch.test_net: 1 = the reference's frame-by-frame loop
     # (test_mv.test_net); n > 1 groups up to n consecutive frames of equal image / BEV shapes and finishes them on the device
     # (ops.detect_post), one read-back per group
-    BATCH_SIZE=1)
+    BATCH_SIZE=1,
+    # (not in the reference) True: fast_rcnn.detect_batch.test_net and ServeGraph run the final NMS on the ORIENTED BEV footprints
+    # (ops.detect_post_oriented, the evaluator's IoU) instead of the axis-aligned pixel boxes; test_mv.test_net raises ValueError with
+    # the key on (get_output_dir below refuses a detection loop without oriented NMS).
+    # NMS_ORIENTED_BOXES: 'regressed' = the class's regressed corners, which are then also what all_boxes_cnr stores, or
+    # 'proposal' = the proposal's own corners
+    NMS_ORIENTED=False, NMS_ORIENTED_BOXES='regressed')
 cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
@@ -123,9 +129,14 @@ def apply_end2end_yml():
             "TEST": {"RPN_PRE_NMS_TOP_N": 6000, "RPN_POST_NMS_TOP_N": 300, "HAS_RPN": True, "NMS": 0.1}}, cfg)
 
 
-def get_output_dir(imdb, weights_filename):
+def get_output_dir(imdb, weights_filename, oriented_nms=False):
     """Directory for the detections of `imdb` (lib/fast_rcnn/config.py:245-257): ROOT_DIR/output/EXP_DIR/<imdb.name>
-    [/<weights_filename>]; created if missing."""
+    [/<weights_filename>]; created if missing.  A detection loop (weights_filename given) that has no oriented NMS
+    (oriented_nms=False: the frame-by-frame test_mv.test_net) is refused here while cfg.TEST.NMS_ORIENTED is on, before anything
+    is created or a frame is loaded: its detections would not be what the configuration says."""
+    if weights_filename is not None and not oriented_nms and cfg.TEST.get("NMS_ORIENTED", False):
+        raise ValueError("cfg.TEST.NMS_ORIENTED is set: the frame-by-frame reference loop (fast_rcnn.test_mv.test_net) has no oriented "
+                         "NMS; use fast_rcnn.detect_batch.test_net")
     outdir = os.path.abspath(os.path.join(cfg.ROOT_DIR, 'output', cfg.EXP_DIR, imdb.name))
     if weights_filename is not None:
         outdir = os.path.join(outdir, weights_filename)

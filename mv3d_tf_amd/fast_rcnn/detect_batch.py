@@ -6,6 +6,11 @@ small read-back instead of a host round trip per frame and class.
 behind the box tail in the same graph; `final_detections()` returns the lists.  post=None captures exactly test_mv.ServeGraph's graph.
 `test_net(...)`: fast_rcnn.test_mv.test_net with the key cfg.TEST.BATCH_SIZE: 1 (the default) calls test_mv.test_net itself; n > 1
 serves up to n consecutive frames of equal image / BEV shapes per forward and finishes them on the device.
+cfg.TEST.NMS_ORIENTED (or `post=dict(..., oriented=True, footprint='regressed' | 'proposal')`) swaps the tail for
+ops.detect_post_oriented: the same cut, order and cap with the NMS judged by the IoU of the oriented BEV footprints; with the
+'regressed' footprint the corner lists carry the regressed corners, the boxes the NMS judged.  The key sends test_net down the
+device route whatever BATCH_SIZE is.  The frame-by-frame loop has no oriented NMS: with the key on test_mv.test_net
+raises ValueError where it asks for its output directory (config.get_output_dir), before it loads a frame.
 fast_rcnn.test_mv keeps the reference's frame-by-frame entry points as they are."""
 import os
 import pickle
@@ -22,11 +27,15 @@ from ..networks.mv3d import n_classes
 
 class ServeGraph(test_mv.ServeGraph):
     """test_mv.ServeGraph whose captured step, with `post=dict(max_per_image=...)`, ends in ops.detect_post: the replay's outputs gain
-    out["post"] = (det_bv, det_cnr, det_cnr_r, det_row, det_count, status), static tensors like the others."""
+    out["post"] = (det_bv, det_cnr, det_cnr_r, det_row, det_count, status), static tensors like the others.  `oriented` (default:
+    cfg.TEST.NMS_ORIENTED) captures ops.detect_post_oriented with `footprint` (default: cfg.TEST.NMS_ORIENTED_BOXES) instead."""
 
     def __init__(self, net, feed, warmup=2, post=None):
         self.post = None if post is None else dict(post)
-        self._post_out = None
+        self._post_out = self._post_ws = None
+        if self.post is not None:
+            self.post.setdefault("oriented", bool(cfg.TEST.get("NMS_ORIENTED", False)))
+            self.post.setdefault("footprint", cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed"))
         super().__init__(net, feed, warmup)
 
     def _step(self):
@@ -34,20 +43,32 @@ class ServeGraph(test_mv.ServeGraph):
         if self.post is not None:
             cap = int(out["rois_per_frame"])
             if self._post_out is None:                          # (the graph's static outputs: allocated once, before the capture)
-                self._post_out = ops.detect_post_outputs(int(out["corners"].shape[0]) // cap, n_classes, cap, out["corners"].device)
-            out["post"] = ops.detect_post(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"], out["num_rois"], cap,
-                                          n_classes, int(self.post.get("max_per_image", 300)), cfg.TEST.NMS, out=self._post_out)
+                B, dev = int(out["corners"].shape[0]) // cap, out["corners"].device
+                self._post_out = ops.detect_post_outputs(B, n_classes, cap, dev)
+                if self.post["oriented"]:
+                    self._post_ws = ops.detect_post_oriented_workspace(B, n_classes, cap, dev)
+            if self.post["oriented"]:
+                out["post"] = ops.detect_post_oriented(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"],
+                                                       out["num_rois"], cap, n_classes, int(self.post.get("max_per_image", 300)),
+                                                       cfg.TEST.NMS, strict_gt=bool(cfg.USE_GPU_NMS), footprint=self.post["footprint"],
+                                                       out=self._post_out, workspace=self._post_ws)
+            else:
+                out["post"] = ops.detect_post(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"], out["num_rois"], cap,
+                                              n_classes, int(self.post.get("max_per_image", 300)), cfg.TEST.NMS, out=self._post_out)
         return out
 
     def final_detections(self):
         """after a replay of a graph built with `post`: per frame (dets, dets_cnr) exactly as class_detections + limit_detections return
         them (dets[0] == [], class j (N,5) / (N,25) f32) -- the score cut, NMS and cap ran inside the graph; the ONE host round trip is the
-        counts, the status words and the rows in front of the counts"""
+        counts, the status words and the rows in front of the counts.  Oriented NMS on the 'regressed' footprint: dets_cnr holds the
+        regressed corners of the kept rows (the boxes the NMS judged)"""
         if self.post is None:
             raise ValueError("final_detections() needs ServeGraph(..., post=dict(max_per_image=...))")
         self.stream.synchronize()
         if int(self.out["status"].max().item()) & 1:
             raise ZeroDivisionError("float division")
+        if self.post["oriented"] and self.post["footprint"] == "regressed":
+            return [(dets, cnr_r) for dets, _, cnr_r in ops.detect_post_lists(self.out["post"], with_cnr_r=True)]
         return ops.detect_post_lists(self.out["post"])
 
 
@@ -87,10 +108,13 @@ def group_frames(keys, batch_size):
 def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
     """test_mv.test_net with cfg.TEST.BATCH_SIZE (not in the reference).  1: test_mv.test_net, untouched.  n > 1: one eager forward
     with fixed ROI rows per group of equally shaped consecutive frames (`iter_frame_groups`), the box tail and ops.detect_post on the
-    device, ONE read-back of the final detections per group.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
+    device, ONE read-back of the final detections per group.  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
+    ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
     group) and the evaluate_detections call are test_mv.test_net's."""
     batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
-    if batch_size <= 1:
+    oriented = bool(cfg.TEST.get("NMS_ORIENTED", False))
+    footprint = cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed")
+    if batch_size <= 1 and not oriented:
         return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
     if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
         net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
@@ -98,7 +122,7 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
     num_images = len(imdb.image_index)
     all_boxes = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
     all_boxes_cnr = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
-    output_dir = get_output_dir(imdb, weights_filename)
+    output_dir = get_output_dir(imdb, weights_filename, oriented_nms=True)
     pending = {}
 
     def keys():
@@ -107,7 +131,7 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
             yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
 
     t_detect = t_misc = 0.0
-    for group in iter_frame_groups(keys(), batch_size):
+    for group in iter_frame_groups(keys(), max(batch_size, 1)):
         ims, bvs, calibs = zip(*(pending.pop(i) for i in group))
         B = len(group)
         t0 = time.time()
@@ -119,16 +143,23 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
             with torch.no_grad():
                 L = net.forward({"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
                                  "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0})
-                cnr, _, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
+                cnr, pr, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
         finally:
             net.fixed_rois = False
         torch.cuda.synchronize()                                       # (for the timer only: one per group)
         t1 = time.time()
-        post = ops.detect_post(L["cls_prob"], pred_bv, cnr, None, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
-                               max_per_image, cfg.TEST.NMS)
+        if oriented:
+            post = ops.detect_post_oriented(L["cls_prob"], pred_bv, cnr, pr, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
+                                            max_per_image, cfg.TEST.NMS, strict_gt=bool(cfg.USE_GPU_NMS), footprint=footprint)
+        else:
+            post = ops.detect_post(L["cls_prob"], pred_bv, cnr, None, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
+                                   max_per_image, cfg.TEST.NMS)
         if int(L["rois_status"].max().item()) & 1:
             raise ZeroDivisionError("float division")
-        frames = ops.detect_post_lists(post)
+        if oriented and footprint == "regressed":
+            frames = [(dets, cnr_r) for dets, _, cnr_r in ops.detect_post_lists(post, with_cnr_r=True)]
+        else:
+            frames = ops.detect_post_lists(post)
         t2 = time.time()
         for i, (dets, dets_cnr) in zip(group, frames):
             for j in range(1, imdb.num_classes):

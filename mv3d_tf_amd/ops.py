@@ -351,6 +351,75 @@ def detect_post(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame
     return out
 
 
+_FOOTPRINTS = {"proposal": 0, "regressed": 1}
+
+
+def detect_post_oriented_workspace(B, K, cap, dev):
+    """A caller-owned workspace for detect_post_oriented (uint8; the kernels write before they read, so it is not initialised)."""
+    params = _lib.DetectPostParams(int(K), int(cap), 0, 0, 0.0, 0, 0.0)
+    return torch.empty((max(lib().mv3d_detect_post_oriented_workspace_bytes(int(B), C.byref(params)), 256),), dtype=torch.uint8, device=dev)
+
+
+def detect_post_oriented(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame, num_classes, max_per_image, nms_thresh,
+                         score_thresh=0.05, strict_gt=False, footprint="regressed", out=None, workspace=None):
+    """detect_post with ORIENTED NMS (mv3d_detect_post_oriented): the same score cut, order, outputs and cap; a candidate is suppressed
+    by an earlier kept one where the IoU of their BEV footprints, computed as the KITTI evaluator computes it, is >= nms_thresh
+    (strict_gt: > nms_thresh), in f64.  footprint: 'regressed' = pred_cnr_r[r, 24j:24j+24] (required then), 'proposal' = corners[r].
+    Returns the six-tuple of detect_post (`out` = detect_post_outputs(...)), for detect_post_lists as it is; status value 2
+    (MV3D_DETECT_STATUS_NONFINITE) marks frames with a candidate whose footprint holds a non-finite value (kept, suppresses
+    nothing).  `workspace`: detect_post_oriented_workspace(...), or the cached one of this stream.  Asynchronous: kernel launches only."""
+    if footprint not in _FOOTPRINTS:
+        raise ValueError("detect_post_oriented: footprint is 'regressed' or 'proposal', not %r" % (footprint,))
+    K, cap = int(num_classes), int(rows_per_frame)
+    if cap <= 0 or cls_prob.shape[0] % cap:
+        check(_lib.ERR_INVALID_ARG, "detect_post_oriented: rows are not a multiple of rows_per_frame")
+    B = cls_prob.shape[0] // cap
+    dev = cls_prob.device
+    cls_prob = cls_prob.float().contiguous()
+    pred_bv, corners = pred_bv.float().contiguous(), corners.float().contiguous()
+    if pred_cnr_r is not None:
+        pred_cnr_r = pred_cnr_r.float().contiguous()
+    if (cls_prob.shape[1], pred_bv.shape, corners.shape) != (K, (B * cap, 4 * K), (B * cap, 24)) or \
+            (pred_cnr_r is not None and pred_cnr_r.shape != (B * cap, 24 * K)) or \
+            (num_rois is not None and (num_rois.dtype != torch.int32 or num_rois.numel() != B)):
+        check(_lib.ERR_INVALID_ARG, "detect_post_oriented: input shapes")
+    params = _lib.DetectPostParams(K, cap, int(max_per_image), 1 if strict_gt else 0, float(score_thresh), 0, float(nms_thresh))
+    need = lib().mv3d_detect_post_oriented_workspace_bytes(B, C.byref(params))
+    if need == 0:
+        check(_lib.ERR_INVALID_ARG, "detect_post_oriented: batch, num_classes or rows_per_frame out of range")
+    if workspace is None:
+        workspace = _workspace(need, dev, "detect_post_oriented")
+    if out is None:
+        out = detect_post_outputs(B, K, cap, dev, pred_cnr_r is not None)
+    det_bv, det_cnr, det_cnr_r, det_row, det_count, status = out
+    status.zero_()
+    rc = lib().mv3d_detect_post_oriented(_ptr(cls_prob), _ptr(pred_bv), _ptr(corners), _ptr(pred_cnr_r), _ptr(num_rois), B,
+                                         C.byref(params), _FOOTPRINTS[footprint], _ptr(det_bv), _ptr(det_cnr),
+                                         _ptr(det_cnr_r if pred_cnr_r is not None else None), _ptr(det_row), _ptr(det_count),
+                                         _ptr(status), _ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
+    check(rc, "mv3d_detect_post_oriented")
+    return out
+
+
+def nms_oriented(corners, scores, thresh, strict_gt=False):
+    """Greedy NMS of n <= 2048 oriented boxes by the IoU of their BEV footprints: corners (n, 24) [x0..7, y0..7, z0..7], scores (n)
+    -> the kept indices (i64 device tensor) in keep order (descending score, equal scores by larger index).  One class of one frame
+    of detect_post_oriented without score cut or cap (a NaN or -inf score is no candidate, as there).  Synchronises (one read of
+    the count)."""
+    corners = corners.float().reshape(-1, 24).contiguous()
+    n = corners.shape[0]
+    if n > 2048:
+        raise ValueError("nms_oriented: %d boxes; at most 2048 (the rows of one frame of detect_post_oriented)" % n)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int64, device=corners.device)
+    scores = scores.float().reshape(n)
+    cls_prob = torch.stack([torch.zeros_like(scores), scores], 1)
+    pred_bv = torch.zeros((n, 8), dtype=torch.float32, device=corners.device)
+    out = detect_post_oriented(cls_prob, pred_bv, corners, None, None, n, 2, 0, thresh, score_thresh=float("-inf"), strict_gt=strict_gt,
+                               footprint="proposal")
+    return out[3][0, 1, :int(out[4][0, 1].item())].to(torch.int64)
+
+
 def detect_post_lists(out, with_cnr_r=False):
     """The ONE read-back behind detect_post: synchronises, reads det_count | status, raises ZeroDivisionError where the reference's NMS
     does, copies the rows in front of the counts and returns per frame (dets, dets_cnr[, dets_cnr_r]) as class_detections +
