@@ -259,7 +259,9 @@ int mv3d_rois_3d_to_fv(const float *rois_3d_dev, int num_rois, float *rois_fv_de
  *     [2] n_bg (labels==0 before subsampling), [3] n_low (max_overlap < NEGATIVE_OVERLAP
  *     among inside anchors), rest reserved.
  *   fg_hi_dev (N) u8: for the k-th fg candidate, 1 iff its max_overlap >= NEGATIVE_OVERLAP
- *     (lets the host know how many positives survive step 9 of SURVEY A.1). */
+ *     (lets the host know how many positives survive step 9 of SURVEY A.1).
+ *   No inside anchor at all (the reference raises there, on the argmax of an empty column): every label is -1, every
+ *     target 0, the four counts are 0, stage 2 emits no debug row and the caller draws nothing. */
 typedef struct {
     int32_t feat_stride;
     int32_t clobber_positives;   /* cfg.TRAIN.RPN_CLOBBER_POSITIVES */
@@ -315,7 +317,9 @@ int mv3d_anchor_target_stage2_batch(int batch, int H, int W, const mv3d_anchor_t
  * [n_candidates, n_fg (max_ov >= FG_THRESH), n_bg (LO <= max_ov < HI), 0].  The caller draws
  * npr.permutation(n_fg)[:k_fg] and npr.permutation(n_bg)[:k_bg] (legacy RandomState.choice
  * without replacement) and stage2 gathers the sampled ROIs: rois_bv (S,5), rois_img (S,5),
- * labels (S) i32, bbox_targets (S, 24*num_classes), rois_3d (S,7), S = n_fg + n_bg rows, fg first. */
+ * labels (S) i32, bbox_targets (S, 24*num_classes), rois_3d (S,7), S = n_fg + n_bg rows, fg first.
+ * An empty candidate list is not drawn from; with both empty S = 0 (the reference asserts there), stage 2 launches nothing
+ * and writes nothing. */
 typedef struct {
     int32_t num_classes;         /* n_classes = 2: lib/networks/MV3D_train.py:4 */
     int32_t frame_index;         /* batch column written for the appended ground-truth rows: 0 = the reference
