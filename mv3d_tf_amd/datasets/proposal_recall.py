@@ -31,29 +31,34 @@ def _boxes4(a):
     return a[:, 1:5] if a.shape[1] == 5 else a
 
 
-def select_objects(roidb, area='all', space='bv'):
-    """imdb.py:149-160 -> (per-frame (G, 4) object boxes, num_pos)"""
+def select_indices(roidb, area='all', area_key='boxes_bv'):
+    """imdb.py:149-160 -> per roidb entry the row indices of its selected objects: class > 0, no crowd row, and `seg_areas`
+    (where the entry has them, else the f32 area of its `area_key` box) within the named range"""
     assert area in AREAS, 'unknown area range: {}'.format(area)
     lo, hi = AREA_RANGES[AREAS[area]]
-    key = SPACES[space][0]
-    gts, num_pos = [], 0
+    inds = []
     for entry in roidb:
         max_gt_overlaps = entry['gt_overlaps'].toarray().max(axis=1) if entry['gt_overlaps'].shape[0] else np.zeros(0)
         gt_inds = np.where((np.asarray(entry['gt_classes']) > 0) & (max_gt_overlaps == 1))[0]
-        gt_boxes = np.asarray(entry[key]).reshape(-1, 4)[gt_inds, :]
         if 'seg_areas' in entry:
             gt_areas = np.asarray(entry['seg_areas'])[gt_inds]
         else:
-            b = gt_boxes.astype(np.float64)
+            b = np.asarray(entry[area_key]).reshape(-1, 4)[gt_inds, :].astype(np.float64)
             gt_areas = ((b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)).astype(np.float32)
-        valid_gt_inds = np.where((gt_areas >= lo) & (gt_areas <= hi))[0]
-        gts.append(gt_boxes[valid_gt_inds, :])
-        num_pos += len(valid_gt_inds)
-    return gts, num_pos
+        inds.append(gt_inds[(gt_areas >= lo) & (gt_areas <= hi)])
+    return inds
 
 
-def _launch(boxes, gts, limits, thresholds, on_short):
-    """per-frame box / object lists -> host (gt_overlaps (L, G), counts (L, T)): one upload, one launch, one read-back"""
+def select_objects(roidb, area='all', space='bv'):
+    """imdb.py:149-160 -> (per-frame (G, 4) object boxes, num_pos)"""
+    key = SPACES[space][0]
+    inds = select_indices(roidb, area, key)
+    return [np.asarray(e[key]).reshape(-1, 4)[i, :] for e, i in zip(roidb, inds)], sum(len(i) for i in inds)
+
+
+def launch_split(split_cls, op, widths, boxes, gts, limits, thresholds, on_short):
+    """per-frame row / object lists -> host (gt_overlaps, counts) of `op` on one `split_cls` of ops: one upload, the launches of
+    one call, one read-back; `widths`: the columns of the empty (row, object) arrays of a call without frames"""
     import torch
     from .. import ops
     from ..fast_rcnn.config import cfg
@@ -61,15 +66,35 @@ def _launch(boxes, gts, limits, thresholds, on_short):
     box_off = np.concatenate([[0], np.cumsum([b.shape[0] for b in boxes])])
     gt_off = np.concatenate([[0], np.cumsum([g.shape[0] for g in gts])])
     if boxes and all(isinstance(b, torch.Tensor) for b in boxes):
-        allb = torch.cat([b.to(dev) for b in boxes]) if boxes else torch.zeros((0, 4), device=dev)
+        allb = torch.cat([b.to(dev) for b in boxes])
     else:
         host = [b.cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b) for b in boxes]
-        allb = np.concatenate(host) if host else np.zeros((0, 4), np.float32)
-    allg = np.concatenate(gts) if gts else np.zeros((0, 4), np.float32)
-    split = ops.RecallSplit(allb, box_off, allg, gt_off, dev)
-    out = ops.proposal_recall(split, limits, thresholds, on_short)
-    ov, counts, _ = ops.proposal_recall_host(out)
+        allb = np.concatenate(host) if host else np.zeros((0, widths[0]), np.float32)
+    allg = np.concatenate(gts) if gts else np.zeros((0, widths[1]), np.float32)
+    ov, counts, _ = ops.proposal_recall_host(op(split_cls(allb, box_off, allg, gt_off, dev), limits, thresholds, on_short))
     return ov, counts
+
+
+def _launch(boxes, gts, limits, thresholds, on_short):
+    """per-frame box / object lists -> host (gt_overlaps (L, G), counts (L, T)): one upload, one launch, one read-back"""
+    from .. import ops
+    return launch_split(ops.RecallSplit, ops.proposal_recall, (4, 4), boxes, gts, limits, thresholds, on_short)
+
+
+def result_dicts(ov, counts, kept, num_pos, thresholds, limits):
+    """(gt_overlaps (L, G), counts (L, T)) of one metric -> the reference's result dictionary per limit; `kept`: the objects of
+    frames that have boxes (the reference skips the others; they still count in num_pos)"""
+    results = []
+    for li in range(len(limits)):
+        with np.errstate(divide='ignore', invalid='ignore'):
+            recalls = np.asarray(counts[li], np.int64) / np.float64(num_pos)
+        results.append({'ar': recalls.mean(), 'recalls': recalls, 'thresholds': thresholds,
+                        'gt_overlaps': np.sort(np.asarray(ov[li], np.float64)[kept])})
+    return results
+
+
+def kept_objects(boxes, gts):
+    return np.concatenate([np.full(g.shape[0], b.shape[0] > 0) for b, g in zip(boxes, gts)]) if gts else np.zeros(0, bool)
 
 
 def evaluate_recall(roidb, candidate_boxes, thresholds=None, area='all', limit=None, space='bv', on_short='raise'):
@@ -100,13 +125,7 @@ def evaluate_recall(roidb, candidate_boxes, thresholds=None, area='all', limit=N
         thresholds = np.arange(0.5, 0.95 + 1e-5, step)
     thresholds = np.asarray(thresholds, np.float64)
     ov, counts = _launch(boxes, gts, limits, thresholds, on_short)
-    kept = np.concatenate([np.full(g.shape[0], b.shape[0] > 0) for b, g in zip(boxes, gts)]) if gts else np.zeros(0, bool)
-    results = []
-    for li in range(len(limits)):
-        with np.errstate(divide='ignore', invalid='ignore'):
-            recalls = counts[li].astype(np.int64) / np.float64(num_pos)
-        results.append({'ar': recalls.mean(), 'recalls': recalls, 'thresholds': thresholds,
-                        'gt_overlaps': np.sort(np.asarray(ov[li], np.float64)[kept])})
+    results = result_dicts(ov, counts, kept_objects(boxes, gts), num_pos, thresholds, limits)
     return results if many else results[0]
 
 

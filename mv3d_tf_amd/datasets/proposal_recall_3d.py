@@ -16,7 +16,7 @@ import pickle
 
 import numpy as np
 
-from .proposal_recall import AREA_RANGES, AREAS, DEFAULT_LIMITS, parse_limits, table
+from .proposal_recall import AREAS, DEFAULT_LIMITS, kept_objects, launch_split, parse_limits, result_dicts, select_indices, table
 
 METRICS = ('bev', '3d')                                    # the planes of the device result, in this order
 MAX_PAIRS = 2 ** 31 - 1
@@ -25,22 +25,9 @@ CLI_THRESHOLDS = np.concatenate([[0.25], np.arange(0.5, 0.95 + 1e-5, 0.05)])
 
 def select_corners(roidb, area='all'):
     """-> (per-frame (G, 24) f32 LIDAR corners, num_pos): the rows of `boxes_corners` that proposal_recall.select_objects(roidb,
-    area, 'bv') selects (imdb.py:149-160 on `boxes_bv`, the same index computation)."""
-    assert area in AREAS, 'unknown area range: {}'.format(area)
-    lo, hi = AREA_RANGES[AREAS[area]]
-    gts, num_pos = [], 0
-    for entry in roidb:
-        max_gt_overlaps = entry['gt_overlaps'].toarray().max(axis=1) if entry['gt_overlaps'].shape[0] else np.zeros(0)
-        gt_inds = np.where((np.asarray(entry['gt_classes']) > 0) & (max_gt_overlaps == 1))[0]
-        if 'seg_areas' in entry:
-            gt_areas = np.asarray(entry['seg_areas'])[gt_inds]
-        else:
-            b = np.asarray(entry['boxes_bv']).reshape(-1, 4)[gt_inds, :].astype(np.float64)
-            gt_areas = ((b[:, 2] - b[:, 0] + 1) * (b[:, 3] - b[:, 1] + 1)).astype(np.float32)
-        valid_gt_inds = np.where((gt_areas >= lo) & (gt_areas <= hi))[0]
-        gts.append(np.asarray(entry['boxes_corners'], np.float32).reshape(-1, 24)[gt_inds[valid_gt_inds], :])
-        num_pos += len(valid_gt_inds)
-    return gts, num_pos
+    area, 'bv') selects (imdb.py:149-160 on `boxes_bv`)."""
+    inds = select_indices(roidb, area, 'boxes_bv')
+    return [np.asarray(e['boxes_corners'], np.float32).reshape(-1, 24)[i, :] for e, i in zip(roidb, inds)], sum(len(i) for i in inds)
 
 
 def _boxes3d(a):
@@ -56,22 +43,8 @@ def _boxes3d(a):
 def _launch_3d(boxes, gts, limits, thresholds, on_short):
     """per-frame proposal / object-corner lists -> host (gt_overlaps (2, L, G), counts (2, L, T)): one upload, the two launches,
     one read-back"""
-    import torch
     from .. import ops
-    from ..fast_rcnn.config import cfg
-    dev = next((b.device for b in boxes if isinstance(b, torch.Tensor) and b.is_cuda), None) or torch.device("cuda", cfg.GPU_ID)
-    box_off = np.concatenate([[0], np.cumsum([b.shape[0] for b in boxes])])
-    gt_off = np.concatenate([[0], np.cumsum([g.shape[0] for g in gts])])
-    if boxes and all(isinstance(b, torch.Tensor) for b in boxes):
-        allb = torch.cat([b.to(dev) for b in boxes])
-    else:
-        host = [b.cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b) for b in boxes]
-        allb = np.concatenate(host) if host else np.zeros((0, 6), np.float32)
-    allg = np.concatenate(gts) if gts else np.zeros((0, 24), np.float32)
-    split = ops.Recall3dSplit(allb, box_off, allg, gt_off, dev)
-    out = ops.proposal_recall_3d(split, limits, thresholds, on_short)
-    ov, counts, _ = ops.proposal_recall_3d_host(out)
-    return ov, counts
+    return launch_split(ops.Recall3dSplit, ops.proposal_recall_3d, (6, 24), boxes, gts, limits, thresholds, on_short)
 
 
 def frame_chunks(pairs, max_workspace_bytes):
@@ -124,15 +97,11 @@ def evaluate_recall_3d(roidb, candidate_boxes, thresholds=None, area='all', limi
         ovs.append(np.asarray(ov, np.float64).reshape(2, len(limits), -1))
         counts += np.asarray(c, np.int64).reshape(counts.shape)
     ov = np.concatenate(ovs, axis=2)
-    kept = np.concatenate([np.full(g.shape[0], b.shape[0] > 0) for b, g in zip(boxes, gts)]) if gts else np.zeros(0, bool)
+    kept = kept_objects(boxes, gts)
     out = {}
     for m in metrics:
         mi = METRICS.index(m)
-        results = []
-        for li in range(len(limits)):
-            with np.errstate(divide='ignore', invalid='ignore'):
-                recalls = counts[mi, li] / np.float64(num_pos)
-            results.append({'ar': recalls.mean(), 'recalls': recalls, 'thresholds': thresholds, 'gt_overlaps': np.sort(ov[mi, li][kept])})
+        results = result_dicts(ov[mi], counts[mi], kept, num_pos, thresholds, limits)
         out[m] = results if many else results[0]
     return out if many_metrics else out[metrics[0]]
 

@@ -1022,29 +1022,45 @@ def _recall_boxes(a, what):
     return _exact_f32(a[:, 1:5] if a.shape[1] == 5 else a, what)
 
 
-class RecallSplit:
-    """A split on the device for mv3d_proposal_recall: frame f owns boxes box_off[f] .. box_off[f+1]-1 and objects gt_off[f] ..
-    gt_off[f+1]-1.  boxes / gt: numpy arrays or device tensors, f32 (another dtype only if it converts exactly), boxes with or
-    without the leading batch column of a `rois` blob.  Everything that comes from the host goes up in ONE packed upload."""
+class _RecallSplitBase:
+    """What RecallSplit and Recall3dSplit share: the offset checks, the int32 host copies of the offsets that the C-ABI
+    validates, ONE packed upload of everything that comes from the host, and device tensors picked up as they are.  A subclass
+    sets `what` (the prefix of its messages) and `_parse(boxes, gt) -> (boxes, gt)` f32; `_offsets` names the offset arrays."""
+    what = None
 
     def __init__(self, boxes, box_off, gt, gt_off, device):
         box_off = np.ascontiguousarray(box_off, np.int64)
         gt_off = np.ascontiguousarray(gt_off, np.int64)
         if box_off.ndim != 1 or box_off.size < 1 or box_off.shape != gt_off.shape:
-            raise ValueError("proposal recall: box_off and gt_off need num_frames + 1 entries each")
-        if box_off[-1] > np.iinfo(np.int32).max:
-            raise ValueError("proposal recall: more than 2^31 - 1 boxes in one split")
-        boxes, gt = _recall_boxes(boxes, "boxes"), _recall_boxes(gt, "objects")
+            raise ValueError(f"{self.what}: box_off and gt_off need num_frames + 1 entries each")
+        offs = self._offsets(box_off, gt_off)
+        boxes, gt = self._parse(boxes, gt)
         if boxes.shape[0] != box_off[-1] or gt.shape[0] != gt_off[-1]:
-            raise ValueError("proposal recall: the offsets do not end at the number of boxes / objects")
-        self.box_off, self.gt_off = box_off.astype(np.int32), gt_off.astype(np.int32)     # host copies the C-ABI validates
+            raise ValueError(f"{self.what}: the offsets do not end at the number of boxes / objects")
         self.device = device
         self.F, self.N, self.G = box_off.size - 1, int(box_off[-1]), int(gt_off[-1])
-        host = [self.box_off, self.gt_off] + [a for a in (boxes, gt) if not isinstance(a, torch.Tensor)]
-        up = upload_packed(host, device)
-        self.box_off_dev, self.gt_off_dev = up[0], up[1]
-        rest = list(up[2:])
-        self.boxes, self.gt = (a.to(device).contiguous() if isinstance(a, torch.Tensor) else rest.pop(0) for a in (boxes, gt))
+        names = list(offs)
+        for k in names:
+            setattr(self, k, offs[k].astype(np.int32))          # host copies the C-ABI validates
+        up = list(upload_packed([getattr(self, k) for k in names] + [a for a in (boxes, gt) if not isinstance(a, torch.Tensor)], device))
+        for k in names:
+            setattr(self, k + "_dev", up.pop(0))
+        self.boxes, self.gt = (a.to(device).contiguous() if isinstance(a, torch.Tensor) else up.pop(0) for a in (boxes, gt))
+
+    def _offsets(self, box_off, gt_off):
+        if box_off[-1] > np.iinfo(np.int32).max:
+            raise ValueError(f"{self.what}: more than 2^31 - 1 boxes in one split")
+        return {"box_off": box_off, "gt_off": gt_off}
+
+
+class RecallSplit(_RecallSplitBase):
+    """A split on the device for mv3d_proposal_recall: frame f owns boxes box_off[f] .. box_off[f+1]-1 and objects gt_off[f] ..
+    gt_off[f+1]-1.  boxes / gt: numpy arrays or device tensors, f32 (another dtype only if it converts exactly), boxes with or
+    without the leading batch column of a `rois` blob.  Everything that comes from the host goes up in ONE packed upload."""
+    what = "proposal recall"
+
+    def _parse(self, boxes, gt):
+        return _recall_boxes(boxes, "boxes"), _recall_boxes(gt, "objects")
 
 
 def recall_limits(limits):
@@ -1068,32 +1084,40 @@ class _RecallOut(tuple):
     keep = None
 
 
+def _recall_prepare(what, split, limits, thresholds, on_short, planes):
+    """-> (limits, thresholds on the device, short_mode, result): the packed (gt_overlaps, counts, status) of `planes` metric
+    planes (1: (L, G) / (L, T); 2: (2, L, G) / (2, L, T)); `.keep` holds what a descriptor points to"""
+    if on_short not in ('raise', 'zero'):
+        raise ValueError(f"{what}: on_short is 'raise' or 'zero'")
+    lim = recall_limits(limits)
+    thr = np.ascontiguousarray(default_recall_thresholds() if thresholds is None else thresholds, np.float64).reshape(-1)
+    L, T, dev = lim.size, thr.size, split.device
+    d_lim = torch.from_numpy(lim).to(dev)
+    d_thr = torch.from_numpy(thr).to(dev) if T else None
+    lead = () if planes == 1 else (planes,)
+    nb = [8 * planes * L * split.G, 4 * planes * L * T, 4 * split.F]
+    pack = torch.empty((max(sum(nb), 8),), dtype=torch.uint8, device=dev)
+    out = _RecallOut((pack[:nb[0]].view(torch.float64).view(*lead, L, split.G),
+                      pack[nb[0]:nb[0] + nb[1]].view(torch.int32).view(*lead, L, T), pack[nb[0] + nb[1]:sum(nb)].view(torch.int32)))
+    out.pack, out.keep = pack, (split, d_lim, d_thr)
+    return d_lim, d_thr, 1 if on_short == 'zero' else 0, out
+
+
 def proposal_recall(split, limits=(None,), thresholds=None, on_short='raise'):
     """-> (gt_overlaps (L, G) f64, counts (L, T) int32, status (F) int32), device tensors: the greedy matching of
     lib/datasets/imdb.py:162-196 for every frame and every limit in one launch (csrc/proposal_recall.hip).  on_short: frames with
     fewer boxes than objects, 'raise' = the reference's failing assert (status bit MV3D_RECALL_STATUS_SHORT, see
     `proposal_recall_host`), 'zero' = this library's definition, NOT the reference's: the objects left over record 0.0.
     Asynchronous."""
-    if on_short not in ('raise', 'zero'):
-        raise ValueError("proposal recall: on_short is 'raise' or 'zero'")
-    lim = recall_limits(limits)
-    thr = np.ascontiguousarray(default_recall_thresholds() if thresholds is None else thresholds, np.float64).reshape(-1)
-    L, T, dev = lim.size, thr.size, split.device
-    d_lim = torch.from_numpy(lim).to(dev)
-    d_thr = torch.from_numpy(thr).to(dev) if T else None
-    nb = [8 * L * split.G, 4 * L * T, 4 * split.F]
-    pack = torch.empty((max(sum(nb), 8),), dtype=torch.uint8, device=dev)
-    ov = pack[:nb[0]].view(torch.float64).view(L, split.G)
-    counts = pack[nb[0]:nb[0] + nb[1]].view(torch.int32).view(L, T)
-    status = pack[nb[0] + nb[1]:sum(nb)].view(torch.int32)
-    desc = _lib.RecallSplit(split.F, split.G, L, T, 1 if on_short == 'zero' else 0, 0, split.N, split.box_off.ctypes.data,
+    d_lim, d_thr, mode, out = _recall_prepare("proposal recall", split, limits, thresholds, on_short, 1)
+    ov, counts, status = out
+    T = counts.shape[-1]
+    desc = _lib.RecallSplit(split.F, split.G, d_lim.numel(), T, mode, 0, split.N, split.box_off.ctypes.data,
                             split.gt_off.ctypes.data, split.box_off_dev.data_ptr(), split.gt_off_dev.data_ptr(),
                             split.boxes.data_ptr() if split.N else None, split.gt.data_ptr() if split.G else None, d_lim.data_ptr(),
                             d_thr.data_ptr() if T else None)
     check(lib().mv3d_proposal_recall(C.byref(desc), _ptr(ov) if split.G else None, _ptr(counts) if T else None,
                                      _ptr(status) if split.F else None, _stream()), "mv3d_proposal_recall")
-    out = _RecallOut((ov, counts, status))
-    out.pack = pack
     return out
 
 
@@ -1137,20 +1161,21 @@ def _recall3d_boxes(a, what):
     return _exact_f32(a[:, 1:7] if a.shape[1] == 7 else a, what), (1 if a.shape[1] == 24 else 0)
 
 
-class Recall3dSplit:
+class Recall3dSplit(_RecallSplitBase):
     """A split on the device for mv3d_proposal_recall_3d: frame f owns proposals box_off[f] .. box_off[f+1]-1 and objects gt_off[f]
     .. gt_off[f+1]-1.  boxes: (N, 6) x y z l w h, (N, 7) with the batch column in front, or (N, 24) corners; gt: (G, 24) LIDAR
     corners; numpy arrays or device tensors, f32 (another dtype only if it converts exactly).  Everything that comes from the
     host goes up in ONE packed upload."""
+    what = "proposal recall 3d"
 
-    def __init__(self, boxes, box_off, gt, gt_off, device):
-        box_off = np.ascontiguousarray(box_off, np.int64)
-        gt_off = np.ascontiguousarray(gt_off, np.int64)
-        if box_off.ndim != 1 or box_off.size < 1 or box_off.shape != gt_off.shape:
-            raise ValueError("proposal recall 3d: box_off and gt_off need num_frames + 1 entries each")
+    def _offsets(self, box_off, gt_off):
         pair_off = np.concatenate([[0], np.cumsum(np.diff(box_off) * np.diff(gt_off))]).astype(np.int64)
         if box_off[-1] > np.iinfo(np.int32).max or pair_off[-1] > np.iinfo(np.int32).max:
             raise ValueError("proposal recall 3d: more than 2^31 - 1 boxes or (box, object) pairs in one split")
+        self.P = int(pair_off[-1])
+        return {"box_off": box_off, "gt_off": gt_off, "pair_off": pair_off}
+
+    def _parse(self, boxes, gt):
         boxes, self.box_format = _recall3d_boxes(boxes, "boxes")
         if not isinstance(gt, torch.Tensor):
             gt = np.asarray(gt)
@@ -1158,17 +1183,7 @@ class Recall3dSplit:
             gt = gt.reshape(0, 24)
         if gt.ndim != 2 or gt.shape[1] != 24:
             raise ValueError(f"proposal recall 3d: objects must be (G, 24) corners, got {tuple(gt.shape)}")
-        gt = _exact_f32(gt, "objects")
-        if boxes.shape[0] != box_off[-1] or gt.shape[0] != gt_off[-1]:
-            raise ValueError("proposal recall 3d: the offsets do not end at the number of boxes / objects")
-        self.box_off, self.gt_off, self.pair_off = (a.astype(np.int32) for a in (box_off, gt_off, pair_off))   # host copies the C-ABI validates
-        self.device = device
-        self.F, self.N, self.G, self.P = box_off.size - 1, int(box_off[-1]), int(gt_off[-1]), int(pair_off[-1])
-        host = [self.box_off, self.gt_off, self.pair_off] + [a for a in (boxes, gt) if not isinstance(a, torch.Tensor)]
-        up = upload_packed(host, device)
-        self.box_off_dev, self.gt_off_dev, self.pair_off_dev = up[0], up[1], up[2]
-        rest = list(up[3:])
-        self.boxes, self.gt = (a.to(device).contiguous() if isinstance(a, torch.Tensor) else rest.pop(0) for a in (boxes, gt))
+        return boxes, _exact_f32(gt, "objects")
 
 
 def proposal_recall_3d_workspace_bytes(num_pairs):
@@ -1178,26 +1193,14 @@ def proposal_recall_3d_workspace_bytes(num_pairs):
 def recall3d_prepare(split, limits=(None,), thresholds=None, on_short='raise'):
     """-> (descriptor, workspace, result): the mv3d_recall3d_split of one call, its IoU workspace and the packed result tensors
     (gt_overlaps, counts, status; `.keep` holds the small device arrays the descriptor points to)"""
-    if on_short not in ('raise', 'zero'):
-        raise ValueError("proposal recall 3d: on_short is 'raise' or 'zero'")
-    lim = recall_limits(limits)
-    thr = np.ascontiguousarray(default_recall_thresholds() if thresholds is None else thresholds, np.float64).reshape(-1)
-    L, T, dev = lim.size, thr.size, split.device
-    d_lim = torch.from_numpy(lim).to(dev)
-    d_thr = torch.from_numpy(thr).to(dev) if T else None
-    ws = torch.empty((max(proposal_recall_3d_workspace_bytes(split.P) // 8, 1),), dtype=torch.float64, device=dev)
-    nb = [16 * L * split.G, 8 * L * T, 4 * split.F]
-    pack = torch.empty((max(sum(nb), 8),), dtype=torch.uint8, device=dev)
-    ov = pack[:nb[0]].view(torch.float64).view(2, L, split.G)
-    counts = pack[nb[0]:nb[0] + nb[1]].view(torch.int32).view(2, L, T)
-    status = pack[nb[0] + nb[1]:sum(nb)].view(torch.int32)
-    desc = _lib.Recall3dSplit(split.F, split.G, L, T, 1 if on_short == 'zero' else 0, split.box_format, split.N, split.P,
+    d_lim, d_thr, mode, out = _recall_prepare("proposal recall 3d", split, limits, thresholds, on_short, 2)
+    T = out[1].shape[-1]
+    ws = torch.empty((max(proposal_recall_3d_workspace_bytes(split.P) // 8, 1),), dtype=torch.float64, device=split.device)
+    desc = _lib.Recall3dSplit(split.F, split.G, d_lim.numel(), T, mode, split.box_format, split.N, split.P,
                               split.box_off.ctypes.data, split.gt_off.ctypes.data, split.pair_off.ctypes.data,
                               split.box_off_dev.data_ptr(), split.gt_off_dev.data_ptr(), split.pair_off_dev.data_ptr(),
                               split.boxes.data_ptr() if split.N else None, split.gt.data_ptr() if split.G else None, d_lim.data_ptr(),
                               d_thr.data_ptr() if T else None)
-    out = _RecallOut((ov, counts, status))
-    out.pack, out.keep = pack, (split, d_lim, d_thr)
     return desc, ws, out
 
 

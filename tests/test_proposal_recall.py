@@ -370,6 +370,46 @@ def test_frame_with_more_boxes_than_the_used_bit_mask(ops, torch_cuda, oracle):
     assert (ov[0, :5] == 1.0).sum() == 3 and (ov[1, :5] == 1.0).sum() == 0
 
 
+def tied_columns_frame():
+    """one frame, 70 objects x 80 boxes, integer coordinates: objects 3 and 67 (another wave of the round reduction) share their
+    best box X with exactly the same overlap, 9500 / 10500, the largest of the frame; their second-best boxes differ clearly.
+    Every other object has one box of its own with an overlap of its own, 97 (100 - dx) / (20000 - 97 (100 - dx)) < 0.64, which
+    no value of the two tied objects equals (those are multiples of 100 over multiples of 100)."""
+    sq = lambda x, y: [x, y, x + 99, y + 99]
+    gts, boxes = [], []
+    for k in range(70):
+        x, y = 300 * (k % 10), 300 * (k // 10)
+        gts.append(sq(x, y))
+        if k not in (3, 67):
+            boxes.append(sq(x + 20 + k, y + 3))
+    x, y = 900, 0                                            # the slot of object 3; object 67 moves next to it
+    gts[3], gts[67] = sq(x - 5, y), sq(x + 5, y)
+    boxes += [sq(x, y), sq(x - 35, y), sq(x + 55, y)]        # X; 7000 / 13000 with object 3, 6000 / 14000 with 67; 5000 / 15000 with 67
+    boxes += [sq(5000 + 150 * i, 5000) for i in range(9)]    # far from everything
+    b = np.float32(boxes)[np.random.RandomState(3).permutation(80)]
+    return b, np.float32(gts)
+
+
+@gpu
+def test_tied_columns_across_waves_take_the_first(ops, torch_cuda, oracle):
+    """the first-index tie-break of the round reduction across waves: whichever of the two tied objects stands at index 3 takes
+    the shared box, and the one at index 67 is left with its own second best, which differs between the two"""
+    b, g = tied_columns_frame()
+    assert b.shape == (80, 4) and g.shape == (70, 4)
+    o = oracle.bbox_overlaps(b.astype(np.float64), g.astype(np.float64))
+    x = int(o[:, 3].argmax())
+    assert o[x, 3] == o[x, 67] == o.max() == 9500.0 / 10500.0 and int(o[:, 67].argmax()) == x and (o == o.max()).sum() == 2
+    swapped = g.copy()
+    swapped[[3, 67]] = g[[67, 3]]
+    want = [RR.recall_vectors([b], [gg], oracle.bbox_overlaps, (None,), None, "raise") for gg in (g, swapped)]
+    assert not np.array_equal(want[0][0], want[1][0])        # the order of the two decides: the test cannot pass vacuously
+    assert want[0][0][0, 0] == want[1][0][0, 0] == o.max()
+    assert sorted(set(want[0][0][0]) ^ set(want[1][0][0])) == [6000.0 / 14000.0, 7000.0 / 13000.0]
+    for gg, w in zip((g, swapped), want):
+        _, (ov, counts, status) = run(ops, torch_cuda, [b], [gg])
+        assert np.array_equal(ov, w[0]) and np.array_equal(counts, w[1]) and np.array_equal(status, w[2]) and not status.any()
+
+
 # ------------------------------------------------------------------ end to end
 def small_net(torch):
     from mv3d_tf_amd.networks import get_network

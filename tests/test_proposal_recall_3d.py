@@ -530,6 +530,48 @@ def test_256_objects_in_one_frame(ops, torch_cuda):
     assert same(got, want) and not got[2].any() and (got[0] > 0.1).sum() > 100 and (got[0][:, 1] == 0.0).sum() >= 2 * 156
 
 
+def tied_columns_frame():
+    """one frame, 70 objects x 80 proposals, axis-aligned 4 x 2 x 2 boxes on multiples of 1 / 64 (every overlap is exact in f64):
+    objects 3 and 67 (another wave of the round reduction) are copies of their best proposal X shifted by -0.25 and +0.25 in x,
+    the same overlap 7.5 / 8.5, the largest of the frame; their second-best proposals differ clearly.  Every other object has
+    one proposal of its own with an overlap of its own, footprint intersection 8 - (33 + 2 k) / 32, which no value of the two
+    tied objects equals (their intersections are multiples of 1 / 2)."""
+    box = lambda x, y: [x, y, -1.0, 4.0, 2.0, 2.0]
+    gts, boxes = [], []
+    for k in range(70):
+        x, y = 10.0 * (k % 10), 10.0 * (k // 10) - 30.0
+        gts.append(box(x, y))
+        if k not in (3, 67):
+            boxes.append(box(x + (33 + 2 * k) / 64.0, y))
+    x, y = 30.0, -30.0                                       # the slot of object 3; object 67 moves next to it
+    gts[3], gts[67] = box(x - 0.25, y), box(x + 0.25, y)
+    boxes += [box(x, y), box(x - 1.25, y), box(x + 2.25, y)] # X; 6 / 10 with object 3, 5 / 11 with 67; 4 / 12 with 67
+    boxes += [box(200.0 + 10.0 * i, 0.0) for i in range(9)]  # far from everything
+    b = np.float32(boxes)[np.random.RandomState(3).permutation(80)]
+    return b, R3.box6_corners(np.float32(gts))
+
+
+@gpu
+def test_tied_columns_across_waves_take_the_first(ops, torch_cuda):
+    """the first-index tie-break of the round reduction across waves: whichever of the two tied objects stands at index 3 takes
+    the shared proposal, and the one at index 67 is left with its own second best, which differs between the two"""
+    b, g = tied_columns_frame()
+    assert b.shape == (80, 6) and g.shape == (70, 24)
+    cb = R3.box6_corners(b)
+    x = int(np.flatnonzero((b[:, 0] == 30.0) & (b[:, 1] == -30.0))[0])
+    assert KR.iou_pair(cb[x], g[3]) == KR.iou_pair(cb[x], g[67]) == (7.5 / 8.5, 15.0 / 17.0)
+    swapped = g.copy()
+    swapped[[3, 67]] = g[[67, 3]]
+    want = [R3.recall_vectors_3d([b], [gg], (None,), None, "raise") for gg in (g, swapped)]
+    for m in range(2):
+        assert not np.array_equal(want[0][0][m], want[1][0][m])                  # the order of the two decides: the test cannot pass vacuously
+        assert want[0][0][m, 0, 0] == want[1][0][m, 0, 0] == want[0][0][m].max() == 7.5 / 8.5
+        assert sorted(set(want[0][0][m, 0]) ^ set(want[1][0][m, 0])) == [5.0 / 11.0, 6.0 / 10.0]
+    for gg, w in zip((g, swapped), want):
+        _, got = run(ops, torch_cuda, [b], [gg])
+        assert same(got, w) and not got[2].any()
+
+
 # ------------------------------------------------------------------ end to end
 def small_net(torch):
     from mv3d_tf_amd.networks import get_network
