@@ -883,6 +883,15 @@ int mv3d_proposal_recall_3d_overlaps(const mv3d_recall3d_split *split, double *i
 int mv3d_proposal_recall_3d_match(const mv3d_recall3d_split *split, const double *iou_ws_dev, double *gt_overlaps_dev,
                                   int32_t *counts_dev, int32_t *status_dev, void *stream);
 
+/* ------------------------------------------------------------------ mirrored training frames (cfg.TRAIN.USE_FLIPPED)
+ * Left/right mirror of a contiguous (rows, width, channels) f32 array IN PLACE: afterwards data[r][w][c] holds the old
+ * data[r][width - 1 - w][c].  No workspace; every element is read once and written once (one thread per pair of mirrored
+ * elements), the middle column of an odd width is not touched; width == 1 or rows == 0 launches nothing.  Nothing is assumed
+ * about alignment beyond the floats' own (pixels of 3 and 9 channels are 12 and 36 bytes); element offsets are 64-bit, one row
+ * (width * channels) must stay below 2^31 elements.  One launch, no allocation or synchronisation.  MV3D_ERR_INVALID_ARG: NULL
+ * data with rows > 0, rows < 0, width < 1, channels < 1, or a row of 2^31 elements or more. */
+int mv3d_mirror_columns(float *data_dev, long long rows, int width, int channels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -268,6 +268,7 @@ _SIGS = {
     "mv3d_proposal_recall_3d": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P, _P, _P]),
     "mv3d_proposal_recall_3d_overlaps": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P]),
     "mv3d_proposal_recall_3d_match": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P, _P, _P]),
+    "mv3d_mirror_columns": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, _P]),
 }
 EXPORTS = tuple(_SIGS)
 

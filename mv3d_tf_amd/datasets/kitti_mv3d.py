@@ -14,7 +14,8 @@ objects go to the device in one upload, `mv3d_gt_encode` (csrc/gt_encode.hip) co
 box and BEV box for all objects at once, and one download brings the four arrays back.  Pinned bit for bit (values and
 dtypes) by tests/golden/kitti_label.npz, which the reference's own loader produced.  `evaluate_detections` writes the
 reference's result files and scores the detections on the device (datasets/kitti_eval.py); `evaluate_recall` is the base
-class's proposal-recall statistics on the device (datasets/proposal_recall.py); caching is out of scope."""
+class's proposal-recall statistics on the device (datasets/proposal_recall.py); `append_flipped_images` appends the
+left/right mirror of every frame (datasets/mirror.py); caching is out of scope."""
 import os
 
 import numpy as np
@@ -23,6 +24,7 @@ import torch
 
 from .. import ops
 from ..fast_rcnn.config import cfg
+from .mirror import mirror_annotation, mirror_calib
 
 # calibration file: the reference reads lines 2..5 by position (:158-168); KITTI writes them in this order
 _CALIB_ROWS = ((2, 'P2', (3, 4)), (3, 'P3', (3, 4)), (4, 'R0', (3, 3)), (5, 'Tr_velo2cam', (3, 4)))
@@ -110,6 +112,7 @@ class kitti_mv3d(object):
             self._image_index = f.read().split()
         self.name = 'kitti_mv3d_' + image_set
         self._roidb = None
+        self._widths = None                                        # image widths of the source frames once the mirrors are appended
 
     classes = property(lambda self: self._classes)
     num_classes = property(lambda self: len(self._classes))
@@ -140,6 +143,8 @@ class kitti_mv3d(object):
         return load_kitti_calib(os.path.join(self._dir('calib'), index + '.txt'))
 
     def calib_at(self, i):
+        if self._widths is not None and i >= len(self._widths):    # the mirror of frame i - N (append_flipped_images)
+            return mirror_calib(self.calib_at(i - len(self._widths)), self._widths[i - len(self._widths)])
         return pack_calib(self._load_kitti_calib('%06d' % i))      # by POSITION, like the reference (kitti_mv3d.py:67)
 
     def _load_kitti_annotation(self, index):
@@ -191,5 +196,28 @@ class kitti_mv3d(object):
                                   on_short=on_short)
 
     def append_flipped_images(self):
-        raise NotImplementedError("cfg.TRAIN.USE_FLIPPED: the reference's flip only mirrors the 2-D image boxes "
-                                  "(lib/datasets/imdb.py:104-121) and would leave BEV / 3-D ground truth unflipped; not built")
+        """cfg.TRAIN.USE_FLIPPED (lib/datasets/imdb.py:104-121): appends the left/right mirror of every frame -- roidb[N + i] =
+        mirror_annotation(roidb[i], width of image i) (datasets/mirror.py: image boxes AND BEV / 3-D ground truth, where the
+        reference mirrors the image boxes only) -- and doubles the image index, so that `image_path_at` / `lidar_path_at` of a
+        mirror name the source frame's files and `calib_at` gives its mirrored table.  Only the image files' headers are read;
+        the data layer mirrors the maps on the device when it loads them (`flipped` entries, roi_data_layer/minibatch_mv3d.py).
+        The evaluators (`evaluate_detections`, `evaluate_recall*`) on a doubled imdb are out of scope, as in the reference: a
+        doubled imdb is for training.  A second call raises."""
+        if self._widths is not None:
+            raise RuntimeError("append_flipped_images: the mirrored frames have been appended already")
+        roidb = self.roidb
+        n = self.num_images
+        assert len(roidb) == n
+        widths = [_image_width(self.image_path_at(i)) for i in range(n)]
+        roidb.extend(mirror_annotation(roidb[i], widths[i]) for i in range(n))
+        self._image_index = self._image_index * 2
+        self._widths = widths
+
+
+def _image_width(path):
+    """width in pixels from the file's header (the pixel data is not read)"""
+    if path.endswith('.npy'):
+        return int(np.load(path, mmap_mode='r').shape[1])
+    from PIL import Image
+    with Image.open(path) as im:
+        return int(im.size[0])

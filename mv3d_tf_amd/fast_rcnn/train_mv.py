@@ -104,13 +104,20 @@ def total_loss(net_layers, sigma=3.0):
 
 def stack_blobs(frames):
     """blobs of several frames (RoIDataLayer.forward() each) -> the feed of one batched pass: images / BEV maps stacked on
-    axis 0 (same size per batch, as KITTI crops are), im_info (B,3), calib (B,4,12), ground truth as per-frame lists."""
+    axis 0 (same size per batch, as KITTI crops are), im_info (B,3), calib (B,4,12), ground truth as per-frame lists.  A map may be
+    a device tensor (the mirrored frames of cfg.TRAIN.USE_FLIPPED): a stack that holds one is made on the device, its numpy
+    members uploaded first."""
     if len(frames) == 1:
         return dict(frames[0])
     feed = {}
     for k in ("image_data", "lidar_bv_data", "lidar_fv_data"):
         if k in frames[0]:
-            feed[k] = np.concatenate([np.asarray(f[k]) for f in frames], 0)
+            maps = [f[k] for f in frames]
+            if any(isinstance(m, torch.Tensor) for m in maps):
+                dev = next(m.device for m in maps if isinstance(m, torch.Tensor))
+                feed[k] = torch.cat([ops._dev(m, device=dev) for m in maps], 0)
+            else:
+                feed[k] = np.concatenate([np.asarray(m) for m in maps], 0)
     feed["im_info"] = np.concatenate([np.asarray(f["im_info"], np.float32).reshape(1, 3) for f in frames], 0)
     feed["calib"] = np.stack([np.asarray(f["calib"], np.float32).reshape(4, 12) for f in frames], 0)
     for k in ("gt_boxes", "gt_boxes_bv", "gt_boxes_3d", "gt_boxes_corners"):
@@ -125,7 +132,8 @@ def group_frames_by_shape(frames):
     (lib/roi_data_layer/minibatch_mv3d.py:17-76), so the frames of a step can only be stacked when their sizes agree."""
     groups, index = [], {}
     for f in frames:
-        key = tuple(tuple(np.asarray(f[k]).shape) for k in ("image_data", "lidar_bv_data", "lidar_fv_data") if k in f)
+        key = tuple(tuple(f[k].shape if isinstance(f[k], torch.Tensor) else np.asarray(f[k]).shape)
+                    for k in ("image_data", "lidar_bv_data", "lidar_fv_data") if k in f)
         if key not in index:
             index[key] = len(groups)
             groups.append([])

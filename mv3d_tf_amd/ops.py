@@ -554,6 +554,22 @@ def gt_encode(box_cam, cos_sin, inv_rot, tr):
     return pack, spec, views
 
 
+def mirror_columns(t):
+    """Left/right mirror of a (..., W, C) f32 device tensor IN PLACE on the current stream (mv3d_mirror_columns): afterwards
+    t[..., w, :] holds the old t[..., W - 1 - w, :].  Returns t.  The tensor must be contiguous (a slice along the leading axes
+    is); anything else raises -- there is no torch path."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise TypeError("mirror_columns: a CUDA float32 tensor is required, got %s"
+                        % ("%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__))
+    if t.dim() < 3 or not t.is_contiguous() or t.shape[-1] < 1 or t.shape[-2] < 1:
+        raise ValueError("mirror_columns: a contiguous (..., W, C) tensor with W, C >= 1 is required, got shape %s strides %s"
+                         % (tuple(t.shape), tuple(t.stride())))
+    W, Cn = int(t.shape[-2]), int(t.shape[-1])
+    with torch.cuda.device(t.device):
+        check(lib().mv3d_mirror_columns(_ptr(t), t.numel() // (W * Cn), W, Cn, _stream()), "mv3d_mirror_columns")
+    return t
+
+
 # ------------------------------------------------------------------ training losses (SURVEY §8(f) rank 4)
 def _loss_call(fn, name, cls, labels, pred, tgt, extra, sigma, want_grad):
     dev = cls.device

@@ -6,10 +6,12 @@ lidar_bv_data (1,Hbv,Wbv,9), calib (4,12), gt_boxes / gt_boxes_bv (G,5), gt_boxe
 im_info (1,3) = BEV size.  One numpy draw is kept for RNG-stream parity with the reference (`npr.randint` over
 cfg.TRAIN.SCALES, :22-23, whose result the reference never uses either).  A roidb entry may carry the frame in memory
 ('image' (H,W,3) BGR array, 'lidar_bv' array) instead of 'image_path' / 'lidar_bv_path'; image files are read with
-numpy (.npy) or PIL -- cv2 is not a dependency here."""
+numpy (.npy) or PIL -- cv2 is not a dependency here.  An entry with `flipped` true (cfg.TRAIN.USE_FLIPPED) returns its two maps as
+device tensors, mirrored left/right by ops.mirror_columns; every other entry returns numpy as the reference does."""
 import numpy as np
 import numpy.random as npr
 
+from .. import ops
 from ..datasets.kitti_mv3d import gt_blobs
 from ..fast_rcnn.config import cfg
 
@@ -33,4 +35,13 @@ def get_minibatch(roidb, num_classes):
     bev = entry['lidar_bv'] if 'lidar_bv' in entry else np.load(entry['lidar_bv_path'])
     blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': np.asarray(bev)[None], 'calib': entry['calib']}
     blobs.update(gt_blobs(entry, np.asarray(bev).shape))
+    if entry.get('flipped', False):
+        # a mirrored frame (kitti_mv3d.append_flipped_images): the files are the source frame's, the entry's ground truth and
+        # calibration are the mirror's already; the two maps are uploaded and mirrored on the device (ops.mirror_columns) and
+        # go to the network as device tensors.  The BEV raster's mirror axis is its column 300 (datasets/mirror.py).
+        if blobs['lidar_bv_data'].shape[2] != 601:
+            raise ValueError("a mirrored frame needs the 601 columns wide BEV map of point_cloud_2_top (mirror axis = column "
+                             "300), this one is {} wide".format(blobs['lidar_bv_data'].shape[2]))
+        for k in ('image_data', 'lidar_bv_data'):
+            blobs[k] = ops.mirror_columns(ops._dev(blobs[k]))
     return blobs
