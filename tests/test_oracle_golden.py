@@ -31,6 +31,37 @@ def test_defined_exp_log(oracle):
     assert np.all(np.abs(lg - g["log64"]) <= 4e-16 * np.maximum(1.0, np.abs(g["log64"])))
 
 
+def exp_edge_arguments():
+    """22 015 f32 arguments around the two cut-offs of numpy's f32 exp and through the zone where its result is subnormal"""
+    hi, lo = np.float32(88.72283935546875), np.float32(-103.97208404541015625)
+    up, down = np.float32(np.inf), np.float32(-np.inf)
+    hand = [hi, np.nextafter(hi, up), np.nextafter(hi, down), lo, np.nextafter(lo, up), np.nextafter(lo, down),
+            0.0, -0.0, np.inf, -np.inf, np.nan, 88.5, 89.0, -100.0, 88.0]
+    return np.concatenate([np.linspace(-104.5, -87, 20000), np.linspace(88, 89, 2000), hand]).astype(np.float32)
+
+
+def test_defined_exp_edges_against_numpy(oracle):
+    """the restated exp against numpy ITSELF where exp_log.npz (arguments in [-80, 80], 88 and -100) does not reach: overflow,
+    underflow and subnormal results.  numpy's f32 exp is one SIMD kernel on AVX512F and on AVX2 + FMA3 hosts (the same bits on
+    both, the oracle's) and the C library's expf elsewhere, whose subnormal results differ in the last bits: the comparison is
+    made for the numpy version of the fixtures on a host that dispatches to the SIMD kernel."""
+    recorded = str(golden("exp_log")["numpy_version"])
+    if np.__version__ != recorded:
+        pytest.skip("numpy %s here; the f32 exp is pinned for numpy %s, the fixtures' version" % (np.__version__, recorded))
+    # (a private name of numpy: safe to import only because the version check above has let nothing but numpy 2.2.x through)
+    from numpy._core._multiarray_umath import __cpu_features__ as have
+    if not (have.get("AVX512F") or (have.get("AVX2") and have.get("FMA3"))):
+        pytest.skip("numpy's f32 exp falls back to the C library on this host (no AVX512F, no AVX2 + FMA3)")
+    x = exp_edge_arguments()
+    assert x.size == 22015
+    with np.errstate(all="ignore"):
+        want = np.exp(x)
+    got = oracle.expf(x)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    tiny = (want > 0) & (want < np.float32(2.0 ** -126))
+    assert tiny.sum() > 5000 and np.isposinf(want).sum() > 500 and (want == 0).sum() > 100
+
+
 @pytest.mark.parametrize("name", ["bbox_overlaps_int", "bbox_overlaps_frac"])
 def test_bbox_overlaps(oracle, name):
     g = golden(name)
