@@ -1,6 +1,7 @@
 // anchor_target_layer for gfx950 (one frame): lib/rpn_msr/anchor_target_layer_tf.py:21-250
 // with lib/utils/bbox.pyx:15-55 (IoU, f64) and lib/fast_rcnn/bbox_transform.py:32-58 fused in;
-// the N x G overlap matrix is never materialised.
+// the N x G overlap matrix is never materialised.  The anchor grid, the BEV -> 3D anchor arithmetic,
+// the overlap and the ground-truth staging are geometry.h's (shared with proposal.hip / proposal_target.hip).
 //
 //  at_overlap_kernel   per anchor: inside test, f64 IoU against the G ground-truth boxes staged
 //                      in LDS, first-argmax / max per anchor, per-GT column maximum of the workgroup's
@@ -16,10 +17,7 @@
 //  stage 2             applies the host-drawn permutations (numpy MT19937 draws stay on the host:
 //                      draw-for-draw parity) and emits the debug anchor lists.
 #include <math.h>
-#include "common.h"
-
-__constant__ int c_at_base[16] = {-19, -8, 20, 8, -5, -2, 5, 3, -8, -19, 8, 20, -2, -5, 3, 5};
-#define AT_MAX_GT 1024
+#include "geometry.h"
 
 // Defined natural log (f64): x = m 2^k, m in [sqrt(1/2), sqrt(2)), s = (m-1)/(m+1),
 // log m = 2 s sum_{d odd <= 39} s^(d-1)/d, Horner with explicit fma; same sequence of IEEE
@@ -40,22 +38,6 @@ __device__ __forceinline__ double mv3d_log(double x)
     const double LN2_HI = 6.93147180369123816490e-01, LN2_LO = 1.90821492927058770002e-10;
     const double lm = 2.0 * s * p;
     return fma((double)k, LN2_HI, fma((double)k, LN2_LO, lm));
-}
-
-// bbox.pyx:33-54 for one (anchor, gt) pair
-__device__ __forceinline__ double iou_f64(double b0, double b1, double b2, double b3, double q0, double q1, double q2,
-                                          double q3)
-{
-    const double iw = fmin(b2, q2) - fmax(b0, q0) + 1;
-    if (iw > 0) {
-        const double ih = fmin(b3, q3) - fmax(b1, q1) + 1;
-        if (ih > 0) {
-            const double qarea = (q2 - q0 + 1) * (q3 - q1 + 1);
-            const double ua = (b2 - b0 + 1) * (b3 - b1 + 1) + qarea - iw * ih;
-            return iw * ih / ua;
-        }
-    }
-    return 0.0;
 }
 
 struct AtDev {
@@ -89,17 +71,9 @@ struct AtFrame {
 };
 struct AtBatch { AtFrame f[AT_MAX_BATCH]; int cap, n_agg1, n_agg2; };
 
-__device__ __forceinline__ void anchor_coords(const AtDev &d, int n, int &x1, int &y1, int &x2, int &y2)
-{
-    const int a = n & 3, cell = n >> 2, w = cell % d.W, h = cell / d.W;
-    const int sx = w * d.stride, sy = h * d.stride;
-    x1 = c_at_base[4 * a] + sx; y1 = c_at_base[4 * a + 1] + sy;
-    x2 = c_at_base[4 * a + 2] + sx; y2 = c_at_base[4 * a + 3] + sy;
-}
-
 __device__ __forceinline__ bool anchor_box(const AtDev &d, int n, int &x1, int &y1, int &x2, int &y2)
 {
-    anchor_coords(d, n, x1, y1, x2, y2);
+    grid_anchor(n, d.W, d.stride, x1, y1, x2, y2);
     // anchor_target_layer_tf.py:93-98 (_allowed_border = 0)
     return x1 >= 0 && y1 >= 0 && (double)x2 < (double)d.im_info[1] && (double)y2 < (double)d.im_info[0];
 }
@@ -112,13 +86,10 @@ __global__ __launch_bounds__(256) void at_overlap_kernel(AtBatch bt)
         for (int t = threadIdx.x; t < bt.n_agg1; t += blockDim.x) F.agg1[t] = 0;
         for (int t = threadIdx.x; t < bt.n_agg2; t += blockDim.x) F.agg2[t] = 0;
     }
-    __shared__ float s_gt[AT_MAX_GT * 4];
-    __shared__ unsigned long long s_max[AT_MAX_GT];
-    for (int g = threadIdx.x; g < d.G; g += blockDim.x) {
-        s_gt[4 * g + 0] = d.gt_bv[5 * g + 0]; s_gt[4 * g + 1] = d.gt_bv[5 * g + 1];
-        s_gt[4 * g + 2] = d.gt_bv[5 * g + 2]; s_gt[4 * g + 3] = d.gt_bv[5 * g + 3];
-        s_max[g] = 0ull;
-    }
+    __shared__ float s_gt[TARGET_MAX_GT * 4];
+    __shared__ unsigned long long s_max[TARGET_MAX_GT];
+    stage_gt_bv(d.gt_bv, d.G, s_gt);
+    for (int g = threadIdx.x; g < d.G; g += blockDim.x) s_max[g] = 0ull;
     __syncthreads();
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n < d.N) {
@@ -128,7 +99,7 @@ __global__ __launch_bounds__(256) void at_overlap_kernel(AtBatch bt)
         int am = 0;
         if (inside) {
             for (int g = 0; g < d.G; ++g) {
-                const double o = iou_f64(x1, y1, x2, y2, s_gt[4 * g], s_gt[4 * g + 1], s_gt[4 * g + 2], s_gt[4 * g + 3]);
+                const double o = bbox_overlap_f64(x1, y1, x2, y2, s_gt[4 * g], s_gt[4 * g + 1], s_gt[4 * g + 2], s_gt[4 * g + 3]);
                 if (o > mx) { mx = o; am = g; }           // :118 argmax = first maximum
                 if (o > 0.0) atomicMax(&s_max[g], (unsigned long long)__double_as_longlong(o));
             }
@@ -143,13 +114,10 @@ __global__ __launch_bounds__(256) void at_overlap_kernel(AtBatch bt)
 __global__ __launch_bounds__(256) void at_label_kernel(AtBatch bt)
 {
     const AtDev &d = bt.f[blockIdx.y].d;
-    __shared__ float s_gt[AT_MAX_GT * 4];
-    __shared__ unsigned long long s_maxu[AT_MAX_GT];
-    for (int g = threadIdx.x; g < d.G; g += blockDim.x) {
-        s_gt[4 * g + 0] = d.gt_bv[5 * g + 0]; s_gt[4 * g + 1] = d.gt_bv[5 * g + 1];
-        s_gt[4 * g + 2] = d.gt_bv[5 * g + 2]; s_gt[4 * g + 3] = d.gt_bv[5 * g + 3];
-        s_maxu[g] = 0ull;
-    }
+    __shared__ float s_gt[TARGET_MAX_GT * 4];
+    __shared__ unsigned long long s_maxu[TARGET_MAX_GT];
+    stage_gt_bv(d.gt_bv, d.G, s_gt);
+    for (int g = threadIdx.x; g < d.G; g += blockDim.x) s_maxu[g] = 0ull;
     __syncthreads();
     // column maxima = max over the overlap launch's per-workgroup partials (non-negative f64: the bit patterns order like
     // the values); coalesced over the (GT, workgroup) table, folded with LDS atomics
@@ -169,18 +137,16 @@ __global__ __launch_bounds__(256) void at_label_kernel(AtBatch bt)
         const double mx = d.max_ov[n];
         if (!d.clobber && 0 < mx && mx < d.neg_ov) lab = 0.0f;   // :125-130
         for (int g = 0; g < d.G; ++g) {                            // :123,:133 every anchor tying a column max
-            const double o = iou_f64(x1, y1, x2, y2, s_gt[4 * g], s_gt[4 * g + 1], s_gt[4 * g + 2], s_gt[4 * g + 3]);
+            const double o = bbox_overlap_f64(x1, y1, x2, y2, s_gt[4 * g], s_gt[4 * g + 1], s_gt[4 * g + 2], s_gt[4 * g + 3]);
             if (o == s_max[g]) { lab = 1.0f; break; }
         }
         if (mx >= d.pos_ov) lab = 1.0f;                            // :139
         if (d.clobber && mx < d.neg_ov) lab = 0.0f;                // :141-143
         if (d.G > 0) {
             // transform.py:89-111 (f64) and bbox_transform.py:32-58 (f64) then astype(f32)
-            const double ex_len = (double)(y2 - y1) * 0.1, ex_wid = (double)(x2 - x1) * 0.1;
-            const double cx = (double)(x1 + x2) / 2.0, cy = (double)(y1 + y2) / 2.0;
-            const double ey = 600 * 0.1 - (cx + 0.5) * 0.1 + (-30.0);
-            const double ex = 600 * 0.1 - (cy + 0.5) * 0.1 + 0.0;
-            const double ez = (double)(float)(-(1.73 - 1.56 / 2.0)), eh = (double)(float)1.56;
+            double A[6];
+            anchor_to_lidar_f64(x1, y1, x2, y2, A);
+            const double ex = A[0], ey = A[1], ez = A[2], ex_len = A[3], ex_wid = A[4], eh = A[5];
             const float *gt = d.gt_3d + 7 * d.argmax[n];
             T[0] = (float)(((double)gt[0] - ex) / ex_wid);         // dx / ex_widths  (sic)
             T[1] = (float)(((double)gt[1] - ey) / ex_len);         // dy / ex_lengths (sic)
@@ -257,16 +223,11 @@ __global__ __launch_bounds__(256) void at_emit_relabel_kernel(AtBatch bt)
         [&](int, int r, int n) {
             if (r >= cap) return;
             int x1, y1, x2, y2;
-            anchor_coords(d, n, x1, y1, x2, y2);
+            grid_anchor(n, d.W, d.stride, x1, y1, x2, y2);
             float *A = anchors + 5 * (long long)r, *B = anchors_3d + 7 * (long long)r;
             A[0] = 0.0f; A[1] = (float)x1; A[2] = (float)y1; A[3] = (float)x2; A[4] = (float)y2;
-            const double ex_len = (double)(y2 - y1) * 0.1, ex_wid = (double)(x2 - x1) * 0.1;
-            const double cx = (double)(x1 + x2) / 2.0, cy = (double)(y1 + y2) / 2.0;
             B[0] = 0.0f;
-            B[1] = (float)(600 * 0.1 - (cy + 0.5) * 0.1 + 0.0);
-            B[2] = (float)(600 * 0.1 - (cx + 0.5) * 0.1 + (-30.0));
-            B[3] = (float)(-(1.73 - 1.56 / 2.0));
-            B[4] = (float)ex_len; B[5] = (float)ex_wid; B[6] = (float)1.56;
+            anchor_to_lidar(x1, y1, x2, y2, B + 1);                // transform.py:89-111
         },
         F.agg2, tot);
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0 && F.n_anchors) F.n_anchors[0] = tot[0];
@@ -288,7 +249,7 @@ struct AtLayout { size_t o_maxov, o_argmax, o_gtpart, o_agg1, o_agg2, o_fg, o_bg
 
 static bool at_layout(int H, int W, int G, AtLayout &L)
 {
-    if (H <= 0 || W <= 0 || G < 0 || G > AT_MAX_GT) return false;
+    if (H <= 0 || W <= 0 || G < 0 || G > TARGET_MAX_GT) return false;
     const long long N = (long long)H * W * 4;
     if (N > (1 << 22)) return false;
     L.N = (int)N;

@@ -1,6 +1,7 @@
-// Device-side geometry shared by proposal.hip and proposal_target.hip: the BEV <-> LIDAR <->
-// corner <-> image arithmetic of lib/utils/transform.py and numpy's f32 exp / f64 floor_divide,
-// restated operation for operation (provenance: oracle/mv3d_oracle.c and DESIGN.md).
+// Device-side geometry shared by proposal.hip, anchor_target.hip and proposal_target.hip: the anchor
+// grid, the BEV <-> LIDAR <-> corner <-> image arithmetic of lib/utils/transform.py, the f64 box
+// overlap of lib/utils/bbox.pyx and numpy's f32 exp / f64 floor_divide, restated operation for
+// operation (provenance: oracle/mv3d_oracle.c and DESIGN.md).
 #pragma once
 #include <math.h>
 #include "common.h"
@@ -13,6 +14,16 @@
 #define TOP_Y_MIN_D (-30.0)
 #define TOP_X_MIN_D 0.0
 static __constant__ int c_base_anchors[16] = {-19, -8, 20, 8, -5, -2, 5, 3, -8, -19, 8, 20, -2, -5, 3, 5};
+
+// anchor n = (h, w, a), a fastest, of a W-wide grid: base anchor a shifted by the cell's (w, h) * stride
+// (proposal_layer_tf.py:79-95, anchor_target_layer_tf.py:72-88)
+__device__ __forceinline__ void grid_anchor(int n, int W, int stride, int &x1, int &y1, int &x2, int &y2)
+{
+    const int a = n & 3, cell = n >> 2, w = cell % W, h = cell / W;
+    const int sx = w * stride, sy = h * stride;
+    x1 = c_base_anchors[4 * a] + sx; y1 = c_base_anchors[4 * a + 1] + sy;
+    x2 = c_base_anchors[4 * a + 2] + sx; y2 = c_base_anchors[4 * a + 3] + sy;
+}
 
 // numpy f32 exp (simd_exp_FLOAT), see oracle/mv3d_oracle.c:mv3d_ref_expf for the provenance.
 __device__ __forceinline__ float np_expf(float x)
@@ -91,20 +102,54 @@ __device__ __forceinline__ void proj_matrix(const float *__restrict__ calib, flo
         }
 }
 
-// transform.py:89-111 + :81-87 for one integer BEV anchor box; f64, then .astype(f32)
-// (bbox_transform.py:112).  z and h are f32 constants in the reference.
-__device__ __forceinline__ void anchor_to_lidar(int x1, int y1, int x2, int y2, float o[6])
+// transform.py:89-111 + :81-87 for one integer BEV anchor box in f64: x, y, z, l, w, h.  z and h are
+// f32 constants in the reference.
+__device__ __forceinline__ void anchor_to_lidar_f64(int x1, int y1, int x2, int y2, double o[6])
 {
     const double ex_len = (double)(y2 - y1) * BV_RES;
     const double ex_wid = (double)(x2 - x1) * BV_RES;
     const double cx = (double)(x1 + x2) / 2.0;
     const double cy = (double)(y1 + y2) / 2.0;
-    const double y = BV_XN * BV_RES - (cx + 0.5) * BV_RES + TOP_Y_MIN_D;
-    const double x = BV_YN * BV_RES - (cy + 0.5) * BV_RES + TOP_X_MIN_D;
-    o[0] = (float)x; o[1] = (float)y;
-    o[2] = (float)(-(1.73 - 1.56 / 2.0));     // -(LIDAR_HEIGHT - CAR_HEIGHT/2.)
-    o[3] = (float)ex_len; o[4] = (float)ex_wid;
-    o[5] = (float)1.56;                       // CAR_HEIGHT
+    o[0] = BV_YN * BV_RES - (cy + 0.5) * BV_RES + TOP_X_MIN_D;
+    o[1] = BV_XN * BV_RES - (cx + 0.5) * BV_RES + TOP_Y_MIN_D;
+    o[2] = (double)(float)(-(1.73 - 1.56 / 2.0));     // -(LIDAR_HEIGHT - CAR_HEIGHT/2.)
+    o[3] = ex_len; o[4] = ex_wid;
+    o[5] = (double)(float)1.56;                       // CAR_HEIGHT
+}
+
+// ... then .astype(f32) (bbox_transform.py:112)
+__device__ __forceinline__ void anchor_to_lidar(int x1, int y1, int x2, int y2, float o[6])
+{
+    double d[6];
+    anchor_to_lidar_f64(x1, y1, x2, y2, d);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) o[j] = (float)d[j];
+}
+
+// bbox.pyx:33-54 for one (box, query box) pair, f64
+__device__ __forceinline__ double bbox_overlap_f64(double b0, double b1, double b2, double b3, double q0, double q1, double q2,
+                                                   double q3)
+{
+    const double iw = fmin(b2, q2) - fmax(b0, q0) + 1;
+    if (iw > 0) {
+        const double ih = fmin(b3, q3) - fmax(b1, q1) + 1;
+        if (ih > 0) {
+            const double qarea = (q2 - q0 + 1) * (q3 - q1 + 1);
+            const double ua = (b2 - b0 + 1) * (b3 - b1 + 1) + qarea - iw * ih;
+            return iw * ih / ua;
+        }
+    }
+    return 0.0;
+}
+
+// The two target layers stage a frame's ground-truth BEV boxes, columns 0..3 of gt_bv (G, 5), in LDS (4 floats per box,
+// TARGET_MAX_GT boxes at most; the workgroup synchronises afterwards).
+#define TARGET_MAX_GT 1024
+__device__ __forceinline__ void stage_gt_bv(const float *__restrict__ gt_bv, int G, float *s_gt)
+{
+    for (int g = threadIdx.x; g < G; g += blockDim.x)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_gt[4 * g + j] = gt_bv[5 * g + j];
 }
 
 // transform.py:483-500 for one box given its 6 decoded numbers

@@ -42,14 +42,14 @@ __global__ __launch_bounds__(DEC_THREADS) void proposal_decode_kernel(ProposalDe
     const int n = blockIdx.x * DEC_THREADS + threadIdx.x;
     bool ok = false;
     if (n < d.N) {
-        const int a = n & 3, cell = n >> 2, w = cell % d.W, h = cell / d.W;
+        const int a = n & 3, cell = n >> 2;
         const float *info = d.im_info + 3 * f;
         float M[12];
         proj_matrix(d.calib + 48 * f, M);
-        const int sx = w * d.feat_stride, sy = h * d.feat_stride;                 // proposal_layer_tf.py:79-95
+        int x1, y1, x2, y2;
+        grid_anchor(n, d.W, d.feat_stride, x1, y1, x2, y2);                       // proposal_layer_tf.py:79-95
         float A[6];
-        anchor_to_lidar(c_base_anchors[4 * a] + sx, c_base_anchors[4 * a + 1] + sy,
-                        c_base_anchors[4 * a + 2] + sx, c_base_anchors[4 * a + 3] + sy, A);
+        anchor_to_lidar(x1, y1, x2, y2, A);
         const float *dl = d.pred + ((long long)f * d.H * d.W + cell) * 24 + 6 * a;   // :105
         float P[6];
         P[0] = __fadd_rn(__fmul_rn(dl[0], A[3]), A[0]);                            // bbox_transform.py:130-135

@@ -16,8 +16,6 @@
 #include "geometry.h"
 #include "front_view.h"
 
-#define PT_MAX_GT 1024
-
 struct PtDev {
     const float *rois_bv, *rois_3d;      // (R,5), (R,7)
     const float *gt_bv, *gt_3d;          // (G,5), (G,7)
@@ -61,9 +59,8 @@ __device__ __forceinline__ void cand_3d(const PtDev &d, const int R, int r, floa
 __global__ __launch_bounds__(256) void pt_overlap_kernel(PtBatch bt)
 {
     const PtDev &d = bt.f[blockIdx.y].d;
-    __shared__ float s_gt[PT_MAX_GT * 4];
-    for (int g = threadIdx.x; g < d.G; g += blockDim.x)
-        for (int j = 0; j < 4; ++j) s_gt[4 * g + j] = d.gt_bv[5 * g + j];
+    __shared__ float s_gt[TARGET_MAX_GT * 4];
+    stage_gt_bv(d.gt_bv, d.G, s_gt);
     __syncthreads();
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     const int R = pt_num_rois(d);
@@ -75,17 +72,7 @@ __global__ __launch_bounds__(256) void pt_overlap_kernel(PtBatch bt)
     int am = 0;
     // bbox.pyx:33-54; overlaps.argmax(axis=1) = first maximum, overlaps.max(axis=1) (:233-237)
     for (int g = 0; g < d.G; ++g) {
-        const double q0 = s_gt[4 * g], q1 = s_gt[4 * g + 1], q2 = s_gt[4 * g + 2], q3 = s_gt[4 * g + 3];
-        double o = 0.0;
-        const double iw = fmin(b2, q2) - fmax(b0, q0) + 1;
-        if (iw > 0) {
-            const double ih = fmin(b3, q3) - fmax(b1, q1) + 1;
-            if (ih > 0) {
-                const double qarea = (q2 - q0 + 1) * (q3 - q1 + 1);
-                const double ua = (b2 - b0 + 1) * (b3 - b1 + 1) + qarea - iw * ih;
-                o = iw * ih / ua;
-            }
-        }
+        const double o = bbox_overlap_f64(b0, b1, b2, b3, s_gt[4 * g], s_gt[4 * g + 1], s_gt[4 * g + 2], s_gt[4 * g + 3]);
         if (g == 0 || o > mx) { mx = o; am = g; }
     }
     d.max_ov[r] = mx;
@@ -196,7 +183,7 @@ __global__ __launch_bounds__(PT_EMIT_THREADS) void pt_emit_kernel(PtBatch bt)
 struct PtLayout { size_t o_maxov, o_assign, o_fg, o_bg, total; };
 static bool pt_layout(int R, int G, PtLayout &L)
 {
-    if (R < 0 || G <= 0 || G > PT_MAX_GT || (long long)R + G > (1 << 22)) return false;
+    if (R < 0 || G <= 0 || G > TARGET_MAX_GT || (long long)R + G > (1 << 22)) return false;
     const size_t n = (size_t)R + G;
     size_t o = 0;
     L.o_maxov = o; o += mv3d_align_up(n * 8);

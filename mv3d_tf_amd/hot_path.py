@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import AnchorTargetParams, ProposalTargetParams, RoiGradView, RoiView, check, lib
+from ._lib import ProposalTargetParams, RoiGradView, RoiView, check, lib
 from .rpn_msr.anchor_target_layer_tf import draw_subsamples
 from .rpn_msr.proposal_target_layer_tf import draw_samples
 
@@ -105,11 +105,9 @@ class TrainPathBatch:
         self.pparams = ops.proposal_params(TRAIN_CFG)
         from .fast_rcnn.config import cfg
         T = cfg.TRAIN
-        self.aparams = AnchorTargetParams(8, 1 if T.RPN_CLOBBER_POSITIVES else 0, float(T.RPN_NEGATIVE_OVERLAP),
-                                          float(T.RPN_POSITIVE_OVERLAP))
-        self.tparams = [ProposalTargetParams(self.nc, b, float(T.FG_THRESH), float(T.BG_THRESH_HI), float(T.BG_THRESH_LO))
-                        for b in range(self.B)]
-        self.anchor_cap = max(int(T.RPN_BATCHSIZE), 1) * 2
+        self.aparams = ops.anchor_target_params(T)
+        self.tparams = [ops.proposal_target_params(T, self.nc, b) for b in range(self.B)]
+        self.anchor_cap = ops.anchor_debug_rows(T)
         self.top_diff_seed = top_diff_seed
         self.bound = None
 

@@ -104,6 +104,25 @@ def proposal_params(cfg_section, feat_stride=8, img_height=375, img_width=1242, 
                           float(cfg_section["RPN_MIN_SIZE"]))
 
 
+def anchor_target_params(T, feat_stride=8):
+    """cfg.TRAIN (anchor_target_layer_tf.py:125-143) -> mv3d_anchor_target_params"""
+    return AnchorTargetParams(int(feat_stride), 1 if T["RPN_CLOBBER_POSITIVES"] else 0, float(T["RPN_NEGATIVE_OVERLAP"]),
+                              float(T["RPN_POSITIVE_OVERLAP"]))
+
+
+def anchor_debug_rows(T):
+    """capacity of anchor_target_layer's debug outputs (anchors, anchors_3d): at most RPN_BATCHSIZE labelled anchors survive
+    the draws of :146-159, and the relabel of :176 can add as many again before the last draw"""
+    return max(int(T["RPN_BATCHSIZE"]), 1) * 2
+
+
+def proposal_target_params(T, num_classes, frame_index=0):
+    """cfg.TRAIN (proposal_target_layer_tf.py:246-260) -> mv3d_proposal_target_params; `frame_index` is the batch column of
+    the ground-truth rows a batched caller appends to frame b's proposals (0 in the reference)"""
+    return ProposalTargetParams(int(num_classes), int(frame_index), float(T["FG_THRESH"]), float(T["BG_THRESH_HI"]),
+                                float(T["BG_THRESH_LO"]))
+
+
 def proposal_3d_outputs(B, cap, dev):
     """The five outputs of proposal_3d as views of ONE buffer (bv | img | 3d | num | status, 4-byte slots), so that
     a host consumer fetches them with a single device-to-host copy.  Returns (pack, (bv, img, b3, num, status))."""

@@ -12,45 +12,38 @@ import numpy.random as npr
 import torch
 
 from .. import ops
-from .._lib import AnchorTargetParams
 from ..fast_rcnn.config import cfg
 
 
-def draw_subsamples(cf, fg_hi, N):
+REPORT_HEAD = 4096                 # bytes of (counts + foreground flags) per frame that travel with the first copy
+
+
+def draw_subsamples_host(head, fetch_flags, N):
     """The three random subsamplings of anchor_target_layer_tf.py:146-183, drawn from the numpy GLOBAL RNG in the
-    reference's order given stage 1's device results (`cf` = counts + per-foreground flags in one buffer).  Returns the
+    reference's order given stage 1's counts + foreground flags as HOST bytes (`head`, the first REPORT_HEAD bytes of the
+    frame's report of 32 + N; `fetch_flags()` returns all flags in the rare case of more positives than fit).  Returns the
     positions to disable in the fg list, the first bg list and the second bg list (None = no subsampling)."""
     T = cfg.TRAIN
-    # host sync #1: the counts and (usually all of) the foreground flags in one copy
-    first = min(32 + N, 4096)
-    head = cf[:first].cpu().numpy()
     n_inside, n_fg, n_bg, n_low = (int(v) for v in head[:16].view(np.int32))
-    # anchor_target_layer_tf.py:146-151
     num_fg = int(T.RPN_FG_FRACTION * T.RPN_BATCHSIZE)
-    dis_fg = None
-    if n_fg > num_fg:
-        dis_fg = npr.permutation(n_fg)[:n_fg - num_fg]
-    # :154-159
+    dis_fg = npr.permutation(n_fg)[:n_fg - num_fg] if n_fg > num_fg else None                 # :146-151
     num_bg = T.RPN_BATCHSIZE - min(n_fg, num_fg)
-    dis_bg1 = None
-    if n_bg > num_bg:
-        dis_bg1 = npr.permutation(n_bg)[:n_bg - num_bg]
-    # :176-183 positives that survive `labels[max_overlaps < RPN_NEGATIVE_OVERLAP] = 0`
-    if n_fg:
-        if 32 + n_fg <= first:
-            alive = head[32:32 + n_fg].astype(bool)
-        else:
-            alive = fg_hi[:n_fg].cpu().numpy().astype(bool)                        # host sync #2 (rare: > 4064 positives)
+    dis_bg1 = npr.permutation(n_bg)[:n_bg - num_bg] if n_bg > num_bg else None                # :154-159
+    n_pos = 0
+    if n_fg:                                  # :176-183 positives that survive `labels[max_overlaps < RPN_NEGATIVE_OVERLAP] = 0`
+        alive = (head[32:32 + n_fg] if 32 + n_fg <= len(head) else fetch_flags()[:n_fg]).astype(bool)
         if dis_fg is not None:
             alive[dis_fg] = False
         n_pos = int(alive.sum())
-    else:
-        n_pos = 0
     num_bg2 = T.RPN_BATCHSIZE - n_pos
-    dis_bg2 = None
-    if n_low > num_bg2:
-        dis_bg2 = npr.permutation(n_low)[:n_low - num_bg2]
+    dis_bg2 = npr.permutation(n_low)[:n_low - num_bg2] if n_low > num_bg2 else None
     return dis_fg, dis_bg1, dis_bg2
+
+
+def draw_subsamples(cf, fg_hi, N):
+    """draw_subsamples_host on stage 1's device results (`cf` = counts + per-foreground flags in one buffer)"""
+    head = cf[:min(32 + N, REPORT_HEAD)].cpu().numpy()           # host sync #1: the counts and (usually all of) the flags in one copy
+    return draw_subsamples_host(head, lambda: fg_hi.cpu().numpy(), N)          # host sync #2 (rare: > 4064 positives)
 
 
 def anchor_target_layer(rpn_cls_score, gt_boxes, gt_boxes_3d, im_info, _feat_stride=[8, ], anchor_scales=[1.0, 1.0]):
@@ -69,10 +62,9 @@ def anchor_target_layer(rpn_cls_score, gt_boxes, gt_boxes_3d, im_info, _feat_str
         info = ops._dev(im_info, device=dev).reshape(-1)[:3].contiguous()
     T = cfg.TRAIN
     stride = int(np.asarray(_feat_stride).reshape(-1)[0])
-    params = AnchorTargetParams(stride, 1 if T.RPN_CLOBBER_POSITIVES else 0, float(T.RPN_NEGATIVE_OVERLAP),
-                                float(T.RPN_POSITIVE_OVERLAP))
+    params = ops.anchor_target_params(T, stride)
     N = H * W * 4
-    cap = max(int(T.RPN_BATCHSIZE), 1) * 2
+    cap = ops.anchor_debug_rows(T)
     spec = [((N,), torch.float32), ((N, 6), torch.float32), ((cap, 5), torch.float32), ((cap, 7), torch.float32),
             ((1,), torch.int32)]
     pack, (labels, targets, anchors, anchors_3d, n_anc) = ops.packed_views(spec, dev)   # all outputs: one buffer

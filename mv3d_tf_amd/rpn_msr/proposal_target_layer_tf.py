@@ -10,15 +10,14 @@ import numpy.random as npr
 import torch
 
 from .. import ops
-from .._lib import ProposalTargetParams
 from ..fast_rcnn.config import cfg
 
 
-def draw_samples(counts):
+def draw_samples_host(counts):
     """The two `npr.choice(..., replace=False)` draws of _sample_rois_3d (:246-269) from the numpy GLOBAL RNG given stage 1's
-    device counts: positions in the fg / bg candidate lists."""
+    counts (candidates, fg, bg, -) on the host: positions in the fg / bg candidate lists."""
     T = cfg.TRAIN
-    _, n_fg, n_bg, _ = (int(v) for v in counts.cpu().numpy())                    # the one host sync
+    n_fg, n_bg = int(counts[1]), int(counts[2])
     rois_per_image = T.BATCH_SIZE // 1                                            # :55-57
     fg_rois_per_image = np.round(T.FG_FRACTION * rois_per_image)
     fg_n = int(min(fg_rois_per_image, n_fg))                                      # :251
@@ -26,6 +25,11 @@ def draw_samples(counts):
     bg_n = int(min(rois_per_image - fg_n, n_bg))                                  # :264-266
     bg_pick = npr.permutation(n_bg)[:bg_n] if n_bg > 0 else np.zeros(0, np.int64)   # :268-269
     return fg_pick, bg_pick
+
+
+def draw_samples(counts):
+    """draw_samples_host on stage 1's device counts"""
+    return draw_samples_host(counts.cpu().numpy())                                # the one host sync
 
 
 def proposal_target_layer_3d(rpn_rois_bv, rpn_rois_3d, gt_boxes_bv, gt_boxes_3d, gt_boxes_corners, calib, _num_classes):
@@ -51,7 +55,7 @@ def proposal_target_layer_3d(rpn_rois_bv, rpn_rois_3d, gt_boxes_bv, gt_boxes_3d,
         # Sanity check of the reference (:52-53): single batch only
         assert np.all(np.asarray(rpn_rois_bv).reshape(-1, 5)[:, 0] == 0), 'Only single item batches are supported'
     nc = int(_num_classes)
-    params = ProposalTargetParams(nc, 0, float(T.FG_THRESH), float(T.BG_THRESH_HI), float(T.BG_THRESH_LO))
+    params = ops.proposal_target_params(T, nc)
     counts, ws = ops.proposal_target_stage1(rois_bv, rois_3d, gt_bv, gt_3d, params)
     fg_pick, bg_pick = draw_samples(counts)
     if as_numpy:

@@ -24,54 +24,17 @@ With `depth` slots a caller submits batch i + 1 before it finishes batch i: the 
 thread the library owns, and the legacy `RandomState.permutation` shuffles (21 k background anchors per frame, twice) run in C
 on numpy's own generator state (`mv3d_draw_training_subsamples`, csrc/legacy_rng.hip).  Between submit() and finish() of a slot
 the numpy global RNG belongs to the path (any other draw in that window would interleave with the batch's).
-`draw_subsamples_host` / `draw_samples_host` below are the numpy statement of the same draws (tests compare the two, draw for
-draw)."""
+`draw_subsamples_host` / `draw_samples_host` of the two rpn_msr layers are the numpy statement of the same draws (tests compare
+the two, draw for draw)."""
 import ctypes as C
 
 import numpy as np
-import numpy.random as npr
 import torch
 
 from . import ops
-from ._lib import AnchorTargetParams, DrawParams, ProposalTargetParams, TrainPathConfig, TrainPathSlot, check, lib
+from ._lib import DrawParams, TrainPathConfig, TrainPathSlot, check, lib
 from .fast_rcnn.config import cfg
-
-_HEAD = 4096                       # bytes of (counts + foreground flags) per frame that travel with the first copy
-
-
-def draw_subsamples_host(head, n_fg_flags_fetch, N):
-    """anchor_target_layer_tf.py:146-183 given stage 1's counts + foreground flags as HOST bytes (`head`, the first _HEAD
-    bytes of the frame's report; `n_fg_flags_fetch()` returns all flags in the rare case of more positives than fit).
-    Same draws, same order as rpn_msr.anchor_target_layer_tf.draw_subsamples."""
-    T = cfg.TRAIN
-    n_inside, n_fg, n_bg, n_low = (int(v) for v in head[:16].view(np.int32))
-    num_fg = int(T.RPN_FG_FRACTION * T.RPN_BATCHSIZE)
-    dis_fg = npr.permutation(n_fg)[:n_fg - num_fg] if n_fg > num_fg else None                 # :146-151
-    num_bg = T.RPN_BATCHSIZE - min(n_fg, num_fg)
-    dis_bg1 = npr.permutation(n_bg)[:n_bg - num_bg] if n_bg > num_bg else None                # :154-159
-    n_pos = 0
-    if n_fg:                                                                                  # :176-183
-        alive = (head[32:32 + n_fg] if 32 + n_fg <= len(head) else n_fg_flags_fetch()[:n_fg]).astype(bool)
-        if dis_fg is not None:
-            alive[dis_fg] = False
-        n_pos = int(alive.sum())
-    num_bg2 = T.RPN_BATCHSIZE - n_pos
-    dis_bg2 = npr.permutation(n_low)[:n_low - num_bg2] if n_low > num_bg2 else None
-    return dis_fg, dis_bg1, dis_bg2
-
-
-def draw_samples_host(counts):
-    """proposal_target_layer_tf.py:246-269 given stage 1's counts on the host; same draws as
-    rpn_msr.proposal_target_layer_tf.draw_samples."""
-    T = cfg.TRAIN
-    n_fg, n_bg = int(counts[1]), int(counts[2])
-    rois_per_image = T.BATCH_SIZE // 1
-    fg_n = int(min(np.round(T.FG_FRACTION * rois_per_image), n_fg))
-    fg_pick = npr.permutation(n_fg)[:fg_n] if n_fg > 0 else np.zeros(0, np.int64)
-    bg_n = int(min(rois_per_image - fg_n, n_bg))
-    bg_pick = npr.permutation(n_bg)[:bg_n] if n_bg > 0 else np.zeros(0, np.int64)
-    return fg_pick, bg_pick
-
+from .rpn_msr.anchor_target_layer_tf import REPORT_HEAD as _HEAD
 
 def _global_mt19937_address():
     """Address of the {uint32 key[624]; int pos} state of the numpy GLOBAL legacy RandomState, which the library draws on in C
@@ -79,8 +42,8 @@ def _global_mt19937_address():
     or anything else, whose state the C code would scribble over: ADVICE r04).  Threading contract: the helper thread draws
     without numpy's generator lock (a threading.Lock it cannot take from C) -- between submit() and finish() of a slot no other
     thread of the process may draw from the global RNG; the path is for one submitting thread per process."""
-    bg = npr.mtrand._rand._bit_generator
-    if not isinstance(bg, npr.MT19937):
+    bg = np.random.mtrand._rand._bit_generator
+    if not isinstance(bg, np.random.MT19937):
         raise TypeError("TrainPathStream draws on numpy's global legacy MT19937; the global bit generator is a %s" % type(bg).__name__)
     return bg.ctypes.state_address
 
@@ -107,7 +70,7 @@ class TrainPathStream:
         self.streams = list(streams) if streams else None
         self.max_gt = int(max_gt)
         T = cfg.TRAIN
-        self.anchor_cap = max(int(T.RPN_BATCHSIZE), 1) * 2
+        self.anchor_cap = ops.anchor_debug_rows(T)
         self.roi_cap = int(T.BATCH_SIZE)
         L = lib()
         self.pparams = ops.proposal_params(T)
@@ -136,8 +99,8 @@ class TrainPathStream:
         c.batch, c.H, c.W, c.num_classes = self.B, self.H, self.W, self.nc
         c.proposal_cap, c.anchor_cap, c.roi_cap, c.max_gt = self.cap, self.anchor_cap, self.roi_cap, self.max_gt
         c.proposal = self.pparams
-        c.anchor = AnchorTargetParams(8, 1 if T.RPN_CLOBBER_POSITIVES else 0, float(T.RPN_NEGATIVE_OVERLAP), float(T.RPN_POSITIVE_OVERLAP))
-        c.target = ProposalTargetParams(self.nc, 0, float(T.FG_THRESH), float(T.BG_THRESH_HI), float(T.BG_THRESH_LO))
+        c.anchor = ops.anchor_target_params(T)
+        c.target = ops.proposal_target_params(T, self.nc)
         c.draw = DrawParams(int(T.RPN_BATCHSIZE), int(T.RPN_FG_FRACTION * T.RPN_BATCHSIZE), rois_per_image,
                             int(np.round(T.FG_FRACTION * rois_per_image)))
         return key, c

@@ -2,7 +2,8 @@
 of the reference (`npr.choice(..., replace=False)` in lib/rpn_msr/anchor_target_layer_tf.py:146-183 and
 lib/rpn_msr/proposal_target_layer_tf.py:246-269) that /root/reference does not vendor; the restatement is pinned here:
 same permutations, same generator state afterwards, and the batch entry draws exactly what the numpy statement of the two
-target layers' draws (train_path.draw_subsamples_host / draw_samples_host) draws.  CPU only: host code of libmv3d_hip.so."""
+target layers' draws (rpn_msr.anchor_target_layer_tf.draw_subsamples_host / rpn_msr.proposal_target_layer_tf.draw_samples_host)
+draws.  CPU only: host code of libmv3d_hip.so."""
 import ctypes as C
 
 import numpy as np
@@ -43,7 +44,8 @@ def test_permutation_equals_numpy_and_leaves_the_same_state(L, n):
 def test_batch_draws_equal_the_numpy_statement(L):
     from mv3d_tf_amd._lib import DrawFrame, DrawParams
     from mv3d_tf_amd.fast_rcnn.config import cfg
-    from mv3d_tf_amd.train_path import draw_samples_host, draw_subsamples_host
+    from mv3d_tf_amd.rpn_msr.anchor_target_layer_tf import draw_subsamples_host
+    from mv3d_tf_amd.rpn_msr.proposal_target_layer_tf import draw_samples_host
     rng = np.random.RandomState(1)
     T = cfg.TRAIN
     par = DrawParams(int(T.RPN_BATCHSIZE), int(T.RPN_FG_FRACTION * T.RPN_BATCHSIZE), int(T.BATCH_SIZE),
@@ -89,6 +91,54 @@ def test_batch_draws_equal_the_numpy_statement(L):
                                                scratch.ctypes.data_as(C.c_void_p), scratch.size) == 2
         assert L.mv3d_draw_training_subsamples(_state_addr(), B, frames, C.byref(par), lists.ctypes.data_as(C.c_void_p), lists.size, sizes,
                                                scratch.ctypes.data_as(C.c_void_p), 100) == 2
+
+
+def _same_draws(got, want):
+    assert len(got) == len(want)
+    for a, b in zip(got, want):
+        assert (a is None and b is None) or (a is not None and b is not None and a.dtype == b.dtype and np.array_equal(a, b))
+
+
+# (n_fg, N): no foreground; flags travel in the head; last count that fits the head; first that spills (second fetch); well past
+@pytest.mark.parametrize("n_fg,N", [(0, 64), (57, 23104), (4064, 23104), (4065, 23104), (5000, 23104)])
+def test_fetching_anchor_draws_are_the_host_statement(n_fg, N):
+    """draw_subsamples (fetches stage 1's report, here from CPU tensors) against draw_subsamples_host on the same bytes: same
+    three lists, same generator state.  The rule reads the counts only, so n_bg / n_low are set for the three draws to happen
+    (the foreground draw needs more than 32 positives) whatever N is."""
+    import torch
+    from mv3d_tf_amd.rpn_msr.anchor_target_layer_tf import REPORT_HEAD, draw_subsamples, draw_subsamples_host
+    assert REPORT_HEAD == 4096
+    report = np.zeros(32 + N, np.uint8)
+    report[:16].view(np.int32)[:] = (21500, n_fg, 21000, 21400)
+    report[32:32 + n_fg] = np.random.RandomState(n_fg).random_sample(n_fg) < 0.6
+    cf = torch.from_numpy(report.copy())
+    npr.seed(7 + n_fg)
+    got = draw_subsamples(cf, cf[32:], N)
+    after = npr.get_state()
+    fetched = []
+    npr.seed(7 + n_fg)
+    want = draw_subsamples_host(report[:min(32 + N, REPORT_HEAD)], lambda: fetched.append(1) or report[32:], N)
+    st = npr.get_state()
+    assert len(fetched) == (1 if n_fg > REPORT_HEAD - 32 else 0)
+    _same_draws(got, want)
+    assert [a is not None for a in want] == [n_fg > 32, True, True]
+    assert st[2] == after[2] and np.array_equal(st[1], after[1])
+    assert np.array_equal(cf.numpy(), report)                       # neither form writes to the report
+
+
+@pytest.mark.parametrize("n_fg,n_bg", [(0, 0), (1, 1), (40, 1900), (200, 0)])
+def test_fetching_roi_draws_are_the_host_statement(n_fg, n_bg):
+    import torch
+    from mv3d_tf_amd.rpn_msr.proposal_target_layer_tf import draw_samples, draw_samples_host
+    counts = np.array([n_fg + n_bg, n_fg, n_bg, 0], np.int32)
+    npr.seed(11 + n_fg)
+    got = draw_samples(torch.from_numpy(counts.copy()))
+    after = npr.get_state()
+    npr.seed(11 + n_fg)
+    want = draw_samples_host(counts)
+    st = npr.get_state()
+    _same_draws(got, want)
+    assert st[2] == after[2] and np.array_equal(st[1], after[1])
 
 
 def test_a_replaced_global_bit_generator_is_refused():

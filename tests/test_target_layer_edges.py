@@ -178,7 +178,7 @@ def anchor_cases():
     # none of the three draws (76 inside anchors in all), and another batch shape
     add("no_subsampling", (5, 9), (40, 72, 1), [[24, 10, 60, 26, 1]], 91)
     add("batch_shape", (37, 37), (296, 296, 1), scaled_cars(92, 12, 37, 37), 92, RPN_BATCHSIZE=256, RPN_FG_FRACTION=0.5)
-    # AT_MAX_GT
+    # TARGET_MAX_GT
     add("g_limit", (20, 20), (160, 160, 1), scaled_cars(93, 1024, 20, 20), 93)
     return out
 
@@ -238,7 +238,7 @@ def proposal_cases(oracle):
     gz = tuple(a.copy() for a in tgt)
     gz[2][0, [6, 14, 22]] = gz[2][0, [0, 8, 16]]
     add("zero_diagonal", trois, gz, 161)
-    # PT_MAX_GT
+    # TARGET_MAX_GT
     add("g_limit", (bv, b3), scaled_cars(171, 1024, 20, 20), 171)
     return out
 
@@ -691,6 +691,60 @@ def test_proposal_target_layer_on_the_device(ops, oracle, monkeypatch, name):
     out, pos = run_seeded(c, lambda: proposal_target_layer_3d(c["rois_bv"], c["rois_3d"], c["gt_bv"], c["gt_3d"], c["gt_corners"],
                                                               c["calib"], c["num_classes"]))
     compare_device(name, oracle, out, pos)
+
+
+# ---- the shared ground-truth staging (geometry.h: stage_gt_bv) at its bound, on a grid whose height is not its width
+def staging_bound_cases(oracle):
+    """G = 1024 integer boxes inside a 56 x 40 map (H, W = 5, 7 at stride 8: N = 140 anchors); the last 16 repeat the first 16
+    pixel for pixel with other 3D rows, corners and class, so a first-argmax tie between g and g + 1008 shows in every output
+    that follows the assignment.  The proposal layer gets R = 8 proposals, four of them one pixel off a repeated box, and a
+    BATCH_SIZE above R + G, all of it open to foreground, with BG_THRESH_LO = 0: every candidate row is sampled, so every row's
+    assignment is compared."""
+    G, H, W = 1024, 5, 7
+    r = np.random.RandomState(1024)
+    xs, ys = np.sort(r.randint(0, 8 * W, (G, 2)), 1), np.sort(r.randint(0, 8 * H, (G, 2)), 1)
+    rows = np.stack([xs[:, 0], ys[:, 0], xs[:, 1], ys[:, 1], np.ones(G, np.int64)], 1)
+    rows[-16:, :4] = rows[:16, :4]
+    rows[-16:, 4] = 2
+    gt = hand_gt(rows)
+    gt[1][-16:, :6] += np.array([0.5, -0.25, 0.125, 0.75, 0.5, 0.25], F32)
+    gt[2][-16:, :24] += F32(0.25)
+    at = dict(kind="anchor", grid=(H, W), im_info=np.array([[8 * H, 8 * W, 1]], F32), gt_bv=gt[0], gt_3d=gt[1], gt_corners=gt[2],
+              train=dict(TRAIN_DEFAULTS), seed=1024)
+    near = rows[:4, :4] + np.array([1, 0, 1, 0])
+    rois = hand_rois(np.vstack([near, rows[500:504, :4] + np.array([0, 1, 0, 1])]))
+    pt = dict(kind="proposal", rois_bv=rois[0], rois_3d=rois[1], gt_bv=gt[0], gt_3d=gt[1], gt_corners=gt[2],
+              calib=synth.rpn_head(9, H, W, "rand")[3], num_classes=3, seed=1025,
+              train=dict(TRAIN_DEFAULTS, BATCH_SIZE=2048, FG_FRACTION=1.0, BG_THRESH_LO=0.0))
+    return at, pt
+
+
+@pytest.mark.gpu
+def test_ground_truth_staging_at_its_bound(ops, oracle, monkeypatch):
+    from mv3d_tf_amd.rpn_msr.anchor_target_layer_tf import anchor_target_layer
+    from mv3d_tf_amd.rpn_msr.proposal_target_layer_tf import proposal_target_layer_3d
+    at, pt = staging_bound_cases(oracle)
+    H, W = at["grid"]
+    assert at["gt_bv"].shape == (1024, 5) and H * W * 4 == 140 and pt["rois_bv"].shape == (8, 5)
+    assert np.array_equal(at["gt_bv"], np.floor(at["gt_bv"])) and np.array_equal(at["gt_bv"][-16:, :4], at["gt_bv"][:16, :4])
+    # the ties are real: some inside anchor has its maximum on a repeated box, and the four proposals next to one have theirs there
+    A = all_anchors(H, W)
+    inside = (A[:, 0] >= 0) & (A[:, 1] >= 0) & (A[:, 2] < 8 * W) & (A[:, 3] < 8 * H)
+    assert any(ov.argmax() < 16 and ov[ov.argmax() + 1008] == ov.max() for ov in iou_matrix(A[inside], at["gt_bv"][:, :4]))
+    assert all(ov.argmax() < 16 for ov in iou_matrix(pt["rois_bv"][:4, 1:], pt["gt_bv"][:, :4]))
+    with np.errstate(all="ignore"):
+        want_at, want_pt = run_seeded(at, oracle_call(at, oracle)), run_seeded(pt, oracle_call(pt, oracle))
+    assert want_pt[0][0].shape[0] == 8 + 1024                               # every candidate row was sampled
+    patch_train(monkeypatch, at)
+    got = run_seeded(at, lambda: anchor_target_layer(np.zeros((1, H, W, 8), F32), at["gt_bv"], at["gt_3d"], at["im_info"], [8, ],
+                                                     [1.0, 1.0]))
+    assert got[1] == want_at[1]
+    assert_same_outputs(got[0], want_at[0], "anchor_target_layer at G = 1024")
+    patch_train(monkeypatch, pt)
+    got = run_seeded(pt, lambda: proposal_target_layer_3d(pt["rois_bv"], pt["rois_3d"], pt["gt_bv"], pt["gt_3d"], pt["gt_corners"],
+                                                          pt["calib"], pt["num_classes"]))
+    assert got[1] == want_pt[1]
+    assert_same_outputs(got[0], want_pt[0], "proposal_target_layer_3d at G = 1024")
 
 
 # ---- the C entries directly
