@@ -114,6 +114,37 @@ int mv3d_proposal_3d(const float *prob_dev, const float *pred_dev, int batch, in
                      float *blob_bv_dev, float *blob_img_dev, float *blob_3d_dev,
                      int32_t *num_out_dev, int32_t *status_dev,
                      void *workspace, size_t workspace_bytes, void *stream);
+/* mv3d_proposal_3d with the empty anchors taken out (mv3d_anchor_occupancy below): anchor_mask_dev (batch,N) u8, N = 4 H W, anchor
+ * order (h,w,a).  An anchor whose mask is 0 fails the filter exactly like one that fails _filter_boxes: its key is 0, it is not
+ * counted, ranked or emitted.  Nothing else changes (capacity, workspace size, status words).  NULL: every anchor takes part --
+ * mv3d_proposal_3d is this entry with a NULL mask. */
+int mv3d_proposal_3d_masked(const float *prob_dev, const float *pred_dev, int batch, int H, int W,
+                            const float *im_info_dev, const float *calib_dev,
+                            const mv3d_proposal_params *p, const uint8_t *anchor_mask_dev,
+                            float *blob_bv_dev, float *blob_img_dev, float *blob_3d_dev,
+                            int32_t *num_out_dev, int32_t *status_dev,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ empty anchors (MV3D paper, section 3.2; not in the reference)
+ * "Since LIDAR point cloud is sparse, which results in many empty anchors, we remove all the empty anchors during both training
+ * and testing to reduce computation."  The rule, for a BEV map bev_dev (batch,map_h,map_w,channels) f32 NHWC:
+ *   occupancy  cell (y,x) of a frame is OCCUPIED iff at least one of its channels satisfies !(v == 0.0f): -0.0f is empty, NaN and
+ *              subnormals are occupied.
+ *   count      anchor n = (h,w,a), a fastest, of the H x W grid at feat_stride is the integer pixel box x1,y1,x2,y2 of the proposal
+ *              layer / anchor target layer (base anchor a shifted by (w,h) * feat_stride), corners inclusive; count[n] = number of
+ *              occupied cells in the intersection of [x1,x2] x [y1,y2] with [0,map_w-1] x [0,map_h-1]; an empty intersection: 0.
+ *   mask       mask[n] = count[n] >= min_cells (min_cells >= 1).  Counts are exact int32.
+ * mask_dev (batch,4 H W) u8 0 / 1; count_dev (batch,4 H W) i32 or NULL.  Two kernel launches; no allocation, memset,
+ * synchronisation or host read (capturable in a graph); the workspace (256-byte aligned, at least
+ * mv3d_anchor_occupancy_workspace_bytes(), 0 for unsupported sizes) needs no initialisation.  MV3D_ERR_INVALID_ARG before any HIP
+ * call: a NULL pointer (count_dev excepted), batch outside 1..65535, map_h or map_w outside 1..4096, channels outside 1..64,
+ * feat_stride < 1, min_cells < 1, H or W < 1, 4 H W > 65536 (the proposal layer's limit), bev_dev not 4-byte aligned, or a grid
+ * whose last anchor leaves int32 ((max(H,W) - 1) * feat_stride + 20 > INT32_MAX).  MV3D_ERR_WORKSPACE as elsewhere. */
+size_t mv3d_anchor_occupancy_workspace_bytes(int batch, int map_h, int map_w);
+int mv3d_anchor_occupancy(const float *bev_dev, int batch, int map_h, int map_w, int channels,
+                          int H, int W, int feat_stride, int min_cells,
+                          uint8_t *mask_dev, int32_t *count_dev,
+                          void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------ RoiPool / RoiPoolGrad
  * Replace lib/roi_pooling_layer/roi_pooling_op_gpu.h:18-27 (ROIPoolForwardLaucher /
@@ -302,6 +333,21 @@ int mv3d_anchor_target_stage1_batch(int batch, int H, int W, const float *im_inf
                                     const float *const *gt_3d_dev, const int *G, const mv3d_anchor_target_params *p,
                                     float *labels_dev, float *targets_dev, int32_t *const *counts_dev,
                                     uint8_t *const *fg_hi_dev, void *const *workspace, size_t workspace_bytes, void *stream);
+/* stage 1 with the empty anchors taken out: anchor_mask_dev is a host array of `batch` device pointers to (N) u8 masks
+ * (mv3d_anchor_occupancy); an entry, or the array itself, may be NULL (= no mask for that frame).  An anchor whose mask is 0 is
+ * treated as OUTSIDE the image (the mask extends inds_inside of anchor_target_layer_tf.py:93-98): label -1, target 0, max_overlap
+ * -1, in no candidate list and no count, and no part of a ground-truth box's column maximum -- the "every anchor tying the column
+ * max" flood moves to the best non-empty anchor.  A ground-truth box ALL of whose overlapping inside anchors are masked (a car
+ * with no return under it) is left with a column maximum of 0, and then, as in the reference when a box lies outside every
+ * inside anchor, every surviving anchor whose overlap with it is 0 -- nearly all of them -- ties that maximum and
+ * is labelled positive before the subsampling.  That is the reference's rule applied to the reduced anchor set, kept as it is;
+ * a caller that turns the mask on should drop such boxes from gt first if it does not want the flood.  Stage 2 is unchanged.
+ * mv3d_anchor_target_stage1_batch is this entry with a NULL array. */
+int mv3d_anchor_target_stage1_batch_masked(int batch, int H, int W, const float *im_info_dev, const float *const *gt_bv_dev,
+                                           const float *const *gt_3d_dev, const int *G, const mv3d_anchor_target_params *p,
+                                           const uint8_t *const *anchor_mask_dev, float *labels_dev, float *targets_dev,
+                                           int32_t *const *counts_dev, uint8_t *const *fg_hi_dev, void *const *workspace,
+                                           size_t workspace_bytes, void *stream);
 int mv3d_anchor_target_stage2_batch(int batch, int H, int W, const mv3d_anchor_target_params *p,
                                     const int32_t *const *disable_fg_dev, const int *n_dis_fg,
                                     const int32_t *const *disable_bg1_dev, const int *n_dis_bg1,
@@ -488,6 +534,14 @@ int mv3d_train_path_configure(mv3d_train_path *path, const mv3d_train_path_confi
 int mv3d_train_path_submit(mv3d_train_path *path, int slot, const float *prob_dev, const float *pred_dev, const float *im_info_dev,
                            const float *calib_dev, const float *const *gt_bv_dev, const float *const *gt_3d_dev,
                            const float *const *gt_corners_dev, const int *G, void *mt19937_state, void *stream);
+/* submit with the frames' empty-anchor masks: anchor_mask_dev (B,N) u8, contiguous (mv3d_anchor_occupancy), or NULL.  It is handed
+ * to the batch's proposal layer and anchor-target stage 1 (the masked entries above) and, like the other inputs, must stay valid
+ * until finish() has returned.  The draws, the helper thread and finish() are the same.  mv3d_train_path_submit is this entry with
+ * a NULL mask. */
+int mv3d_train_path_submit_masked(mv3d_train_path *path, int slot, const float *prob_dev, const float *pred_dev,
+                                  const float *im_info_dev, const float *calib_dev, const float *const *gt_bv_dev,
+                                  const float *const *gt_3d_dev, const float *const *gt_corners_dev, const int *G,
+                                  const uint8_t *anchor_mask_dev, void *mt19937_state, void *stream);
 /* rows_out (B): sampled ROIs per frame (frame b's rows start at the sum of the frames before it); num_proposals_out (B); sizes_out
  * (5 B, may be NULL): the lengths of the drawn lists as mv3d_draw_training_subsamples reports them.  Returns the first error of the
  * slot's host stage (MV3D_ERR_ZERO_DIVISION where the reference's NMS raises); the slot is free again either way. */

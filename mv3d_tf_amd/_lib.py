@@ -161,6 +161,11 @@ _SIGS = {
     "mv3d_proposal_3d_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.POINTER(ProposalParams)]),
     "mv3d_proposal_3d": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(ProposalParams),
                                    _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv3d_proposal_3d_masked": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(ProposalParams),
+                                          _P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv3d_anchor_occupancy_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "mv3d_anchor_occupancy": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P,
+                                        C.c_size_t, _P]),
     "mv3d_roi_pool_forward": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, _P, _P, _P, _P]),
     "mv3d_roi_pool_backward": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -172,6 +177,8 @@ _SIGS = {
                                             C.c_int, _P, C.c_int, _P, _P, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "mv3d_anchor_target_stage1_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(AnchorTargetParams), _P, _P, _P, _P,
                                                   _P, C.c_size_t, _P]),
+    "mv3d_anchor_target_stage1_batch_masked": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.POINTER(AnchorTargetParams), _P, _P,
+                                                         _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_anchor_target_stage2_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(AnchorTargetParams), _P, _P, _P, _P, _P, _P, _P,
                                                   _P, _P, _P, C.c_int, _P, C.c_size_t, _P]),
     "mv3d_proposal_target_stage1_batch": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -216,6 +223,7 @@ _SIGS = {
     "mv3d_train_path_create": (C.c_int, [C.POINTER(TrainPathConfig), C.c_int, C.POINTER(TrainPathSlot), C.c_int, C.POINTER(C.c_void_p)]),
     "mv3d_train_path_configure": (C.c_int, [_P, C.POINTER(TrainPathConfig)]),
     "mv3d_train_path_submit": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mv3d_train_path_submit_masked": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mv3d_train_path_finish": (C.c_int, [_P, C.c_int, _P, _P, _P]),
     "mv3d_train_path_host_seconds": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mv3d_train_path_destroy": (None, [_P]),

@@ -44,6 +44,7 @@ struct AtDev {
     int H, W, N, G, stride, clobber;
     double neg_ov, pos_ov;
     const float *im_info, *gt_bv, *gt_3d;
+    const uint8_t *mask;             // (N)  0 = an empty anchor, treated as outside (stage 1 of the masked entry), or NULL
     double *max_ov;                  // (N)  -1 for anchors outside the image
     int32_t *argmax;                 // (N)
     unsigned long long *gtpart;      // (G, nblk) bit pattern of the column max (>= 0) over the anchors of one workgroup
@@ -75,7 +76,7 @@ __device__ __forceinline__ bool anchor_box(const AtDev &d, int n, int &x1, int &
 {
     grid_anchor(n, d.W, d.stride, x1, y1, x2, y2);
     // anchor_target_layer_tf.py:93-98 (_allowed_border = 0)
-    return x1 >= 0 && y1 >= 0 && (double)x2 < (double)d.im_info[1] && (double)y2 < (double)d.im_info[0];
+    return x1 >= 0 && y1 >= 0 && (double)x2 < (double)d.im_info[1] && (double)y2 < (double)d.im_info[0] && (!d.mask || d.mask[n]);
 }
 
 __global__ __launch_bounds__(256) void at_overlap_kernel(AtBatch bt)
@@ -291,11 +292,12 @@ static void at_frame(AtFrame &F, const AtLayout &L, int H, int W, int G, const m
     F.agg1 = (int32_t *)(ws + L.o_agg1); F.agg2 = (int32_t *)(ws + L.o_agg2);
 }
 
-extern "C" int mv3d_anchor_target_stage1_batch(int batch, int H, int W, const float *im_info_dev, const float *const *gt_bv_dev,
-                                               const float *const *gt_3d_dev, const int *G, const mv3d_anchor_target_params *p,
-                                               float *labels_dev, float *targets_dev, int32_t *const *counts_dev,
-                                               uint8_t *const *fg_hi_dev, void *const *workspace, size_t workspace_bytes,
-                                               void *stream)
+extern "C" int mv3d_anchor_target_stage1_batch_masked(int batch, int H, int W, const float *im_info_dev,
+                                                      const float *const *gt_bv_dev, const float *const *gt_3d_dev, const int *G,
+                                                      const mv3d_anchor_target_params *p, const uint8_t *const *anchor_mask_dev,
+                                                      float *labels_dev, float *targets_dev, int32_t *const *counts_dev,
+                                                      uint8_t *const *fg_hi_dev, void *const *workspace, size_t workspace_bytes,
+                                                      void *stream)
 {
     if (batch <= 0 || batch > AT_MAX_BATCH || !p || p->feat_stride <= 0 || !im_info_dev || !labels_dev || !targets_dev ||
         !gt_bv_dev || !gt_3d_dev || !G || !counts_dev || !fg_hi_dev || !workspace)
@@ -310,6 +312,7 @@ extern "C" int mv3d_anchor_target_stage1_batch(int batch, int H, int W, const fl
         AtFrame &F = bt.f[b];
         at_frame(F, L, H, W, G[b], p, (char *)workspace[b]);
         F.d.im_info = im_info_dev + 3 * b; F.d.gt_bv = gt_bv_dev[b]; F.d.gt_3d = gt_3d_dev[b];
+        F.d.mask = anchor_mask_dev ? anchor_mask_dev[b] : nullptr;
         F.d.labels = labels_dev + (size_t)b * L.N; F.d.targets = targets_dev + (size_t)b * L.N * 6;
         F.counts = counts_dev[b]; F.fg_hi = fg_hi_dev[b];
     }
@@ -319,6 +322,16 @@ extern "C" int mv3d_anchor_target_stage1_batch(int batch, int H, int W, const fl
     hipLaunchKernelGGL(at_label_kernel, dim3(blocks, batch), dim3(256), 0, s, bt);
     hipLaunchKernelGGL(at_compact_kernel, dim3(L.ncwg, batch), dim3(256), 0, s, bt);
     return mv3d_launch_status();
+}
+
+extern "C" int mv3d_anchor_target_stage1_batch(int batch, int H, int W, const float *im_info_dev, const float *const *gt_bv_dev,
+                                               const float *const *gt_3d_dev, const int *G, const mv3d_anchor_target_params *p,
+                                               float *labels_dev, float *targets_dev, int32_t *const *counts_dev,
+                                               uint8_t *const *fg_hi_dev, void *const *workspace, size_t workspace_bytes,
+                                               void *stream)
+{
+    return mv3d_anchor_target_stage1_batch_masked(batch, H, W, im_info_dev, gt_bv_dev, gt_3d_dev, G, p, nullptr, labels_dev, targets_dev,
+                                                  counts_dev, fg_hi_dev, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mv3d_anchor_target_stage1(int H, int W, const float *im_info_dev, const float *gt_bv_dev,
@@ -353,7 +366,7 @@ extern "C" int mv3d_anchor_target_stage2_batch(int batch, int H, int W, const mv
         if (!workspace[b] || workspace_bytes < L.total || ((uintptr_t)workspace[b] % MV3D_ALIGN)) return MV3D_ERR_WORKSPACE;
         AtFrame &F = bt.f[b];
         at_frame(F, L, H, W, 0, p, (char *)workspace[b]);
-        F.d.im_info = nullptr; F.d.gt_bv = nullptr; F.d.gt_3d = nullptr; F.d.targets = nullptr;
+        F.d.im_info = nullptr; F.d.gt_bv = nullptr; F.d.gt_3d = nullptr; F.d.mask = nullptr; F.d.targets = nullptr;
         F.d.labels = labels_dev + (size_t)b * L.N;
         F.dis_fg = disable_fg_dev[b]; F.dis_bg1 = disable_bg1_dev[b]; F.dis_bg2 = disable_bg2_dev[b];
         F.n_dis_fg = n_dis_fg[b]; F.n_dis_bg1 = n_dis_bg1[b]; F.n_dis_bg2 = n_dis_bg2[b];

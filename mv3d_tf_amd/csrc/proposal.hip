@@ -21,6 +21,7 @@
 
 struct ProposalDev {
     const float *prob, *pred, *im_info, *calib;
+    const uint8_t *mask;     // (batch, N) 0 = the anchor is no candidate (mv3d_proposal_3d_masked), or NULL
     int H, W, N, key_stride;
     int feat_stride, img_h, img_w, img_pad;
     float min_size;
@@ -80,6 +81,7 @@ __global__ __launch_bounds__(DEC_THREADS) void proposal_decode_kernel(ProposalDe
         ok = ok && (-d.img_pad <= I[0]) && (I[2] <= d.img_w + d.img_pad) &&       // :343-352
              (-d.img_pad <= I[1]) && (I[3] <= d.img_h + d.img_pad);
         const long long o = (long long)f * d.N + n;
+        ok = ok && (!d.mask || d.mask[o]);                                         // an empty anchor fails like a filtered box
         d.bv[o] = make_float4(B0, B1, B2, B3);
         d.img[o] = make_int4(I[0], I[1], I[2], I[3]);
         float *q = d.p3 + o * 6;
@@ -149,10 +151,11 @@ extern "C" size_t mv3d_proposal_3d_workspace_bytes(int batch, int H, int W, cons
     return proposal_layout(batch, H, W, p, L) ? L.total : 0;
 }
 
-extern "C" int mv3d_proposal_3d(const float *prob_dev, const float *pred_dev, int batch, int H, int W,
-                                const float *im_info_dev, const float *calib_dev, const mv3d_proposal_params *p,
-                                float *blob_bv_dev, float *blob_img_dev, float *blob_3d_dev, int32_t *num_out_dev,
-                                int32_t *status_dev, void *workspace, size_t workspace_bytes, void *stream)
+extern "C" int mv3d_proposal_3d_masked(const float *prob_dev, const float *pred_dev, int batch, int H, int W,
+                                       const float *im_info_dev, const float *calib_dev, const mv3d_proposal_params *p,
+                                       const uint8_t *anchor_mask_dev, float *blob_bv_dev, float *blob_img_dev,
+                                       float *blob_3d_dev, int32_t *num_out_dev, int32_t *status_dev, void *workspace,
+                                       size_t workspace_bytes, void *stream)
 {
     ProposalLayout L;
     if (!proposal_layout(batch, H, W, p, L)) return MV3D_ERR_INVALID_ARG;
@@ -165,7 +168,7 @@ extern "C" int mv3d_proposal_3d(const float *prob_dev, const float *pred_dev, in
     int32_t *cnt = (int32_t *)(ws + L.o_cnt);          // no memset: every word is written before it is read
 
     ProposalDev d;
-    d.prob = prob_dev; d.pred = pred_dev; d.im_info = im_info_dev; d.calib = calib_dev;
+    d.prob = prob_dev; d.pred = pred_dev; d.im_info = im_info_dev; d.calib = calib_dev; d.mask = anchor_mask_dev;
     d.H = H; d.W = W; d.N = L.N; d.key_stride = L.key_stride; d.feat_stride = p->feat_stride;
     d.img_h = p->img_height; d.img_w = p->img_width; d.img_pad = p->img_padding;
     d.min_size = (float)p->min_size;
@@ -194,4 +197,13 @@ extern "C" int mv3d_proposal_3d(const float *prob_dev, const float *pred_dev, in
     nl.emit.blob_bv = blob_bv_dev; nl.emit.blob_img = blob_img_dev; nl.emit.blob_3d = blob_3d_dev;
     nl.emit.num_out = num_out_dev;
     return mv3d_launch_nms(nl, s);
+}
+
+extern "C" int mv3d_proposal_3d(const float *prob_dev, const float *pred_dev, int batch, int H, int W,
+                                const float *im_info_dev, const float *calib_dev, const mv3d_proposal_params *p,
+                                float *blob_bv_dev, float *blob_img_dev, float *blob_3d_dev, int32_t *num_out_dev,
+                                int32_t *status_dev, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return mv3d_proposal_3d_masked(prob_dev, pred_dev, batch, H, W, im_info_dev, calib_dev, p, nullptr, blob_bv_dev, blob_img_dev,
+                                   blob_3d_dev, num_out_dev, status_dev, workspace, workspace_bytes, stream);
 }

@@ -325,9 +325,10 @@ extern "C" int mv3d_train_path_configure(mv3d_train_path *tp, const mv3d_train_p
     return MV3D_OK;
 }
 
-extern "C" int mv3d_train_path_submit(mv3d_train_path *tp, int slot, const float *prob, const float *pred, const float *im_info,
-                                      const float *calib, const float *const *gt_bv, const float *const *gt_3d,
-                                      const float *const *gt_corners, const int *G, void *mt19937_state, void *stream)
+extern "C" int mv3d_train_path_submit_masked(mv3d_train_path *tp, int slot, const float *prob, const float *pred, const float *im_info,
+                                             const float *calib, const float *const *gt_bv, const float *const *gt_3d,
+                                             const float *const *gt_corners, const int *G, const uint8_t *anchor_mask,
+                                             void *mt19937_state, void *stream)
 {
     if (!tp || slot < 0 || slot >= tp->depth || !prob || !pred || !im_info || !calib || !gt_bv || !gt_3d || !gt_corners || !G ||
         !mt19937_state)
@@ -346,11 +347,14 @@ extern "C" int mv3d_train_path_submit(mv3d_train_path *tp, int slot, const float
     s.mt = mt19937_state;
     s.calib = calib;
     for (int b = 0; b < B; ++b) { s.gt_bv[b] = gt_bv[b]; s.gt_3d[b] = gt_3d[b]; s.gt_c[b] = gt_corners[b]; s.G[b] = G[b]; }
-    int rc = mv3d_proposal_3d(prob, pred, B, c.H, c.W, im_info, calib, &c.proposal, u.blob_bv, u.blob_img, u.blob_3d, u.num_proposals,
-                              u.num_proposals + B, u.proposal_ws, u.proposal_ws_bytes, stream);
+    // anchor_mask (B, N): the frames' empty-anchor masks for the proposal layer and the anchor targets (NULL: every anchor takes part)
+    const uint8_t *masks[TP_MAX_BATCH];
+    for (int b = 0; b < B; ++b) masks[b] = anchor_mask ? anchor_mask + (size_t)b * 4 * c.H * c.W : nullptr;
+    int rc = mv3d_proposal_3d_masked(prob, pred, B, c.H, c.W, im_info, calib, &c.proposal, anchor_mask, u.blob_bv, u.blob_img, u.blob_3d,
+                                     u.num_proposals, u.num_proposals + B, u.proposal_ws, u.proposal_ws_bytes, stream);
     if (rc != MV3D_OK) return rc;
-    rc = mv3d_anchor_target_stage1_batch(B, c.H, c.W, im_info, s.gt_bv, s.gt_3d, s.G, &c.anchor, u.rpn_labels, u.rpn_targets, s.a_cnt,
-                                         s.a_fgh, s.a_ws, u.anchor_ws_bytes, stream);
+    rc = mv3d_anchor_target_stage1_batch_masked(B, c.H, c.W, im_info, s.gt_bv, s.gt_3d, s.G, &c.anchor, masks, u.rpn_labels, u.rpn_targets,
+                                                s.a_cnt, s.a_fgh, s.a_ws, u.anchor_ws_bytes, stream);
     if (rc != MV3D_OK) return rc;
     rc = mv3d_proposal_target_stage1_batch_devn(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.G, tp->tpar, s.p_cnt, s.p_ws,
                                                 s.p_wsz, stream);
@@ -382,6 +386,13 @@ extern "C" int mv3d_train_path_submit(mv3d_train_path *tp, int slot, const float
     }
     if (tp->threaded) tp->cv_work.notify_one();
     return MV3D_OK;
+}
+
+extern "C" int mv3d_train_path_submit(mv3d_train_path *tp, int slot, const float *prob, const float *pred, const float *im_info,
+                                      const float *calib, const float *const *gt_bv, const float *const *gt_3d,
+                                      const float *const *gt_corners, const int *G, void *mt19937_state, void *stream)
+{
+    return mv3d_train_path_submit_masked(tp, slot, prob, pred, im_info, calib, gt_bv, gt_3d, gt_corners, G, nullptr, mt19937_state, stream);
 }
 
 extern "C" int mv3d_train_path_finish(mv3d_train_path *tp, int slot, int32_t *rows_out, int32_t *num_proposals_out, int32_t *sizes_out)

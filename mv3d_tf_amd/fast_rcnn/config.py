@@ -42,7 +42,11 @@ cfg.TRAIN = _section(
     # (not in the reference) True: the trunks' convolutions on this library's MFMA kernels in the precision MIXED_PRECISION selects --
     # with MIXED_PRECISION False that is the exact-f32 kernels (v_mfma_f32_32x32x2_f32): the reference's precision, 52.9 -> 47.6 ms
     # in a single process (under data parallelism the trunks share one stream and MIOpen's fp32 kernels are the faster choice).
-    MFMA_TRUNK=False)
+    MFMA_TRUNK=False,
+    # (not in the reference) True: the MV3D paper's empty-anchor removal (section 3.2) -- anchors with fewer than
+    # RPN_EMPTY_ANCHOR_MIN_CELLS occupied cells of the bird's-eye-view map under them (ops.anchor_occupancy) get no RPN label and are
+    # no proposal candidates.  False = the reference, which runs every anchor.
+    RPN_SKIP_EMPTY_ANCHORS=False, RPN_EMPTY_ANCHOR_MIN_CELLS=1)
 cfg.TEST = _section(
     NMS=0.5, HAS_RPN=True, RPN_NMS_THRESH=0.7, RPN_PRE_NMS_TOP_N=12000, RPN_POST_NMS_TOP_N=2000, RPN_MIN_SIZE=5,
     DEBUG_TIMELINE=False,
@@ -61,7 +65,10 @@ cfg.TEST = _section(
     # the key on (get_output_dir below refuses a detection loop without oriented NMS).
     # NMS_ORIENTED_BOXES: 'regressed' = the class's regressed corners, which are then also what all_boxes_cnr stores, or
     # 'proposal' = the proposal's own corners
-    NMS_ORIENTED=False, NMS_ORIENTED_BOXES='regressed')
+    NMS_ORIENTED=False, NMS_ORIENTED_BOXES='regressed',
+    # (not in the reference) the paper's empty-anchor removal at test time, as cfg.TRAIN.RPN_SKIP_EMPTY_ANCHORS: the proposal layer
+    # (frame by frame, batched and in the captured ServeGraph step) ranks only the anchors over occupied cells
+    RPN_SKIP_EMPTY_ANCHORS=False, RPN_EMPTY_ANCHOR_MIN_CELLS=1)
 cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14

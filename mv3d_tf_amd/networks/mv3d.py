@@ -433,12 +433,18 @@ class MV3D:
         info, cal = info.contiguous(), cal.contiguous()
         prob = L["rpn_cls_prob_reshape"].detach().contiguous()
         pred = L["rpn_bbox_pred"].detach().contiguous()
+        # (not in the reference) the paper's empty-anchor removal: one mask per step from the RAW bird's-eye-view map as it was fed
+        # (a mirrored frame brings its mirrored map), for the target layers and the proposal layer
+        amask = None
+        if cfg[self.phase].get("RPN_SKIP_EMPTY_ANCHORS", False):
+            amask = L["rpn_anchor_mask"] = ops.anchor_occupancy(L["lidar_bv_data"].detach().float(), h, w, stride,
+                                                               int(cfg[self.phase].get("RPN_EMPTY_ANCHOR_MIN_CELLS", 1)))
         if self.phase == "TRAIN":
             # anchor_target_layer (MV3D_train.py:88) + proposal_layer_3d (:98) + proposal_target_layer_3d (:105), all frames
             # behind one launch per kernel; the subsampling draws come from the numpy global RNG, frame by frame
             gt = [tuple(t.reshape(-1, c).contiguous() for t, c in zip(g, (5, 7, 25))) for g in self._gt_frames(L, B)]
             path = self._train_path(B, h, w, max(int(g[0].shape[0]) for g in gt))
-            out = path.finish(path.submit(prob, pred, info, cal, gt))                 # (views of the slot's buffers: valid for two steps)
+            out = path.finish(path.submit(prob, pred, info, cal, gt, anchor_mask=amask))                 # (views of the slot's buffers: valid for two steps)
             L["roi_rows"] = out["S"]
             bvb, imgb, b3b = out["proposals"][:3]
             cnt = out["num_proposals"]
@@ -459,9 +465,9 @@ class MV3D:
         else:
             if getattr(self, "fixed_rois", False):
                 # the serving step as a capturable graph (fast_rcnn.test_mv.ServeGraph): B * cap rows, no host sync; num_rois read later
-                bv, img, b3, L["num_rois"], L["rois_status"], L["rois_per_frame"] = proposal_layer_3d_fixed(prob, pred, info, cal, self.phase, stride)
+                bv, img, b3, L["num_rois"], L["rois_status"], L["rois_per_frame"] = proposal_layer_3d_fixed(prob, pred, info, cal, self.phase, stride, anchor_mask=amask)
             else:
-                bv, img, b3 = proposal_layer_3d(prob, pred, info, cal, self.phase, [stride, ], anchor_scales)
+                bv, img, b3 = proposal_layer_3d(prob, pred, info, cal, self.phase, [stride, ], anchor_scales, anchor_mask=amask)
             rois = (bv, img, b3, b3)
             L["rois"] = rois
             L["roi_data_bv"], L["roi_data_img"] = rois[0], rois[1]

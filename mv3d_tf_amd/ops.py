@@ -135,10 +135,59 @@ def proposal_3d_outputs(B, cap, dev):
     return pack, (bv, img, b3, tail[:B], tail[B:])
 
 
-def proposal_3d(prob, pred, im_info, calib, params, out=None):
+def anchor_mask_tensor(anchor_mask, B, N, device):
+    """An empty-anchor mask as the kernels take it: numpy / tensor, bool or uint8, (N,) or (B, N) -> contiguous (B, N) uint8
+    device tensor (None stays None)."""
+    if anchor_mask is None:
+        return None
+    if isinstance(anchor_mask, torch.Tensor):
+        m = anchor_mask.to(device=device)
+        m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8))
+    else:
+        m = torch.as_tensor(np.ascontiguousarray(np.asarray(anchor_mask) != 0).view(np.uint8)).to(device)
+    if m.numel() != B * N:
+        raise ValueError("anchor_mask: %d entries for %d frames of %d anchors" % (m.numel(), B, N))
+    return m.reshape(B, N).contiguous()
+
+
+def anchor_occupancy(bev, H, W, feat_stride=8, min_cells=1, want_counts=False, out=None):
+    """The paper's empty-anchor rule (include/mv3d_hip.h: mv3d_anchor_occupancy; not in the reference).  bev (B,Hm,Wm,C) or
+    (Hm,Wm,C) f32 device tensor, the RAW bird's-eye-view map; H, W the RPN head's grid.  Returns mask (B, 4 H W) u8 -- 1 = at
+    least `min_cells` occupied cells under the anchor -- and, with want_counts, (mask, counts (B, 4 H W) i32).
+    out = (mask, counts or None) reuses buffers.  Asynchronous, two launches."""
+    if bev.dim() == 3:
+        bev = bev.unsqueeze(0)
+    if bev.dtype != torch.float32 or not bev.is_cuda:
+        raise TypeError("anchor_occupancy: a float32 device tensor (B, Hm, Wm, C), got %s on %s" % (bev.dtype, bev.device))
+    bev = bev.contiguous()
+    B, Hm, Wm, Cc = (int(v) for v in bev.shape)
+    N = 4 * int(H) * int(W)
+    dev = bev.device
+    if out is None:
+        mask = torch.empty((B, N), dtype=torch.uint8, device=dev)
+        counts = torch.empty((B, N), dtype=torch.int32, device=dev) if want_counts else None
+    else:
+        mask, counts = out
+        for t, dt, what in ((mask, torch.uint8, "mask"), (counts, torch.int32, "counts")):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and tuple(t.shape) == (B, N) and t.is_contiguous()):
+                raise ValueError("anchor_occupancy: out %s must be a contiguous %s tensor of shape (%d, %d) on %s" % (what, dt, B, N, dev))
+        if mask is None or (want_counts and counts is None):
+            raise ValueError("anchor_occupancy: out = (mask, counts); counts may be None only without want_counts")
+    nbytes = lib().mv3d_anchor_occupancy_workspace_bytes(B, Hm, Wm)
+    if nbytes == 0:
+        check(_lib.ERR_INVALID_ARG, "mv3d_anchor_occupancy_workspace_bytes")
+    ws = _workspace(nbytes, dev, "anchor_occupancy")
+    rc = lib().mv3d_anchor_occupancy(_ptr(bev), B, Hm, Wm, Cc, int(H), int(W), int(feat_stride), int(min_cells), _ptr(mask),
+                                     _ptr(counts), _ptr(ws), ws.numel(), _stream())
+    check(rc, "mv3d_anchor_occupancy")
+    return (mask, counts) if want_counts else mask
+
+
+def proposal_3d(prob, pred, im_info, calib, params, out=None, anchor_mask=None):
     """prob (B,H,W,8), pred (B,H,W,24), im_info (B,3), calib (B,4,12) device f32 tensors.
     Returns (blob_bv (B,cap,5), blob_img (B,cap,5), blob_3d (B,cap,7), num_out (B) i32,
-    status (B) i32); rows >= num_out[b] are zero.  Asynchronous."""
+    status (B) i32); rows >= num_out[b] are zero.  Asynchronous.  anchor_mask (B, 4 H W): anchors whose mask is 0 are no
+    candidates (mv3d_proposal_3d_masked)."""
     B, H, W, _ = prob.shape
     dev = prob.device
     cap = lib().mv3d_proposal_3d_capacity(H, W, C.byref(params))
@@ -149,10 +198,16 @@ def proposal_3d(prob, pred, im_info, calib, params, out=None):
     if out is None:
         out = proposal_3d_outputs(B, cap, dev)[1]
     bv, img, b3, num, status = out
-    rc = lib().mv3d_proposal_3d(_ptr(prob), _ptr(pred), B, H, W, _ptr(im_info), _ptr(calib), C.byref(params),
-                                _ptr(bv), _ptr(img), _ptr(b3), _ptr(num), _ptr(status), _ptr(ws), ws.numel(),
-                                _stream())
-    check(rc, "mv3d_proposal_3d")
+    if anchor_mask is None:
+        rc = lib().mv3d_proposal_3d(_ptr(prob), _ptr(pred), B, H, W, _ptr(im_info), _ptr(calib), C.byref(params),
+                                    _ptr(bv), _ptr(img), _ptr(b3), _ptr(num), _ptr(status), _ptr(ws), ws.numel(),
+                                    _stream())
+        check(rc, "mv3d_proposal_3d")
+        return out
+    mask = anchor_mask_tensor(anchor_mask, B, 4 * H * W, dev)
+    rc = lib().mv3d_proposal_3d_masked(_ptr(prob), _ptr(pred), B, H, W, _ptr(im_info), _ptr(calib), C.byref(params), _ptr(mask),
+                                       _ptr(bv), _ptr(img), _ptr(b3), _ptr(num), _ptr(status), _ptr(ws), ws.numel(), _stream())
+    check(rc, "mv3d_proposal_3d_masked")
     return out
 
 
@@ -216,7 +271,8 @@ def roi_pool_backward(top_diff, rois, argmax, data_shape, pooled_height, pooled_
 
 
 # ------------------------------------------------------------------ anchor_target_layer
-def anchor_target_stage1(H, W, im_info, gt_bv, gt_3d, params, labels=None, targets=None):
+def anchor_target_stage1(H, W, im_info, gt_bv, gt_3d, params, labels=None, targets=None, anchor_mask=None):
+    """anchor_mask (N): anchors whose mask is 0 are treated as outside the image (the batched masked entry, batch = 1)"""
     dev = gt_bv.device
     N = H * W * 4
     G = gt_bv.shape[0]
@@ -228,10 +284,19 @@ def anchor_target_stage1(H, W, im_info, gt_bv, gt_3d, params, labels=None, targe
     counts = cf[:32].view(torch.int32)
     fg_hi = cf[32:]
     ws = _workspace(lib().mv3d_anchor_target_workspace_bytes(H, W, G), dev, "anchor_target")
-    rc = lib().mv3d_anchor_target_stage1(H, W, _ptr(im_info), _ptr(gt_bv), _ptr(gt_3d), G, C.byref(params),
-                                         _ptr(labels), _ptr(targets), _ptr(counts), _ptr(fg_hi), _ptr(ws),
-                                         ws.numel(), _stream())
-    check(rc, "mv3d_anchor_target_stage1")
+    if anchor_mask is None:
+        rc = lib().mv3d_anchor_target_stage1(H, W, _ptr(im_info), _ptr(gt_bv), _ptr(gt_3d), G, C.byref(params),
+                                             _ptr(labels), _ptr(targets), _ptr(counts), _ptr(fg_hi), _ptr(ws),
+                                             ws.numel(), _stream())
+        check(rc, "mv3d_anchor_target_stage1")
+        return labels, targets, counts, fg_hi, ws, cf
+    mask = anchor_mask_tensor(anchor_mask, 1, N, dev)
+    P1 = C.c_void_p * 1
+    one = lambda t: P1(0 if t is None else t.data_ptr())
+    rc = lib().mv3d_anchor_target_stage1_batch_masked(1, H, W, _ptr(im_info), one(gt_bv), one(gt_3d), (C.c_int * 1)(G), C.byref(params),
+                                                      one(mask), _ptr(labels), _ptr(targets), one(counts), one(fg_hi), one(ws),
+                                                      ws.numel(), _stream())
+    check(rc, "mv3d_anchor_target_stage1_batch_masked")
     return labels, targets, counts, fg_hi, ws, cf
 
 

@@ -46,8 +46,10 @@ def draw_subsamples(cf, fg_hi, N):
     return draw_subsamples_host(head, lambda: fg_hi.cpu().numpy(), N)          # host sync #2 (rare: > 4064 positives)
 
 
-def anchor_target_layer(rpn_cls_score, gt_boxes, gt_boxes_3d, im_info, _feat_stride=[8, ], anchor_scales=[1.0, 1.0]):
-    """Returns (rpn_labels (N,), rpn_bbox_targets (N,6), anchors (M,5), anchors_3d (M,7)), f32."""
+def anchor_target_layer(rpn_cls_score, gt_boxes, gt_boxes_3d, im_info, _feat_stride=[8, ], anchor_scales=[1.0, 1.0], anchor_mask=None):
+    """Returns (rpn_labels (N,), rpn_bbox_targets (N,6), anchors (M,5), anchors_3d (M,7)), f32.
+    anchor_mask (not in the reference): (N,) bool / uint8, numpy or device tensor -- the paper's empty-anchor removal
+    (ops.anchor_occupancy): an anchor whose mask is 0 is treated as outside the image."""
     assert rpn_cls_score.shape[0] == 1, 'Only single item batches are supported'
     as_numpy = not isinstance(rpn_cls_score, torch.Tensor)
     H, W = int(rpn_cls_score.shape[1]), int(rpn_cls_score.shape[2])
@@ -68,7 +70,7 @@ def anchor_target_layer(rpn_cls_score, gt_boxes, gt_boxes_3d, im_info, _feat_str
     spec = [((N,), torch.float32), ((N, 6), torch.float32), ((cap, 5), torch.float32), ((cap, 7), torch.float32),
             ((1,), torch.int32)]
     pack, (labels, targets, anchors, anchors_3d, n_anc) = ops.packed_views(spec, dev)   # all outputs: one buffer
-    labels, targets, counts, fg_hi, ws, cf = ops.anchor_target_stage1(H, W, info, gt_bv, gt_3d, params, labels, targets)
+    labels, targets, counts, fg_hi, ws, cf = ops.anchor_target_stage1(H, W, info, gt_bv, gt_3d, params, labels, targets, anchor_mask=anchor_mask)
     dis_fg, dis_bg1, dis_bg2 = draw_subsamples(cf, fg_hi, N)
     ops.anchor_target_stage2(H, W, params, dis_fg, dis_bg1, dis_bg2, labels, ws, cap, out=(anchors, anchors_3d, n_anc))
     if as_numpy:

@@ -157,9 +157,11 @@ class TrainPathStream:
         return s
 
     # ------------------------------------------------------------------ stage 1
-    def submit(self, prob, pred, im_info, calib, gt):
+    def submit(self, prob, pred, im_info, calib, gt, anchor_mask=None):
         """prob (B,H,W,8), pred (B,H,W,24), im_info (B,3), calib (B,4,12): device f32 tensors; gt: list (len B) of (gt_bv
-        (G,5), gt_3d (G,7), gt_corners (G,25)) device tensors.  Returns the slot handle for finish()."""
+        (G,5), gt_3d (G,7), gt_corners (G,25)) device tensors.  anchor_mask: (B, N) bool / uint8, numpy or device tensor
+        (ops.anchor_occupancy) -- the frames' empty anchors leave the proposal layer and the anchor targets; None: all take part.
+        Returns the slot handle for finish()."""
         B, L = self.B, lib()
         s = self.slots[self._next]
         if s.busy:
@@ -177,16 +179,22 @@ class TrainPathStream:
             check(L.mv3d_train_path_configure(self._h, C.byref(conf)), "mv3d_train_path_configure")
             self._cfg_key, self._config = key, conf
         self._next = (self._next + 1) % len(self.slots)
+        # (a numpy or bool mask is uploaded / converted on the caller's stream: before the slot's stream is ordered behind that stream)
+        mask = ops.anchor_mask_tensor(anchor_mask, B, self.N, self.dev)
         if s.stream is not None:
             s.stream.wait_stream(torch.cuda.current_stream())            # the inputs were produced on the caller's stream
         st = (s.stream or torch.cuda.current_stream()).cuda_stream
-        s.inputs = (prob, pred, im_info, calib, gt)                              # (kept alive until finish())
+        s.inputs = (prob, pred, im_info, calib, gt, mask)                        # (kept alive until finish())
         s.G = G
         mt = _global_mt19937_address()                                           # the numpy GLOBAL legacy RandomState's MT19937
         PP = C.c_void_p * B
-        check(L.mv3d_train_path_submit(self._h, s.index, prob.data_ptr(), pred.data_ptr(), im_info.data_ptr(), calib.data_ptr(),
-                                       PP(*[g[0].data_ptr() for g in gt]), PP(*[g[1].data_ptr() for g in gt]),
-                                       PP(*[g[2].data_ptr() for g in gt]), (C.c_int * B)(*G), mt, st), "mv3d_train_path_submit")
+        ptrs = (PP(*[g[0].data_ptr() for g in gt]), PP(*[g[1].data_ptr() for g in gt]), PP(*[g[2].data_ptr() for g in gt]), (C.c_int * B)(*G))
+        if mask is None:
+            check(L.mv3d_train_path_submit(self._h, s.index, prob.data_ptr(), pred.data_ptr(), im_info.data_ptr(), calib.data_ptr(),
+                                           *ptrs, mt, st), "mv3d_train_path_submit")
+        else:
+            check(L.mv3d_train_path_submit_masked(self._h, s.index, prob.data_ptr(), pred.data_ptr(), im_info.data_ptr(), calib.data_ptr(),
+                                                  *ptrs, mask.data_ptr(), mt, st), "mv3d_train_path_submit_masked")
         s.busy = True
         return s
 
