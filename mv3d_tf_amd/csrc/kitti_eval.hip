@@ -42,6 +42,9 @@
 //   detection with !(score < t) as fp.
 // Lanes hold detections j = 64 c + lane (c < 32: at most MV3D_KITTI_MAX_DETS detections per frame); the argmax / first-index
 // reductions across lanes give exactly the sequential scan's pick.
+// This is the only statement of the rule: ke_match_wave is pass 1 and ke_count_wave pass 2 for every metric.  A kernel hands them
+// a source object with the three things BEV / 3D and 2D differ in: overlap(j) with the current object (set by object(g)),
+// ignored(j, MIN_HEIGHT), and the pass-2 hooks true_positive(g, j) and keeps_fp(j) on a counted fp ("statistics" below for 2D).
 //
 // 2D detection and orientation (AP_2D, AOS), three more launches over the same split plus a mv3d_kitti_image_split:
 //
@@ -158,6 +161,113 @@ __device__ __forceinline__ int ke_min(int v)
     return v;
 }
 
+// ------------------------------------------------------------------ the two statistics passes, one body each
+// One wave runs one task: a frame (detections d0 .. d0 + D, objects g0 .. g0 + G) at one difficulty; `Src` is its overlap source
+// (header comment, "Matching").  Wave-level operations only (shuffles, ballots, lane-0 stores): barriers stay in the kernels.
+struct KeTask {
+    int d0, D, g0, G, diff, eval_class, neighbor_class;
+    const float *score; const int32_t *cls; const float *attr;     // det_score, gt_cls, gt_attr of the split
+    double min_overlap, min_h;                                      // min_h: MIN_HEIGHT of the difficulty
+    __device__ __forceinline__ int flag(int g) const { return ke_gt_flag(cls, attr, g0 + g, diff, eval_class, neighbor_class); }
+};
+
+// bit c: pred(j) of this lane's detection j = 64 c + lane of chunk c (0 past the frame's D detections)
+template <class Pred>
+__device__ __forceinline__ uint32_t ke_chunk_mask(int D, int lane, Pred pred)
+{
+    uint32_t m = 0u;
+    for (int c = 0; c < (D + 63) >> 6; ++c)
+        if (64 * c + lane < D && pred(64 * c + lane)) m |= 1u << c;
+    return m;
+}
+
+template <class Src>
+__device__ __forceinline__ void ke_match_wave(Src &src, const KeTask &k, int lane, float *__restrict__ out)
+{
+    const int nch = (k.D + 63) >> 6;
+    uint32_t assigned = 0u;
+    for (int g = 0; g < k.G; ++g) {
+        const int flag = k.flag(g);
+        float slot = -INFINITY;
+        if (flag >= 0) {
+            src.object(g);
+            double best = -INFINITY;
+            int bi = INT32_MAX;
+            for (int c = 0; c < nch; ++c) {
+                const int j = 64 * c + lane;
+                if (j < k.D && !((assigned >> c) & 1u) && src.overlap(j) > k.min_overlap) {
+                    const double sc = (double)k.score[k.d0 + j];
+                    if (sc > -10000000.0 && sc > best) { best = sc; bi = j; }
+                }
+            }
+            ke_argmax(best, bi);
+            if (bi != INT32_MAX) {
+                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+                const bool ign_det = src.ignored(bi, k.min_h);
+                if (flag == 0 && !ign_det) slot = k.score[k.d0 + bi];
+            }
+        }
+        if (lane == 0) out[g] = slot;
+    }
+}
+
+// pass 2 at one score threshold t (ign: the mask of src.ignored): the task's tp | fp | fn into o[0..2], integer atomics by lane 0
+template <class Src>
+__device__ __forceinline__ void ke_count_wave(Src &src, const KeTask &k, int lane, uint32_t ign, float t, int32_t *__restrict__ o)
+{
+    const int nch = (k.D + 63) >> 6;
+    const uint32_t cand = ke_chunk_mask(k.D, lane, [&](int j) { return !(k.score[k.d0 + j] < t); });
+    uint32_t assigned = 0u;
+    int tp = 0, fp = 0, fn = 0;
+    for (int g = 0; g < k.G; ++g) {
+        const int flag = k.flag(g);
+        if (flag < 0) continue;
+        src.object(g);
+        double best = -INFINITY;
+        int bi = INT32_MAX, first_ign = INT32_MAX;
+        for (int c = 0; c < nch; ++c) {
+            if (!(((cand & ~assigned) >> c) & 1u)) continue;
+            const int j = 64 * c + lane;
+            const double o = src.overlap(j);
+            if (!(o > k.min_overlap)) continue;
+            if ((ign >> c) & 1u) {
+                if (first_ign == INT32_MAX) first_ign = j;
+            } else if (o > best) {
+                best = o; bi = j;
+            }
+        }
+        ke_argmax(best, bi);
+        if (bi == INT32_MAX) bi = ke_min(first_ign);
+        if (bi == INT32_MAX) {
+            if (flag == 0) ++fn;
+        } else {
+            if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
+            if (flag == 0 && !src.ignored(bi, k.min_h)) {
+                ++tp;
+                src.true_positive(g, bi);
+            }
+        }
+    }
+    for (int c = 0; c < nch; ++c)                       // every unassigned, not ignored candidate that the source keeps
+        fp += __popcll(__ballot((((cand & ~assigned & ~ign) >> c) & 1u) != 0u && src.keeps_fp(64 * c + lane)));
+    if (lane == 0) {
+        if (tp) atomicAdd(o, tp);
+        if (fp) atomicAdd(o + 1, fp);
+        if (fn) atomicAdd(o + 2, fn);
+    }
+}
+
+// BEV / 3D: the frame's D x G block of one metric (global memory or LDS) and the overlap kernel's image heights; no hooks
+struct KeBlockSource {
+    const double *blk, *height;
+    int d0, G, g;
+    __device__ __forceinline__ void object(int gi) { g = gi; }
+    __device__ __forceinline__ double overlap(int j) const { return blk[(long long)j * G + g]; }
+    __device__ __forceinline__ bool ignored(int j, double min_h) const { return height[d0 + j] < min_h; }
+    __device__ __forceinline__ void true_positive(int, int) {}
+    __device__ __forceinline__ bool keeps_fp(int) const { return true; }
+};
+
 __global__ __launch_bounds__(256) void kitti_match_kernel(
     int F, const int32_t *__restrict__ offs, const double *__restrict__ iou, long long P, const float *__restrict__ det_score,
     const double *__restrict__ det_height, const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr, int Gtot,
@@ -168,33 +278,9 @@ __global__ __launch_bounds__(256) void kitti_match_kernel(
     const int f = task / 6, metric = (task / 3) % 2, diff = task % 3;
     const int32_t *det_off = offs, *gt_off = offs + (F + 1), *pair_off = offs + 2 * (F + 1);
     const int d0 = det_off[f], D = det_off[f + 1] - d0, g0 = gt_off[f], G = gt_off[f + 1] - g0;
-    const double *blk = iou + metric * P + pair_off[f];
-    float *out = matched + (long long)(metric * 3 + diff) * Gtot + g0;
-    const int nch = (D + 63) >> 6;
-    const double min_h = (double)c_min_height[diff];
-    uint32_t assigned = 0u;
-    for (int g = 0; g < G; ++g) {
-        const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
-        float slot = -INFINITY;
-        if (flag >= 0) {
-            double best = -INFINITY;
-            int bi = INT32_MAX;
-            for (int c = 0; c < nch; ++c) {
-                const int j = 64 * c + lane;
-                if (j < D && !((assigned >> c) & 1u) && blk[(long long)j * G + g] > min_overlap) {
-                    const double sc = (double)det_score[d0 + j];
-                    if (sc > -10000000.0 && sc > best) { best = sc; bi = j; }
-                }
-            }
-            ke_argmax(best, bi);
-            if (bi != INT32_MAX) {
-                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
-                const bool ign_det = det_height[d0 + bi] < min_h;
-                if (flag == 0 && !ign_det) slot = det_score[d0 + bi];
-            }
-        }
-        if (lane == 0) out[g] = slot;
-    }
+    const KeTask k{d0, D, g0, G, diff, eval_class, neighbor_class, det_score, gt_cls, gt_attr, min_overlap, (double)c_min_height[diff]};
+    KeBlockSource src{iou + metric * P + pair_off[f], det_height, d0, G, 0};
+    ke_match_wave(src, k, lane, matched + (long long)(metric * 3 + diff) * Gtot + g0);
 }
 
 __global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_kernel(
@@ -218,54 +304,12 @@ __global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_kernel(
         __syncthreads();
         blk = s_iou;
     }
-    const int nch = (D + 63) >> 6;
-    const double min_h = (double)c_min_height[diff];
-    uint32_t ign = 0u;
-    for (int c = 0; c < nch; ++c) {
-        const int j = 64 * c + lane;
-        if (j < D && det_height[d0 + j] < min_h) ign |= 1u << c;
-    }
+    const KeTask k{d0, D, g0, G, diff, eval_class, neighbor_class, det_score, gt_cls, gt_attr, min_overlap, (double)c_min_height[diff]};
+    KeBlockSource src{blk, det_height, d0, G, 0};
+    const uint32_t ign = ke_chunk_mask(D, lane, [&](int j) { return src.ignored(j, k.min_h); });
     for (int ti = wave; ti < T; ti += KE_COUNT_WAVES) {
-        const float t = thresholds[md * MV3D_KITTI_NUM_SAMPLE_PTS + ti];
-        uint32_t cand = 0u, assigned = 0u;
-        for (int c = 0; c < nch; ++c) {
-            const int j = 64 * c + lane;
-            if (j < D && !(det_score[d0 + j] < t)) cand |= 1u << c;
-        }
-        int tp = 0, fn = 0;
-        for (int g = 0; g < G; ++g) {
-            const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
-            if (flag < 0) continue;
-            double best = -INFINITY;
-            int bi = INT32_MAX, first_ign = INT32_MAX;
-            for (int c = 0; c < nch; ++c) {
-                if (!(((cand & ~assigned) >> c) & 1u)) continue;
-                const int j = 64 * c + lane;
-                const double o = blk[(long long)j * G + g];
-                if (!(o > min_overlap)) continue;
-                if ((ign >> c) & 1u) {
-                    if (first_ign == INT32_MAX) first_ign = j;
-                } else if (o > best) {
-                    best = o; bi = j;
-                }
-            }
-            ke_argmax(best, bi);
-            if (bi == INT32_MAX) bi = ke_min(first_ign);
-            if (bi == INT32_MAX) {
-                if (flag == 0) ++fn;
-            } else {
-                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
-                if (flag == 0 && !(det_height[d0 + bi] < min_h)) ++tp;
-            }
-        }
-        int fp = 0;
-        for (int c = 0; c < nch; ++c) fp += __popcll(__ballot((((cand & ~assigned & ~ign) >> c) & 1u) != 0u));
-        if (lane == 0) {
-            int32_t *o = counts + 3 * (md * MV3D_KITTI_NUM_SAMPLE_PTS + ti);
-            if (tp) atomicAdd(o, tp);
-            if (fp) atomicAdd(o + 1, fp);
-            if (fn) atomicAdd(o + 2, fn);
-        }
+        const int slot = md * MV3D_KITTI_NUM_SAMPLE_PTS + ti;
+        ke_count_wave(src, k, lane, ign, thresholds[slot], counts + 3 * slot);
     }
 }
 
@@ -356,6 +400,46 @@ __device__ __forceinline__ double ke_iou2d(const double *a, double b0, double b1
     return inter / (((a[2] - a[0]) * (a[3] - a[1]) + area_b) - inter);
 }
 
+// 2D: the overlap computed from the frame's detection image boxes (global memory or LDS) and the object's label box, loaded
+// once per object; a detection is ignored by the height of its image box
+struct KeBoxSource {
+    const double *box;
+    const float *gt_box;
+    int g0;
+    double b0, b1, b2, b3, area_b;
+    __device__ __forceinline__ void object(int g)
+    {
+        const float *gb = gt_box + 4 * (long long)(g0 + g);
+        b0 = gb[0]; b1 = gb[1]; b2 = gb[2]; b3 = gb[3]; area_b = (b2 - b0) * (b3 - b1);
+    }
+    __device__ __forceinline__ double overlap(int j) const { return ke_iou2d(box + 4 * j, b0, b1, b2, b3, area_b); }
+    __device__ __forceinline__ bool ignored(int j, double min_h) const { return box[4 * j + 3] - box[4 * j + 1] < min_h; }
+};
+
+// 2D pass 2: a true positive adds its orientation similarity to s; a counted fp stays unless a DontCare box covers it
+struct KeBoxCountSource : KeBoxSource {
+    const float *gt_alpha, *dc_box;
+    const double *det_cam;
+    int d0, k0, K;
+    double min_overlap, s;
+    __device__ __forceinline__ void true_positive(int g, int j)
+    {
+        s = s + (1.0 + cos((double)gt_alpha[g0 + g] - det_cam[8 * (long long)(d0 + j) + 7])) / 2.0;
+    }
+    __device__ __forceinline__ bool keeps_fp(int j) const     // the devkit's DontCare ("stuff") rule
+    {
+        const double *a = box + 4 * j;
+        const double area_a = (a[2] - a[0]) * (a[3] - a[1]);
+        bool stuff = false;
+        for (int k = 0; k < K && !stuff; ++k) {
+            const float *q = dc_box + 4 * (long long)(k0 + k);
+            const double inter = ke_inter2d(a, q[0], q[1], q[2], q[3]);
+            stuff = inter > 0.0 && inter / area_a > min_overlap;
+        }
+        return !stuff;
+    }
+};
+
 __global__ __launch_bounds__(256) void kitti_match_2d_kernel(
     int F, const int32_t *__restrict__ offs, const double *__restrict__ det_box, const float *__restrict__ det_score,
     const int32_t *__restrict__ gt_cls, const float *__restrict__ gt_attr, const float *__restrict__ gt_box, int Gtot,
@@ -373,35 +457,10 @@ __global__ __launch_bounds__(256) void kitti_match_2d_kernel(
         box = s_box[wave];
     }
     __syncthreads();
-    if (!active) return;
-    float *out = matched + (long long)diff * Gtot + g0;
-    const int nch = (D + 63) >> 6;
-    const double min_h = (double)c_min_height[diff];
-    uint32_t assigned = 0u;
-    for (int g = 0; g < G; ++g) {
-        const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
-        float slot = -INFINITY;
-        if (flag >= 0) {
-            const float *gb = gt_box + 4 * (long long)(g0 + g);
-            const double b0 = gb[0], b1 = gb[1], b2 = gb[2], b3 = gb[3], area_b = (b2 - b0) * (b3 - b1);
-            double best = -INFINITY;
-            int bi = INT32_MAX;
-            for (int c = 0; c < nch; ++c) {
-                const int j = 64 * c + lane;
-                if (j < D && !((assigned >> c) & 1u) && ke_iou2d(box + 4 * j, b0, b1, b2, b3, area_b) > min_overlap) {
-                    const double sc = (double)det_score[d0 + j];
-                    if (sc > -10000000.0 && sc > best) { best = sc; bi = j; }
-                }
-            }
-            ke_argmax(best, bi);
-            if (bi != INT32_MAX) {
-                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
-                const bool ign_det = box[4 * bi + 3] - box[4 * bi + 1] < min_h;
-                if (flag == 0 && !ign_det) slot = det_score[d0 + bi];
-            }
-        }
-        if (lane == 0) out[g] = slot;
-    }
+    if (!active) return;                               // only behind the barrier: the idle waves of the last workgroup reach it too
+    const KeTask k{d0, D, g0, G, diff, eval_class, neighbor_class, det_score, gt_cls, gt_attr, min_overlap, (double)c_min_height[diff]};
+    KeBoxSource src{box, gt_box, g0};
+    ke_match_wave(src, k, lane, matched + (long long)diff * Gtot + g0);
 }
 
 __global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_2d_kernel(
@@ -426,74 +485,14 @@ __global__ __launch_bounds__(64 * KE_COUNT_WAVES) void kitti_count_2d_kernel(
         __syncthreads();
         box = s_box;
     }
-    const int nch = (D + 63) >> 6;
-    const double min_h = (double)c_min_height[diff];
-    uint32_t ign = 0u;
-    for (int c = 0; c < nch; ++c) {
-        const int j = 64 * c + lane;
-        if (j < D && box[4 * j + 3] - box[4 * j + 1] < min_h) ign |= 1u << c;
-    }
+    const KeTask k{d0, D, g0, G, diff, eval_class, neighbor_class, det_score, gt_cls, gt_attr, min_overlap, (double)c_min_height[diff]};
+    KeBoxCountSource src{{box, gt_box, g0}, gt_alpha, dc_box, det_cam, d0, k0, K, min_overlap};
+    const uint32_t ign = ke_chunk_mask(D, lane, [&](int j) { return src.ignored(j, k.min_h); });
     for (int ti = wave; ti < T; ti += KE_COUNT_WAVES) {
-        const float t = thresholds[diff * MV3D_KITTI_NUM_SAMPLE_PTS + ti];
-        uint32_t cand = 0u, assigned = 0u;
-        for (int c = 0; c < nch; ++c) {
-            const int j = 64 * c + lane;
-            if (j < D && !(det_score[d0 + j] < t)) cand |= 1u << c;
-        }
-        int tp = 0, fn = 0;
-        double s = 0.0;
-        for (int g = 0; g < G; ++g) {
-            const int flag = ke_gt_flag(gt_cls, gt_attr, g0 + g, diff, eval_class, neighbor_class);
-            if (flag < 0) continue;
-            const float *gb = gt_box + 4 * (long long)(g0 + g);
-            const double b0 = gb[0], b1 = gb[1], b2 = gb[2], b3 = gb[3], area_b = (b2 - b0) * (b3 - b1);
-            double best = -INFINITY;
-            int bi = INT32_MAX, first_ign = INT32_MAX;
-            for (int c = 0; c < nch; ++c) {
-                if (!(((cand & ~assigned) >> c) & 1u)) continue;
-                const int j = 64 * c + lane;
-                const double o = ke_iou2d(box + 4 * j, b0, b1, b2, b3, area_b);
-                if (!(o > min_overlap)) continue;
-                if ((ign >> c) & 1u) {
-                    if (first_ign == INT32_MAX) first_ign = j;
-                } else if (o > best) {
-                    best = o; bi = j;
-                }
-            }
-            ke_argmax(best, bi);
-            if (bi == INT32_MAX) bi = ke_min(first_ign);
-            if (bi == INT32_MAX) {
-                if (flag == 0) ++fn;
-            } else {
-                if (lane == (bi & 63)) assigned |= 1u << (bi >> 6);
-                if (flag == 0 && !(box[4 * bi + 3] - box[4 * bi + 1] < min_h)) {
-                    ++tp;
-                    s = s + (1.0 + cos((double)gt_alpha[g0 + g] - det_cam[8 * (long long)(d0 + bi) + 7])) / 2.0;
-                }
-            }
-        }
-        int fp = 0;
-        for (int c = 0; c < nch; ++c) {
-            const bool counted = (((cand & ~assigned & ~ign) >> c) & 1u) != 0u;
-            bool stuff = false;
-            if (counted) {                              // the devkit's DontCare ("stuff") rule
-                const double *a = box + 4 * (64 * c + lane);
-                const double area_a = (a[2] - a[0]) * (a[3] - a[1]);
-                for (int k = 0; k < K && !stuff; ++k) {
-                    const float *q = dc_box + 4 * (long long)(k0 + k);
-                    const double inter = ke_inter2d(a, q[0], q[1], q[2], q[3]);
-                    stuff = inter > 0.0 && inter / area_a > min_overlap;
-                }
-            }
-            fp += __popcll(__ballot(counted && !stuff));
-        }
-        if (lane == 0) {
-            int32_t *o = counts + 3 * (diff * MV3D_KITTI_NUM_SAMPLE_PTS + ti);
-            if (tp) atomicAdd(o, tp);
-            if (fp) atomicAdd(o + 1, fp);
-            if (fn) atomicAdd(o + 2, fn);
-            sim[(long long)task * MV3D_KITTI_NUM_SAMPLE_PTS + ti] = s;
-        }
+        const int slot = diff * MV3D_KITTI_NUM_SAMPLE_PTS + ti;
+        src.s = 0.0;
+        ke_count_wave(src, k, lane, ign, thresholds[slot], counts + 3 * slot);
+        if (lane == 0) sim[(long long)task * MV3D_KITTI_NUM_SAMPLE_PTS + ti] = src.s;
     }
 }
 

@@ -88,6 +88,19 @@ def get_thresholds(scores, n_gt):
     return np.array(t[:N_SAMPLE_PTS], np.float32)
 
 
+def threshold_tables(matched, n_gt):
+    """The host step between the passes: matched (..., 3, G) pass-1 slots and n_gt[di] counted objects per difficulty ->
+    (thr (..., 3, 41) f32, nthr (..., 3) int32), `get_thresholds` of the true-positive scores of every (metric, difficulty)."""
+    matched = np.asarray(matched)
+    thr = np.zeros(matched.shape[:-1] + (N_SAMPLE_PTS,), np.float32)
+    nthr = np.zeros(matched.shape[:-1], np.int32)
+    for idx in np.ndindex(*nthr.shape):
+        if n_gt[idx[-1]] > 0:
+            t = get_thresholds(matched[idx][matched[idx] > -np.inf], n_gt[idx[-1]])
+            thr[idx][:len(t)], nthr[idx] = t, len(t)
+    return thr, nthr
+
+
 def average_precision(counts, n_thresholds, recall_points=11):
     """counts (41, 3) tp | fp | fn of the first n_thresholds thresholds -> (AP in percent, precision (41), recall (41)).
     precision = tp / (tp + fp) (0 where nothing is counted), then the running maximum from the right; AP = mean of the
@@ -221,16 +234,9 @@ def evaluate(dets_cnr, gts, calibs, classes=('Car',), min_overlap=None, recall_p
             continue
         iou, height = ops.kitti_eval_overlaps(sp)
         matched = ops.kitti_eval_match(sp, iou, height, code, nb, mo[cls]).cpu().numpy()
-        thr = np.zeros((2, 3, N_SAMPLE_PTS), np.float32)
-        nthr = np.zeros((2, 3), np.int32)
         n_gt = [int((gt_flags(gt_cls, gt_attr[:, 0], gt_attr[:, 1], gt_attr[:, 2], gt_attr[:, 3], di, code, nb) == 0).sum())
                 for di in range(3)]
-        for mi in range(2):
-            for di in range(3):
-                v = matched[mi, di][matched[mi, di] > -np.inf]
-                t = get_thresholds(v, n_gt[di]) if n_gt[di] > 0 else np.zeros(0, np.float32)
-                thr[mi, di, :len(t)] = t
-                nthr[mi, di] = len(t)
+        thr, nthr = threshold_tables(matched, n_gt)
         d_thr, d_nthr = ops.upload_packed([thr, nthr], dev)
         counts = ops.kitti_eval_count(sp, iou, height, code, nb, mo[cls], d_thr, d_nthr).cpu().numpy()
         for mi, m in enumerate(METRICS):
@@ -249,14 +255,9 @@ def _evaluate_2d(res, metrics, cls, sp, im, code, nb, min_overlap, gt_cls, gt_at
     """The 2D passes of one class: AP_2D and / or AOS into `res`."""
     box, cam = ops.kitti_eval_image_boxes(sp, im)
     matched = ops.kitti_eval_match_2d(sp, im, box, code, nb, min_overlap).cpu().numpy()
-    thr = np.zeros((3, N_SAMPLE_PTS), np.float32)
-    nthr = np.zeros(3, np.int32)
-    for di in range(3):
-        n_gt = int((gt_flags(gt_cls, gt_attr[:, 0], gt_attr[:, 1], gt_attr[:, 2], gt_attr[:, 3], di, code, nb) == 0).sum())
-        v = matched[di][matched[di] > -np.inf]
-        t = get_thresholds(v, n_gt) if n_gt > 0 else np.zeros(0, np.float32)
-        thr[di, :len(t)] = t
-        nthr[di] = len(t)
+    n_gt = [int((gt_flags(gt_cls, gt_attr[:, 0], gt_attr[:, 1], gt_attr[:, 2], gt_attr[:, 3], di, code, nb) == 0).sum())
+            for di in range(3)]
+    thr, nthr = threshold_tables(matched, n_gt)
     d_thr, d_nthr = ops.upload_packed([thr, nthr], sp.device)
     counts, sim = ops.kitti_eval_count_2d(sp, im, box, cam, code, nb, min_overlap, d_thr, d_nthr)
     counts, sim = counts.cpu().numpy(), sim.cpu().numpy()

@@ -64,11 +64,7 @@ def bench_2d(a, metrics):
     box, cam = ops.kitti_eval_image_boxes(sp, im)
     m = ops.kitti_eval_match_2d(sp, im, box, 0, 1, 0.7).cpu().numpy()
     flags = [KE.gt_flags(np.concatenate([g['cls'] for g in gts]), attr[:, 0], attr[:, 1], attr[:, 2], attr[:, 3], d, 0, 1) for d in range(3)]
-    thr = np.zeros((3, 41), np.float32)
-    nthr = np.zeros(3, np.int32)
-    for di in range(3):
-        t = KE.get_thresholds(m[di][m[di] > -np.inf], int((flags[di] == 0).sum()))
-        thr[di, :len(t)], nthr[di] = t, len(t)
+    thr, nthr = KE.threshold_tables(m, [int((fl == 0).sum()) for fl in flags])
     d_thr, d_nthr = ops.upload_packed([thr, nthr], dev)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
     t_box, t_p1, t_p2 = [], [], []
@@ -119,12 +115,7 @@ def bench_3d(a):
         h0 = time.perf_counter()
         flags = [KE.gt_flags(np.concatenate([g['cls'] for g in gts]), attr[:, 0], attr[:, 1], attr[:, 2], attr[:, 3], d, 0, 1)
                  for d in range(3)]
-        thr = np.zeros((2, 3, 41), np.float32)
-        nthr = np.zeros((2, 3), np.int32)
-        for mi in range(2):
-            for di in range(3):
-                t = KE.get_thresholds(m[mi, di][m[mi, di] > -np.inf], int((flags[di] == 0).sum()))
-                thr[mi, di, :len(t)], nthr[mi, di] = t, len(t)
+        thr, nthr = KE.threshold_tables(m, [int((fl == 0).sum()) for fl in flags])
         t_host.append(time.perf_counter() - h0)
         d_thr, d_nthr = ops.upload_packed([thr, nthr], dev)
         ev[2].record()
