@@ -946,6 +946,31 @@ int mv3d_proposal_recall_3d_match(const mv3d_recall3d_split *split, const double
  * data with rows > 0, rows < 0, width < 1, channels < 1, or a row of 2^31 elements or more. */
 int mv3d_mirror_columns(float *data_dev, long long rows, int width, int channels, void *stream);
 
+/* ------------------------------------------------------------------ the deep-fusion join (csrc/fusion_join.hip)
+ * The element-wise mean that joins the views after a fully connected layer of the deep-fusion head (MV3D paper §3.3, Fig. 3c), with
+ * the layer's ReLU in front and the join's dropout behind, for `paths` networks at once (the main one and the auxiliary paths).
+ *   h      (sets_in, views, rows, channels) contiguous, the layer's pre-ReLU output; sets_in = 1 (every path reads the same h) or paths
+ *   out    (paths, rows, channels), g_out the same, g_h like h; all in `dtype`: 0 = f32, 1 = f16, 2 = bf16
+ *   keep   HOST bytes (paths, views), non-zero = path p reads view v; copied into the kernel's arguments by the call
+ *   drop   NULL, or DEVICE bytes (paths, rows, channels), non-zero = the element survives the dropout and is scaled by `scale`
+ * Forward, per element, in f32: a_v = x < 0 ? 0 : x (a NaN propagates); s = 0 + a_v over the kept views in ascending v; m = s / n_p
+ * (n_p = kept views of the path, a true division); with a mask m = drop ? m * scale : 0; the store rounds to nearest even and writes
+ * the type's canonical quiet NaN for a NaN.  A view no path keeps is never read.
+ * Backward, per element: t = g_out * (drop ? scale : 0) (g_out without a mask); g = (keep[p][v] && x > 0) ? t / n_p : 0; with
+ * sets_in == 1 the paths' g are added to 0 in ascending p by the one thread that owns (v, r, c).  No atomics, no workspace,
+ * bit-reproducible; views a path dropped get zeros.
+ * One launch each, no allocation, memset or synchronisation (capturable in a graph).  16-byte vector accesses when rows * channels is a
+ * multiple of the vector width (4 f32, 8 16-bit elements) and the buffers are 16-byte aligned (drop: 4 / 8 bytes).  Otherwise the
+ * WHOLE launch runs with scalar accesses -- there is no vector body with a scalar tail: the planes of h, out and the mask start at
+ * multiples of rows * channels, so with an odd product they are misaligned against each other and no element range is 16-byte aligned
+ * in all of them.  Expect several times less bandwidth there; the head's planes (channels = 2048) always vectorise.  Offsets are 64-bit.  rows == 0 launches nothing.  MV3D_ERR_INVALID_ARG before any HIP call: dtype outside 0..2, views
+ * outside 1..4, paths outside 1..8, sets_in not 1 or paths, rows < 0, channels < 1, rows * channels > 2^48, keep NULL, a path that
+ * keeps no view, or a NULL buffer (drop excepted) with rows > 0. */
+int mv3d_fusion_join_forward(const void *h_dev, int dtype, int sets_in, int paths, int views, int rows, int channels,
+                             const uint8_t *keep, const uint8_t *drop_dev, float scale, void *out_dev, void *stream);
+int mv3d_fusion_join_backward(const void *h_dev, const void *g_out_dev, int dtype, int sets_in, int paths, int views, int rows,
+                              int channels, const uint8_t *keep, const uint8_t *drop_dev, float scale, void *g_h_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,12 @@ cfg.TRAIN = _section(
     # (not in the reference) True: the MV3D paper's empty-anchor removal (section 3.2) -- anchors with fewer than
     # RPN_EMPTY_ANCHOR_MIN_CELLS occupied cells of the bird's-eye-view map under them (ops.anchor_occupancy) get no RPN label and are
     # no proposal candidates.  False = the reference, which runs every anchor.
-    RPN_SKIP_EMPTY_ANCHORS=False, RPN_EMPTY_ANCHOR_MIN_CELLS=1)
+    RPN_SKIP_EMPTY_ANCHORS=False, RPN_EMPTY_ANCHOR_MIN_CELLS=1,
+    # (not in the reference; cfg.FUSION = 'deep' only) the MV3D paper's training regularisers for the deep-fusion head (section 3.3):
+    # DROP_PATH draws global or local drop-path for the two joins of every training forward from the network's own generator
+    # (net.drop_path_rng, seeded with RNG_SEED); AUX_LOSSES adds one weight-sharing auxiliary path per view with its own
+    # classification and box loss (weight 1), removed at inference.
+    DROP_PATH=False, AUX_LOSSES=False)
 cfg.TEST = _section(
     NMS=0.5, HAS_RPN=True, RPN_NMS_THRESH=0.7, RPN_PRE_NMS_TOP_N=12000, RPN_POST_NMS_TOP_N=2000, RPN_MIN_SIZE=5,
     DEBUG_TIMELINE=False,
@@ -70,6 +75,10 @@ cfg.TEST = _section(
     # (frame by frame, batched and in the captured ServeGraph step) ranks only the anchors over occupied cells
     RPN_SKIP_EMPTY_ANCHORS=False, RPN_EMPTY_ANCHOR_MIN_CELLS=1)
 cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
+# (not in the reference) how the views meet in the second stage: 'early' = the reference's head (every view runs fc6 -> fc7 alone, the
+# towers are concatenated in front of cls_score / bbox_pred); 'deep' = the MV3D paper's deep fusion (the views' activations are joined
+# by an element-wise mean after every layer, networks/mv3d.py)
+cfg.FUSION = 'early'
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
 cfg.EXP_DIR = 'default'

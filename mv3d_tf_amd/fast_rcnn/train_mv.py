@@ -79,27 +79,41 @@ def rcnn_losses(cls_score, roi_data_3d, bbox_pred, sigma=3.0):
 def total_loss(net_layers, sigma=3.0):
     """train_mv.py:130: cross_entropy + loss_box + rpn_cross_entropy + rpn_loss_box from the train graph's layers.  For a batch
     of B frames every loss is the mean over the frames of the reference's per-frame loss (what B single-frame steps with
-    averaged gradients give, and what the data-parallel all-reduce averages across ranks)."""
+    averaged gradients give, and what the data-parallel all-reduce averages across ranks).  Under deep fusion with
+    cfg.TRAIN.AUX_LOSSES the layers hold one auxiliary path per view (`cls_score_aux`, `bbox_pred_aux`): the total gains every path's
+    two ROI losses with weight 1, the returned 4-tuple stays the main terms, and net_layers['loss_aux'] (V, 2) holds the auxiliary ones."""
     L = net_layers
     rpn_data = L['rpn_data']
+    data = L['roi_data_3d']
+    aux = L.get('cls_score_aux')                                # deep fusion with cfg.TRAIN.AUX_LOSSES: (V, R, 2) / (V, R, 48)
+
+    def aux_terms(slices):
+        """every auxiliary path's (cross_entropy, loss_box), weight 1 each, through the same loss kernel: the mean over the frames,
+        kept as net_layers['loss_aux'] (V, 2); returns their sum"""
+        vals = [t for sl in slices for v in range(aux.shape[0])
+                for t in rcnn_losses(aux[v][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred_aux'][v][sl], sigma)]
+        L['loss_aux'] = torch.stack(vals).view(len(slices), aux.shape[0], 2).mean(0)
+        return L['loss_aux'].sum()
+
     if rpn_data[0].dim() == 1:                                  # one frame: the reference's shapes
         rpn_ce, rpn_box = rpn_losses(L['rpn_cls_score_reshape'], rpn_data, L['rpn_bbox_pred'], sigma)
-        ce, box = rcnn_losses(L['cls_score'], L['roi_data_3d'], L['bbox_pred'], sigma)
-        return ce + box + rpn_ce + rpn_box, (ce, box, rpn_ce, rpn_box)
+        ce, box = rcnn_losses(L['cls_score'], data, L['bbox_pred'], sigma)
+        total = ce + box + rpn_ce + rpn_box
+        return (total if aux is None else total + aux_terms([slice(None)])), (ce, box, rpn_ce, rpn_box)
     B = rpn_data[0].shape[0]
     rows = L['roi_rows']
-    vals = []
+    vals, slices = [], []
     o = 0
     for b in range(B):
         r_ce, r_box = rpn_losses(L['rpn_cls_score_reshape'][b], (rpn_data[0][b], rpn_data[1][b]), L['rpn_bbox_pred'][b], sigma)
         sl = slice(o, o + rows[b])
+        slices.append(sl)
         o += rows[b]
-        data = L['roi_data_3d']
         ce, box = rcnn_losses(L['cls_score'][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred'][sl], sigma)
         vals += [ce, box, r_ce, r_box]
     # the frames' means with ONE stack + ONE reduction (4 B scalars added and divided one by one were 4 B + 4 B launches each way)
     parts = torch.stack(vals).view(B, 4).mean(0)
-    return parts.sum(), tuple(parts.unbind(0))
+    return (parts.sum() if aux is None else parts.sum() + aux_terms(slices)), tuple(parts.unbind(0))
 
 
 def stack_blobs(frames):
@@ -141,6 +155,17 @@ def group_frames_by_shape(frames):
     return groups
 
 
+def rng_state_plain(rng):
+    """a numpy RandomState's state as plain Python values (what torch.save / torch.load carry without pickling numpy arrays)"""
+    name, keys, pos, has_gauss, cached = rng.get_state()
+    return [str(name), [int(k) for k in keys], int(pos), int(has_gauss), float(cached)]
+
+
+def rng_set_state_plain(rng, plain):
+    name, keys, pos, has_gauss, cached = plain
+    rng.set_state((name, np.asarray(keys, np.uint32), int(pos), int(has_gauss), float(cached)))
+
+
 def snapshot_filename(output_dir, iter):
     """train_mv.py:56-61: <output_dir>/<SNAPSHOT_PREFIX>[_<SNAPSHOT_INFIX>]_iter_<iter+1>.ckpt"""
     infix = ('_' + cfg.TRAIN.SNAPSHOT_INFIX if cfg.TRAIN.SNAPSHOT_INFIX != '' else '')
@@ -176,7 +201,9 @@ class SolverWrapper(object):
 
     def snapshot(self, sess, iter):
         """<output_dir>/<SNAPSHOT_PREFIX>[_<INFIX>]_iter_<iter+1>.ckpt (:49-65).  The file holds the `.npy` weight dict
-        that `network.load` reads; the optimiser state goes next to it (<name>.optim.pt) so that training can resume."""
+        that `network.load` reads; the optimiser state goes next to it (<name>.optim.pt) so that training can resume -- with it the
+        state of the network's drop-path generator (net.drop_path_rng, cfg.TRAIN.DROP_PATH), so a resumed run continues the draw
+        stream instead of replaying it from the seed."""
         if not os.path.exists(self.output_dir):
             os.makedirs(self.output_dir)
         filename = snapshot_filename(self.output_dir, iter)
@@ -184,7 +211,10 @@ class SolverWrapper(object):
             np.save(f, {name: {'weights': _tf_layout(w), 'biases': b.detach().cpu().numpy()}
                         for name, (w, b) in self.net.params.items()}, allow_pickle=True)
         if self.optimizer is not None:
-            torch.save({'iter': iter + 1, 'optimizer': self.optimizer.state_dict()}, filename + '.optim.pt')
+            state = {'iter': iter + 1, 'optimizer': self.optimizer.state_dict()}
+            if getattr(self.net, "drop_path_rng", None) is not None:
+                state['drop_path_rng'] = rng_state_plain(self.net.drop_path_rng)
+            torch.save(state, filename + '.optim.pt')
         self.log('Wrote snapshot to: {:s}'.format(filename))
         return filename
 
@@ -226,6 +256,8 @@ class SolverWrapper(object):
                 state = torch.load(resume + '.optim.pt', map_location=params[0].device)
                 self.optimizer.load_state_dict(state['optimizer'])
                 start_iter = int(state['iter'])
+                if 'drop_path_rng' in state and getattr(self.net, "drop_path_rng", None) is not None:
+                    rng_set_state_plain(self.net.drop_path_rng, state['drop_path_rng'])
             self.log('Resumed from {:s} at iteration {:d}'.format(resume, start_iter))
         bucketer = sharding.GradBucketer(params, dist)
         history, last_snapshot_iter, spent = [], -1, 0.0

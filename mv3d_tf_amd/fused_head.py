@@ -12,7 +12,9 @@ issued back to back with no graph nodes in between:
   * backward: the same GEMMs transposed, one masked elementwise per layer; the weight-gradient GEMMs write f32 directly where the
     installed torch offers `out_dtype` (else their results are cast).
 The GEMMs themselves are the vendor library's (a dense contraction: hipBLASLt behind torch.baddbmm / addmm); the results equal the
-op-by-op graph up to GEMM batching (tests/test_train_entry.py::test_fused_head_equals_the_op_by_op_head)."""
+op-by-op graph up to GEMM batching (tests/test_train_entry.py::test_fused_head_equals_the_op_by_op_head).
+DeepFusedHead is the same structure for the MV3D paper's deep fusion (cfg.FUSION = 'deep'): the views meet in an element-wise mean
+after fc6 and after fc7 (ops.fusion_join, one launch each way), for the main network and the auxiliary paths at once."""
 import torch
 
 _F32_OUT = [None]         # does this torch take bmm / mm(..., out_dtype=torch.float32) on the device?  (probed once)
@@ -127,16 +129,132 @@ class FusedHead(torch.autograd.Function):
         return (None, None, None, None) + tuple(gpools) + tuple(grads)
 
 
-def head_buffers(params, names6, names7, dt, device):
+class DeepFusedHead(torch.autograd.Function):
+    """The deep-fusion head (MV3D paper section 3.3, Fig. 3c) as one autograd function beside FusedHead, for
+    P paths at once (path 0 the main network, then the auxiliary paths):
+        fc6_v(pool_v) per view (the batched GEMM of FusedHead) -> join 1 (ops.fusion_join, sets_in = 1: every path reads the same fc6)
+        -> fc7_v(join 1 of path p) for every (p, v): ONE GEMM batched over the views on the paths' rows stacked to (P R, 2048)
+        -> join 2 (sets_in = P) -> cls_score / bbox_pred as ONE GEMM on (P R, 2048).
+    apply(keep_prob, gemm_dtype, n_views, held, keep1, keep2, masks, *tensors): keep1 / keep2 (P, V) host 0 / 1 tables of the two joins,
+    masks None (no dropout) or the joins' dropout masks (M1, M2), uint8 (P, R, 2048) on the device, whose survivors are scaled by
+    1 / keep_prob (deep_fused_head below draws them); tensors as for FusedHead, with w_cls (nc, 2048) and w_box (nb, 2048).  Returns
+    (cls_score f32 (P, R, nc), bbox_pred f32 (P, R, nb), join 1 and join 2 (P, R, 2048) in gemm_dtype, not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, keep_prob, dt, V, held, keep1, keep2, masks, *ts):
+        from . import ops
+        pools, wts = ts[:V], ts[V:]
+        R = pools[0].shape[0]
+        dev = pools[0].device
+        K = pools[0][0].numel()
+        w6 = [wts[4 * v] for v in range(V)]; b6 = [wts[4 * v + 1] for v in range(V)]
+        w7 = [wts[4 * v + 2] for v in range(V)]; b7 = [wts[4 * v + 3] for v in range(V)]
+        wc, bc, wb, bb = wts[4 * V:4 * V + 4]
+        N6, N7 = w6[0].shape[0], w7[0].shape[0]
+        nc, nb = wc.shape[0], wb.shape[0]
+        P = len(keep1)
+        if held is not None:
+            (W6, B6, W7, B7, WH, BH), current = held
+        else:
+            W6 = torch.empty((V, N6, K), dtype=dt, device=dev); B6 = torch.empty((V, 1, N6), dtype=dt, device=dev)
+            W7 = torch.empty((V, N7, N6), dtype=dt, device=dev); B7 = torch.empty((V, 1, N7), dtype=dt, device=dev)
+            WH = torch.empty((nc + nb, N7), dtype=dt, device=dev); BH = torch.empty((nc + nb,), dtype=dt, device=dev)
+            current = False
+        if not current:
+            dst = [W6[v] for v in range(V)] + [B6[v, 0] for v in range(V)] + [W7[v] for v in range(V)] + [B7[v, 0] for v in range(V)] + [WH[:nc], WH[nc:], BH[:nc], BH[nc:]]
+            src = [t.detach() for t in (w6 + b6 + w7 + b7 + [wc, wb, bc, bb])]
+            torch._foreach_copy_(dst, src)
+        X = torch.empty((V, R, K), dtype=dt, device=dev)
+        for v in range(V):
+            p = pools[v]
+            X[v].view(R, p.shape[3], p.shape[1], p.shape[2]).copy_(p.detach().permute(0, 3, 1, 2))
+        scale = 1.0 / keep_prob
+        M1, M2 = masks if masks is not None else (None, None)
+        H6 = torch.baddbmm(B6, X, W6.transpose(1, 2)).view(1, V, R, N6)            # pre-ReLU, bias through beta
+        J1 = ops.fusion_join(H6, keep1, M1, scale)                                 # (P, R, N6)
+        # fc7 of every (path, view): the paths' rows are one (P R, N6) matrix every view's weights multiply -> (V, P R, N7); the join
+        # reads (P, V, R, N7) (a view for P = 1, one small copy otherwise)
+        H7v = torch.baddbmm(B7, J1.view(1, P * R, N6).expand(V, P * R, N6), W7.transpose(1, 2))
+        H7 = H7v.view(V, P, R, N7).permute(1, 0, 2, 3).contiguous()
+        J2 = ops.fusion_join(H7, keep2, M2, scale)                                 # (P, R, N7)
+        out = torch.addmm(BH, J2.view(P * R, N7), WH.t()).float()
+        ctx.save_for_backward(X, W6, W7, WH, H6, H7, J1, J2, M1, M2)
+        ctx.meta = (scale, dt, V, P, R, K, N6, N7, nc, nb, [tuple(p.shape) for p in pools], [t.requires_grad for t in ts],
+                    [list(map(int, k)) for k in keep1], [list(map(int, k)) for k in keep2])
+        ctx.mark_non_differentiable(J1, J2)
+        return out[:, :nc].reshape(P, R, nc), out[:, nc:].reshape(P, R, nb), J1, J2
+
+    @staticmethod
+    def backward(ctx, g_cls, g_box, _g1, _g2):
+        from . import ops
+        X, W6, W7, WH, H6, H7, J1, J2, M1, M2 = ctx.saved_tensors
+        scale, dt, V, P, R, K, N6, N7, nc, nb, pshapes, needs, keep1, keep2 = ctx.meta
+        dev = X.device
+        gout = torch.empty((P * R, nc + nb), dtype=dt, device=dev)
+        if g_cls is not None:
+            gout[:, :nc].copy_(g_cls.reshape(P * R, nc))
+        else:
+            gout[:, :nc].zero_()
+        if g_box is not None:
+            gout[:, nc:].copy_(g_box.reshape(P * R, nb))
+        else:
+            gout[:, nc:].zero_()
+        gWH = _mm_f32(gout.t(), J2.view(P * R, N7), False)                         # (nc + nb, N7), f32
+        gBH = gout.float().sum(0)
+        gJ2 = gout.mm(WH).view(P, R, N7)
+        gH7 = ops.fusion_join_backward(H7, gJ2, keep2, M2, scale)                  # (P, V, R, N7): zeros where a path dropped a view
+        # with the views side by side, (P R, V N7), fc7's backward is plain GEMMs: the paths meet in the weight gradient's K = P R,
+        # the views in the data gradient's K = V N7 (f32 accumulation inside the GEMM both times)
+        G7 = gH7.permute(0, 2, 1, 3).reshape(P * R, V * N7)
+        gW7 = _mm_f32(G7.t(), J1.view(P * R, N6), False).view(V, N7, N6)           # f32
+        gB7 = G7.float().sum(0).view(V, N7)
+        gJ1 = G7.mm(W7.view(V * N7, N6)).view(P, R, N6)
+        gH6 = ops.fusion_join_backward(H6, gJ1, keep1, M1, scale).view(V, R, N6)   # the paths added in ascending order in the kernel
+        gW6 = _mm_f32(gH6.transpose(1, 2), X, True)                                # (V, N6, K), f32
+        gB6 = gH6.float().sum(1)
+        gpools = [None] * V
+        if any(needs[:V]):
+            gX = torch.bmm(gH6, W6)                                                # (V, R, K)
+            for v in range(V):
+                if needs[v]:
+                    R_, h, w, c = pshapes[v]
+                    gp = torch.empty(pshapes[v], dtype=torch.float32, device=dev)
+                    gp.permute(0, 3, 1, 2).copy_(gX[v].view(R_, c, h, w))
+                    gpools[v] = gp
+        grads = []
+        for v in range(V):
+            grads += [gW6[v], gB6[v], gW7[v], gB7[v]]
+        grads += [gWH[:nc], gBH[:nc].contiguous(), gWH[nc:], gBH[nc:].contiguous()]
+        return (None,) * 7 + tuple(gpools) + tuple(grads)
+
+
+def deep_fused_head(pools, params, names6, names7, keep_prob, gemm_dtype, keep1, keep2, held=None, masks=None):
+    """pools, params, names6 / names7, held as for fused_head; keep1 / keep2: the (P, V) keep tables of join 1 / join 2 (row 0 the
+    main network, further rows auxiliary paths); masks: None = with keep_prob < 1 one dropout mask per join, on the joined vector,
+    is drawn here by torch on the device, or the (M1, M2) to use.  Returns (cls_score (P, R, nc), bbox_pred (P, R, nb), join 1,
+    join 2, the masks used (None without dropout))."""
+    V = len(pools)
+    if masks is None and keep_prob < 1.0:
+        P, R, dev = len(keep1), pools[0].shape[0], pools[0].device
+        masks = tuple((torch.rand((P, R, params[n[0]][0].shape[0]), device=dev) < keep_prob).to(torch.uint8) for n in (names6, names7))
+    ts = list(pools)
+    for n6, n7 in zip(names6, names7):
+        ts += [params[n6][0], params[n6][1], params[n7][0], params[n7][1]]
+    ts += [params["cls_score"][0], params["cls_score"][1], params["bbox_pred"][0], params["bbox_pred"][1]]
+    return DeepFusedHead.apply(float(keep_prob), gemm_dtype, V, held, keep1, keep2, masks, *ts) + (masks,)
+
+
+def head_buffers(params, names6, names7, dt, device, fusion="early"):
     """the stacked 16-bit weight buffers of the fused head for a network to keep, and which piece of them holds which master parameter:
-    ((W6, B6, W7, B7, WH, BH), [(param, view of its copy), ...])"""
+    ((W6, B6, W7, B7, WH, BH), [(param, view of its copy), ...]).  fusion = 'deep': cls_score / bbox_pred read the 2048-wide join, so
+    their buffer is (50, 2048) instead of (50, views * 2048)."""
     V = len(names6)
     N6, K = params[names6[0]][0].shape
     N7 = params[names7[0]][0].shape[0]
     nc, nb = params["cls_score"][0].shape[0], params["bbox_pred"][0].shape[0]
     W6 = torch.empty((V, N6, K), dtype=dt, device=device); B6 = torch.empty((V, 1, N6), dtype=dt, device=device)
     W7 = torch.empty((V, N7, N6), dtype=dt, device=device); B7 = torch.empty((V, 1, N7), dtype=dt, device=device)
-    WH = torch.empty((nc + nb, V * N7), dtype=dt, device=device); BH = torch.empty((nc + nb,), dtype=dt, device=device)
+    WH = torch.empty((nc + nb, N7 if fusion == "deep" else V * N7), dtype=dt, device=device); BH = torch.empty((nc + nb,), dtype=dt, device=device)
     pieces = []
     for v, (n6, n7) in enumerate(zip(names6, names7)):
         pieces += [(params[n6][0], W6[v]), (params[n6][1], B6[v, 0]), (params[n7][0], W7[v]), (params[n7][1], B7[v, 0])]

@@ -2,9 +2,10 @@
 from .mv3d import MV3D
 
 
-def get_network(name):
+def get_network(name, fusion=None):
     """'MV3D_train' / 'MV3D_test' (the legacy VGGnet_* 2-D Faster-RCNN graphs are out of scope); 'MV3D_train_3view' /
-    'MV3D_test_3view' add the front-view tower the reference leaves a TODO (networks/mv3d.py)."""
+    'MV3D_test_3view' add the front-view tower the reference leaves a TODO (networks/mv3d.py).  fusion: 'early' | 'deep', None =
+    cfg.FUSION."""
     parts = name.split('_')
     if parts[0] != 'MV3D' or len(parts) < 2:
         raise KeyError('Unknown dataset: {}'.format(name))
@@ -12,9 +13,9 @@ def get_network(name):
     if parts[2:] not in ([], ['3view']):
         raise KeyError('Unknown dataset: {}'.format(name))
     if parts[1] == 'test':
-        return MV3D(phase="TEST", views=views)
+        return MV3D(phase="TEST", views=views, fusion=fusion)
     if parts[1] == 'train':
-        return MV3D(phase="TRAIN", views=views)
+        return MV3D(phase="TRAIN", views=views, fusion=fusion)
     raise KeyError('Unknown dataset: {}'.format(name))
 
 

@@ -41,16 +41,40 @@ _INPUTS = ("lidar_bv_data", "image_data", "lidar_fv_data", "im_info", "calib", "
            "gt_boxes_corners")
 
 
+def draw_drop_path(rng, views):
+    """One training forward's drop-path draw for the main network (MV3D paper section 3.3): (2, views) uint8, row j the views join
+    j + 1 keeps.  u = random_sample(); u < 0.5: global drop-path, ONE view v* = randint(views) kept at both joins; otherwise local
+    drop-path, join 1 then join 2: keep = random_sample(views) >= 0.5, and keep[randint(views)] = 1 if that kept nothing."""
+    keep = np.zeros((2, views), np.uint8)
+    if rng.random_sample() < 0.5:
+        keep[:, rng.randint(views)] = 1
+        return keep
+    for j in range(2):
+        k = rng.random_sample(views) >= 0.5
+        if not k.any():
+            k[rng.randint(views)] = True
+        keep[j] = k
+    return keep
+
+
 class MV3D:
     """One class for both graphs; `phase` is 'TEST' (MV3D_test) or 'TRAIN' (MV3D_train)."""
 
-    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2):
+    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2, fusion=None):
         """views = 2: the reference's graphs (BEV + RGB towers).  views = 3 adds the front view the MV3D paper has and the
         reference leaves a TODO (`proposal_transform`, network.py:293-315): a third VGG16 trunk on `lidar_fv_data`
         (1, 64, 512, 3), `rois_fv` = mv3d_rois_3d_to_fv(rois_3d), a third RoiPool `pool_5_3` and tower fc6_3 / fc7_3, the
-        three towers concatenated (6144 -> cls_score / bbox_pred).  Parity unpinned by construction."""
+        three towers concatenated (6144 -> cls_score / bbox_pred).  Parity unpinned by construction.
+        fusion = 'early' (the reference's head) | 'deep' (the paper's deep fusion: the views are joined by an element-wise mean after
+        fc6 and after fc7, cls_score / bbox_pred read the 2048-wide join); None = cfg.FUSION."""
         self.phase = phase
         self.views = int(views)
+        self.fusion = cfg.FUSION if fusion is None else fusion
+        if self.fusion not in ("early", "deep"):
+            raise ValueError("fusion must be 'early' or 'deep', got %r" % (self.fusion,))
+        # drop-path draws of the deep head (cfg.TRAIN.DROP_PATH): the network's own generator, never numpy's global one (the
+        # target layers' draw stream is the reference's); the same seed on every rank
+        self.drop_path_rng = np.random.RandomState(cfg.RNG_SEED)
         self.trainable = trainable
         self.device = torch.device(device or ("cuda:%d" % cfg.GPU_ID))
         self.layers = {}
@@ -92,8 +116,9 @@ class MV3D:
         for t in towers:
             var("fc6" + t, (2048, 7 * 7 * 512), 0.01)
             var("fc7" + t, (2048, 2048), 0.01)
-        var("cls_score", (n_classes, 2048 * len(towers)), 0.01)
-        var("bbox_pred", (n_classes * 24, 2048 * len(towers)), 0.001)   # network.py:382-384
+        width = 2048 if self.fusion == "deep" else 2048 * len(towers)   # deep: the joined vector; early: the concatenated towers
+        var("cls_score", (n_classes, width), 0.01)
+        var("bbox_pred", (n_classes * 24, width), 0.001)                # network.py:382-384
 
     # ---- lib/networks/network.py plumbing
     def get_output(self, layer):
@@ -210,6 +235,13 @@ class MV3D:
         """The fusion head (MV3D_train.py:108-136 / MV3D_test.py:95-123) on the pooled maps: per view fc6 -> (dropout) -> fc7 ->
         (dropout), concatenated, cls_score (+ softmax) and bbox_pred.  P(name) -> (w, b) | None (= this network's own).  Returns
         ([fc7 per view], cls_score f32, cls_prob, bbox_pred f32)."""
+        if self.fusion == "deep":
+            ones = np.ones((1, len(pools)), np.uint8)
+            joins, cls, box = self._deep_head_fn(pools, P, keep_prob, ones, ones)
+            cls, box = cls[0], box[0]
+            self.layers["fc6_join"], self.layers["fc7_join"] = joins[0][0], joins[1][0]
+            prob = ops.softmax_rows(cls) if not (torch.is_grad_enabled() and cls.requires_grad) else F.softmax(cls, dim=1)
+            return [], cls, prob, box
         tower = []
         for t, x in zip(("_1", "_2", "_3"), pools):
             x = self._fc(x, "fc6" + t, wb=P("fc6" + t))
@@ -223,6 +255,50 @@ class MV3D:
         cls = self._fc(fused, "cls_score", relu=False, wb=P("cls_score")).float()
         prob = ops.softmax_rows(cls) if (cls.is_cuda and not (torch.is_grad_enabled() and cls.requires_grad)) else F.softmax(cls, dim=1)
         return tower, cls, prob, self._fc(fused, "bbox_pred", relu=False, wb=P("bbox_pred")).float()
+
+    def _deep_head_fn(self, pools, P, keep_prob, keep1, keep2):
+        """The deep-fusion head op by op (the fixed-ROI serving step, and TRAIN without fused_head): fc6_v per view, join 1
+        (ops.FusionJoin: ReLU, mean over the kept views, dropout on the mean), fc7_v of the join for every path and view, join 2,
+        cls_score / bbox_pred on the 2048-wide join.  keep1 / keep2 (paths, views) 0 / 1.  Returns ((join 1, join 2) (paths, R, 2048),
+        cls_score f32 (paths, R, 2), bbox_pred f32 (paths, R, 48)).  Device tensors only: the join has no torch path."""
+        sfx = ("_1", "_2", "_3")[:len(pools)]
+        NP, R = len(keep1), pools[0].shape[0]
+        train = self.phase == "TRAIN" and keep_prob < 1.0
+        scale = 1.0 / keep_prob if train else 1.0
+        mask = lambda n: (torch.rand((NP, R, n), device=pools[0].device) < keep_prob).to(torch.uint8) if train else None
+        if not torch.is_grad_enabled() and all(P(n + t) is None for n in ("fc6", "fc7") for t in sfx):
+            # serving: every GEMM writes its (R, 2048) plane of the buffer the join reads -- no stacking copy in front of a join
+            def fc_into(out, x, name):
+                w, b = self._serving_weights(name, tuple(x.shape[1:]) if x.ndim == 4 else None)
+                torch.addmm(b, x.reshape(x.shape[0], -1).to(w.dtype), w.t(), out=out)
+
+            dt, N = self.amp_dtype or torch.float32, self.params["fc6" + sfx[0]][0].shape[0]
+            h6 = torch.empty((1, len(sfx), R, N), dtype=dt, device=pools[0].device)
+            for v, (t, x) in enumerate(zip(sfx, pools)):
+                fc_into(h6[0, v], x, "fc6" + t)
+            j1 = ops.fusion_join(h6, keep1, mask(N), scale)
+            h7 = torch.empty((NP, len(sfx), R, N), dtype=dt, device=pools[0].device)
+            for p in range(NP):
+                for v, t in enumerate(sfx):
+                    fc_into(h7[p, v], j1[p], "fc7" + t)
+            j2 = ops.fusion_join(h7, keep2, mask(N), scale)
+        else:
+            h6 = torch.stack([self._fc(x, "fc6" + t, relu=False, wb=P("fc6" + t)) for t, x in zip(sfx, pools)]).unsqueeze(0)
+            j1 = ops.FusionJoin.apply(h6, keep1, mask(h6.shape[-1]), scale)
+            h7 = torch.stack([torch.stack([self._fc(j1[p], "fc7" + t, relu=False, wb=P("fc7" + t)) for t in sfx]) for p in range(NP)])
+            j2 = ops.FusionJoin.apply(h7, keep2, mask(h7.shape[-1]), scale)
+        flat = j2.reshape(NP * R, -1)
+        cls = self._fc(flat, "cls_score", relu=False, wb=P("cls_score")).float().view(NP, R, -1)
+        box = self._fc(flat, "bbox_pred", relu=False, wb=P("bbox_pred")).float().view(NP, R, -1)
+        return (j1, j2), cls, box
+
+    def _fusion_keep(self):
+        """the (2, paths, views) keep tables of a training forward of the deep head: row 0 the main network (all views, or the step's
+        drop-path draw), then one row e_v per auxiliary path under cfg.TRAIN.AUX_LOSSES"""
+        V = self.views
+        main = draw_drop_path(self.drop_path_rng, V) if cfg.TRAIN.get("DROP_PATH", False) else np.ones((2, V), np.uint8)
+        rows = [main] + ([np.stack([e, e]) for e in np.eye(V, dtype=np.uint8)] if cfg.TRAIN.get("AUX_LOSSES", False) else [])
+        return np.ascontiguousarray(np.stack(rows, 1))
 
     _HEAD_LAYERS = ("rpn_cls_score", "rpn_bbox_pred", "fc6_1", "fc7_1", "fc6_2", "fc7_2", "fc6_3", "fc7_3", "cls_score", "bbox_pred")
 
@@ -281,7 +357,8 @@ class MV3D:
         h = self.__dict__.get("_head_lowp")
         if h is None or h["dtype"] != self.amp_dtype or h["sfx"] != sfx:
             from ..fused_head import head_buffers
-            bufs, pieces = head_buffers(self.params, ["fc6" + t for t in sfx], ["fc7" + t for t in sfx], self.amp_dtype, self.device)
+            bufs, pieces = head_buffers(self.params, ["fc6" + t for t in sfx], ["fc7" + t for t in sfx], self.amp_dtype, self.device,
+                                        fusion=self.fusion)
             h = self.__dict__["_head_lowp"] = {"dtype": self.amp_dtype, "sfx": sfx, "bufs": bufs, "pieces": pieces, "stamp": {}}
             opt = self.__dict__.get("_lowp_opt")
             if opt is not None:
@@ -485,7 +562,23 @@ class MV3D:
         # (serving in 16-bit mode: the pooled maps in the head's type straight from the pooling launch -- no f32 copy, no cast launch)
         for name, top in zip(names, roi_pool_views([(d.contiguous(), r.contiguous()) for d, r in views], 7, 7, 1.0 / 8, top_dtype=self.amp_dtype)):
             L[name] = top
-        if self.fused_head and self.phase == "TRAIN" and torch.is_grad_enabled():
+        if self.fusion == "deep" and self.phase == "TRAIN":
+            # deep fusion: P = 1 path, or 1 + views with the auxiliary paths; the step's keep tables are recorded
+            sfx = ("_1", "_2", "_3")[:len(names)]
+            keep = L["fusion_keep"] = self._fusion_keep()
+            if self.fused_head and torch.is_grad_enabled():
+                from ..fused_head import deep_fused_head
+                cls, box, j1, j2, _ = deep_fused_head([L[n] for n in names], self.params, ["fc6" + t for t in sfx], ["fc7" + t for t in sfx],
+                                                   keep_prob, self.amp_dtype or torch.float32, keep[0], keep[1], held=self._held_head(sfx))
+            else:
+                (j1, j2), cls, box = self._deep_head_fn([L[n] for n in names], lambda n: None, keep_prob, keep[0], keep[1])
+            L["cls_score"], L["bbox_pred"] = cls[0], box[0]
+            if keep.shape[1] > 1:
+                L["cls_score_aux"], L["bbox_pred_aux"] = cls[1:], box[1:]
+            L["fc6_join"], L["fc7_join"] = j1[0], j2[0]
+            L["cls_prob"] = ops.softmax_rows(L["cls_score"])
+            tower = []
+        elif self.fused_head and self.phase == "TRAIN" and torch.is_grad_enabled():
             # the head as ONE autograd function (mv3d_tf_amd/fused_head.py): batched GEMMs over the views, no per-op graph nodes
             from ..fused_head import fused_head
             sfx = ("_1", "_2", "_3")[:len(names)]

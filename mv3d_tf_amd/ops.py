@@ -654,6 +654,71 @@ def mirror_columns(t):
     return t
 
 
+# ------------------------------------------------------------------ the deep-fusion join
+_FJ_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+
+
+def _fusion_join_args(h, keep, drop, what):
+    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype not in _FJ_DTYPES:
+        raise TypeError("%s: a CUDA float32 / float16 / bfloat16 tensor is required, got %s"
+                        % (what, "%s on %s" % (h.dtype, h.device) if isinstance(h, torch.Tensor) else type(h).__name__))
+    if h.dim() != 4 or not h.is_contiguous():
+        raise ValueError("%s: h must be a contiguous (sets_in, views, rows, channels) tensor, got shape %s strides %s"
+                         % (what, tuple(h.shape), tuple(h.stride())))
+    S, V, R, Cn = (int(n) for n in h.shape)
+    k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+    if k.ndim != 2 or k.shape[1] != V:
+        raise ValueError("%s: keep must be (paths, %d views), got shape %s" % (what, V, k.shape))
+    P = int(k.shape[0])
+    if drop is not None:
+        if not isinstance(drop, torch.Tensor) or drop.device != h.device or drop.dtype != torch.uint8 or not drop.is_contiguous() \
+                or tuple(drop.shape) != (P, R, Cn):
+            raise ValueError("%s: drop must be a contiguous uint8 tensor of shape %s on %s" % (what, (P, R, Cn), h.device))
+    return S, P, V, R, Cn, k
+
+
+def fusion_join(h, keep, drop=None, scale=1.0):
+    """The deep-fusion join, forward (mv3d_fusion_join_forward): h (sets_in, views, rows, channels) pre-ReLU, keep (paths, views)
+    host 0 / 1, drop None or (paths, rows, channels) uint8 on the device -> (paths, rows, channels) in h's type: the mean over each
+    path's kept views of relu(h), dropout applied to the mean.  Device tensors only; there is no torch path."""
+    S, P, V, R, Cn, k = _fusion_join_args(h, keep, drop, "fusion_join")
+    out = torch.empty((P, R, Cn), dtype=h.dtype, device=h.device)
+    with torch.cuda.device(h.device):
+        check(lib().mv3d_fusion_join_forward(_ptr(h), _FJ_DTYPES[h.dtype], S, P, V, R, Cn, k.ctypes.data_as(C.c_void_p), _ptr(drop),
+                                             C.c_float(scale), _ptr(out), _stream()), "mv3d_fusion_join_forward")
+    return out
+
+
+def fusion_join_backward(h, g_out, keep, drop=None, scale=1.0):
+    """The join's gradient (mv3d_fusion_join_backward): g_out (paths, rows, channels) in h's type -> g_h of h's shape and type;
+    with sets_in == 1 the paths' contributions are added in ascending path order.  Views a path dropped get zeros."""
+    S, P, V, R, Cn, k = _fusion_join_args(h, keep, drop, "fusion_join_backward")
+    if not isinstance(g_out, torch.Tensor) or g_out.device != h.device or g_out.dtype != h.dtype or not g_out.is_contiguous() \
+            or tuple(g_out.shape) != (P, R, Cn):
+        raise ValueError("fusion_join_backward: g_out must be a contiguous %s tensor of shape %s on %s" % (h.dtype, (P, R, Cn), h.device))
+    g_h = torch.empty_like(h)
+    with torch.cuda.device(h.device):
+        check(lib().mv3d_fusion_join_backward(_ptr(h), _ptr(g_out), _FJ_DTYPES[h.dtype], S, P, V, R, Cn, k.ctypes.data_as(C.c_void_p),
+                                              _ptr(drop), C.c_float(scale), _ptr(g_h), _stream()), "mv3d_fusion_join_backward")
+    return g_h
+
+
+class FusionJoin(torch.autograd.Function):
+    """apply(h, keep, drop, scale) -> the joined activations; differentiable in h"""
+
+    @staticmethod
+    def forward(ctx, h, keep, drop, scale):
+        h = h.detach().contiguous()
+        ctx.keep, ctx.scale = np.array(keep, copy=True), float(scale)
+        ctx.save_for_backward(h, drop)
+        return fusion_join(h, keep, drop, scale)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        h, drop = ctx.saved_tensors
+        return fusion_join_backward(h, g_out.contiguous(), ctx.keep, drop, ctx.scale), None, None, None
+
+
 # ------------------------------------------------------------------ training losses (SURVEY §8(f) rank 4)
 def _loss_call(fn, name, cls, labels, pred, tgt, extra, sigma, want_grad):
     dev = cls.device
