@@ -124,10 +124,10 @@ Tr_imu_to_velo: 9.999976000000e-01 7.553071000000e-04 -2.035826000000e-03 -8.086
 """
 
 
-def gen_kitti(d):
-    """KITTI calib / label files -> GT encodings, through the reference's own loader
-    (lib/datasets/kitti_mv3d.py, imported with a stub `datasets` package: the real one drags in every dataset) and
-    the gt part of lib/roi_data_layer/minibatch_mv3d.py:get_minibatch (cv2.imread stubbed to np.load)."""
+def kitti_loader(d):
+    """(kitti_mv3d, get_minibatch) of the reference in the scratch build `d`: lib/datasets/kitti_mv3d.py, imported with a stub
+    `datasets` package (the real one drags in every dataset), and lib/roi_data_layer/minibatch_mv3d.py (cv2.imread stubbed to
+    np.load)."""
     L = os.path.join(d, "lib")
     os.makedirs(f"{L}/datasets", exist_ok=True)
     os.makedirs(f"{L}/roi_data_layer", exist_ok=True)
@@ -146,9 +146,19 @@ def gen_kitti(d):
         subprocess.check_call([sys.executable, "-m", "lib2to3", "-w", "-n", f], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     from datasets.kitti_mv3d import kitti_mv3d
     from roi_data_layer.minibatch_mv3d import get_minibatch
+    return kitti_mv3d, get_minibatch
+
+
+KITTI_TREE_DIRS = ("ImageSets", "object/training/calib", "object/training/label_2", "object/training/image_2", "object/training/lidar_bv")
+
+
+def gen_kitti(d):
+    """KITTI calib / label files -> GT encodings, through the reference's own loader and the gt part of
+    get_minibatch (`kitti_loader`)."""
+    kitti_mv3d, get_minibatch = kitti_loader(d)
     rng = np.random.RandomState(71)
     root = os.path.join(d, "KITTI")
-    for sub_ in ("ImageSets", "object/training/calib", "object/training/label_2", "object/training/image_2", "object/training/lidar_bv"):
+    for sub_ in KITTI_TREE_DIRS:
         os.makedirs(os.path.join(root, sub_))
     types = ["Car", "Van", "Car", "Pedestrian", "DontCare", "Car", "Cyclist", "Car", "Truck", "Car", "Car", "Misc", "Car"]
     frames, calib_txt = [], []
