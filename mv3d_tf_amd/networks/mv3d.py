@@ -387,7 +387,9 @@ class MV3D:
         """feed -> L on the device.  Tensors go as they are.  The SMALL host arrays of a step (im_info, calib, the ground-truth lists: a
         dozen arrays of a few hundred bytes) are packed into one pinned staging buffer and cross in ONE asynchronous copy -- each on
         its own is a pageable, synchronous hipMemcpy (profiles/r06_train_tail: 7 copy -> copy gaps of 24 us per step).  Two staging
-        buffers alternate: the copy of step n may still be reading when step n + 1 packs."""
+        buffers alternate: the copy of step n may still be reading when step n + 1 packs.  Each buffer has an event recorded after
+        its copy, and the host waits for it before it packs into that buffer again: the copy of step n may ALSO still be queued when
+        step n + 2 packs (a host two steps ahead of the stream).  The event has normally completed by then."""
         small, order = [], []
         for k in _INPUTS:
             if k not in feed or feed[k] is None:
@@ -410,9 +412,11 @@ class MV3D:
             return
         st = self.__dict__.get("_stage")
         if st is None:                                                  # (pinned allocations cost milliseconds: once per network)
-            st = self.__dict__["_stage"] = {"pin": [torch.empty(self._STAGE_BYTES // 4, dtype=torch.float32).pin_memory() for _ in range(2)], "n": 0}
-        pin = st["pin"][st["n"] & 1]
+            st = self.__dict__["_stage"] = {"pin": [torch.empty(self._STAGE_BYTES // 4, dtype=torch.float32).pin_memory() for _ in range(2)],
+                                            "copied": [torch.cuda.Event() for _ in range(2)], "n": 0}
+        pin, copied = st["pin"][st["n"] & 1], st["copied"][st["n"] & 1]
         st["n"] += 1
+        copied.synchronize()                                            # (this buffer's last copy has read it; at once if never recorded)
         host = pin.numpy()
         off, offs = 0, []
         for a in small:
@@ -421,6 +425,7 @@ class MV3D:
             off += -(-a.size // 4) * 4
         devbuf = torch.empty(total, dtype=torch.float32, device=dev)
         devbuf.copy_(pin[:total], non_blocking=True)
+        copied.record(torch.cuda.current_stream(dev))
         it = iter(zip(offs, small))
         for k, is_list, shapes in order:
             views = []

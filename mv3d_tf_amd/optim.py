@@ -33,7 +33,10 @@ class Adam(torch.optim.Adam):
     def _tables_for(self, key, items, dev):
         """device tables of one launch: the chunk tables depend on the tensors' sizes only (built once per parameter list); the tensor
         table (pointers) is refilled in a pinned staging buffer and copied asynchronously on the step's stream whenever a pointer
-        moved -- gradients are fresh allocations in a single-process step (zero_grad drops them), usually at the same addresses"""
+        moved -- gradients are fresh allocations in a single-process step (zero_grad drops them), usually at the same addresses.
+        Two staging buffers alternate, each with an event recorded after its copy: the host waits for that event before it rewrites
+        the buffer (a host that runs ahead of the stream would otherwise hand step n the pointers of step n + 1).  The event has
+        normally completed: the wait costs something only when the host is two refills ahead of the device."""
         cache = self.__dict__.setdefault("_cache", {})
         ent = cache.get(key)
         if ent is None:
@@ -45,7 +48,9 @@ class Adam(torch.optim.Adam):
             ct_dev = torch.from_numpy(np.concatenate(ct)).to(dev)
             cf_dev = torch.from_numpy(np.concatenate(cf)).to(dev)
             nbytes = C.sizeof(AdamTensor) * len(items)
-            ent = {"ct": ct_dev, "cf": cf_dev, "n": int(ct_dev.numel()), "pin": torch.empty(nbytes, dtype=torch.uint8).pin_memory(),
+            ent = {"ct": ct_dev, "cf": cf_dev, "n": int(ct_dev.numel()),
+                   "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)],
+                   "copied": [torch.cuda.Event() for _ in range(2)], "fills": 0,
                    "dev": torch.empty(nbytes, dtype=torch.uint8, device=dev), "ptrs": None}
             cache[key] = ent
         lp = [self.lowp.get(id(p)) for p, _, _ in items]
@@ -55,10 +60,15 @@ class Adam(torch.optim.Adam):
             raise ValueError("register_lowp: one 16-bit type per optimizer")
         ent["lowp"] = 0 if not kinds else (1 if kinds.pop() == torch.float16 else 2)
         if ptrs != ent["ptrs"]:
-            arr = (AdamTensor * len(items)).from_buffer(ent["pin"].numpy())
+            slot = ent["fills"] & 1
+            ent["fills"] += 1
+            pin, copied = ent["pin"][slot], ent["copied"][slot]
+            copied.synchronize()                                      # (this buffer's last copy has read it; at once if never recorded)
+            arr = (AdamTensor * len(items)).from_buffer(pin.numpy())
             for k, ((p, _, _), q) in enumerate(zip(items, ptrs)):
                 arr[k] = AdamTensor(q[0], q[1], q[2], q[3], p.numel(), q[4] or None)
-            ent["dev"].copy_(ent["pin"], non_blocking=True)           # (stream-ordered before the launch below)
+            ent["dev"].copy_(pin, non_blocking=True)                  # (stream-ordered before the launch below)
+            copied.record(torch.cuda.current_stream(dev))
             ent["ptrs"] = ptrs
         return ent
 
