@@ -971,6 +971,43 @@ int mv3d_fusion_join_forward(const void *h_dev, int dtype, int sets_in, int path
 int mv3d_fusion_join_backward(const void *h_dev, const void *g_out_dev, int dtype, int sets_in, int paths, int views, int rows,
                               int channels, const uint8_t *keep, const uint8_t *drop_dev, float scale, void *g_h_dev, void *stream);
 
+/* ------------------------------------------------------------------ upsampled ROI features (csrc/upsample.hip)
+ * Bilinear upsampling of a feature map by an integer factor s = 2 or 4 in front of RoiPool (MV3D paper §3.2), for up to
+ * MV3D_MAX_ROI_VIEWS views in ONE launch (the views' workgroups share the grid).  x (batch, height, width, channels) ->
+ * y (batch, s*height, s*width, channels).
+ * The coordinate rule is TensorFlow 1's resize_bilinear(align_corners=False): up-pixel o sits at source coordinate o / s.  Up-pixel
+ * s*i therefore IS source pixel i -- RoiPool's own convention (feature pixel i <-> input coordinate i / scale) -- and the ROI scale
+ * after the upsampling is s / 8 with no half-pixel shift.  (NOT the half-pixel rule of torch's F.interpolate.)
+ * Per axis of n source pixels, up-index o has the taps i0 = o / s with weight (s - o % s) / s and i1 = min(i0 + 1, n - 1) with weight
+ * (o % s) / s.  A tap of weight 0 is dropped: its value never enters the arithmetic, so a NaN or Inf neighbour does not reach an
+ * aligned up-pixel.  Two taps on the same source index (the clamped last rows and columns) merge into one tap of weight 1.  So every
+ * up-index has one tap of weight 1, or two taps with dyadic weights.
+ * Forward, per channel, in f32 with every operation rounded on its own (no contraction): horizontally first, on each of the one or
+ * two source rows: t = a (one tap) or t = fadd(fmul(w0, a), fmul(w1, b)) (two taps); then the same rule vertically on the one or two
+ * t.  f16 / bf16 inputs are converted to f32 first (exact); the output is f32.
+ * Backward, the exact transpose: g_x[iy][ix] = sum of fmul(W, g_y[oy][ox]) over the up-pixels that have a tap on (iy, ix), W = wy * wx
+ * (exact in f32), the terms added to 0.0f in raster order (oy ascending, then ox ascending) -- at most (2s - 1)^2 of them -- by the one
+ * thread that owns the element.  No atomics, no workspace, bit-reproducible; every element of g_x is written.
+ *   in       forward: x in `dtype` (0 = f32, 1 = f16, 2 = bf16, the numbering of mv3d_fusion_join_*), addressed through the strides;
+ *            backward: g_y (batch, s*height, s*width, channels) contiguous f32 (dtype must be 0, the strides are ignored)
+ *   out      forward: y contiguous f32; backward: g_x (batch, height, width, channels) contiguous f32
+ *   frame_stride, row_stride, pixel_stride   of `in`, in ELEMENTS (forward): the interior of a framed 16-bit map is read where it lies
+ * One launch each, no allocation, memset or synchronisation (capturable in a graph); 64-bit element offsets.  A view whose channel
+ * count is a multiple of the vector width (4 f32, 8 16-bit elements) and whose pointers and strides are 16-byte aligned moves 16 bytes
+ * per lane; otherwise the WHOLE view runs with scalar accesses (no vector body with a scalar tail).  batch == 0 in a view launches
+ * nothing for it.  MV3D_ERR_INVALID_ARG before any HIP call: num_views outside 1..MV3D_MAX_ROI_VIEWS or NULL views; dtype outside
+ * 0..2 (backward: not 0), a factor other than 2 or 4; batch < 0, height, width or channels < 1; (forward) a pixel stride < channels,
+ * a row stride < width * pixel stride or a frame stride < height * row stride; an up-map of 2^31 elements per frame or more; a NULL
+ * buffer with batch > 0. */
+typedef struct {
+    const void *in;
+    void *out;
+    int64_t frame_stride, row_stride, pixel_stride;
+    int32_t dtype, batch, height, width, channels, factor;
+} mv3d_upsample_view;
+int mv3d_upsample_bilinear_views(int num_views, const mv3d_upsample_view *views, void *stream);
+int mv3d_upsample_bilinear_backward_views(int num_views, const mv3d_upsample_view *views, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmv3d_hip.so")
 
 OK, ERR_INVALID_ARG, ERR_WORKSPACE, ERR_HIP, ERR_ZERO_DIVISION = 0, 1, 2, 3, 4
+MAX_ROI_VIEWS = 4          # MV3D_MAX_ROI_VIEWS: the views one grouped RoiPool / upsampling launch takes
 
 
 class ProposalParams(C.Structure):
@@ -148,6 +149,13 @@ class Recall3dSplit(C.Structure):
                 ("limits_dev", C.c_void_p), ("thresholds_dev", C.c_void_p)]
 
 
+class UpsampleView(C.Structure):
+    """mv3d_upsample_view"""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("frame_stride", C.c_int64), ("row_stride", C.c_int64),
+                ("pixel_stride", C.c_int64), ("dtype", C.c_int32), ("batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("channels", C.c_int32), ("factor", C.c_int32)]
+
+
 _P = C.c_void_p
 _SIGS = {
     "mv3d_version": (C.c_int, []),
@@ -279,6 +287,8 @@ _SIGS = {
     "mv3d_mirror_columns": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, _P]),
     "mv3d_fusion_join_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P]),
     "mv3d_fusion_join_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P]),
+    "mv3d_upsample_bilinear_views": (C.c_int, [C.c_int, C.POINTER(UpsampleView), _P]),
+    "mv3d_upsample_bilinear_backward_views": (C.c_int, [C.c_int, C.POINTER(UpsampleView), _P]),
 }
 EXPORTS = tuple(_SIGS)
 

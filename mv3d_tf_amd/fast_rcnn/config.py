@@ -79,6 +79,11 @@ cfg.PIXEL_MEANS = np.array([[[95.8814, 98.7743, 93.8549]]])
 # towers are concatenated in front of cls_score / bbox_pred); 'deep' = the MV3D paper's deep fusion (the views' activations are joined
 # by an element-wise mean after every layer, networks/mv3d.py)
 cfg.FUSION = 'early'
+# (not in the reference, which has the layers commented out: MV3D_train.py:117-120) the MV3D paper's upsampling of the feature maps in
+# front of ROI pooling (section 3.2): bilinear factors for (bird's-eye view, image, front view), each 1, 2 or 4; the paper's setting is
+# (4, 2, 4).  A view with factor s pools its conv5_3 upsampled s times at scale s / 8 (ops.upsample_bilinear_views, DESIGN.md section
+# 3.20); (1, 1, 1) = the reference: nothing is upsampled.  No parameters, so every checkpoint loads under every setting.
+cfg.ROI_UPSAMPLE = (1, 1, 1)
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
 cfg.EXP_DIR = 'default'
@@ -104,6 +109,8 @@ def _merge(a, b, path=""):
             continue
         if isinstance(old, np.ndarray):
             v = np.array(v, dtype=old.dtype)
+        elif path + k == "ROI_UPSAMPLE" and isinstance(v, list):  # (YAML has no tuples: its sequence for this one key)
+            v = tuple(v)
         elif type(old) is not type(v) and not (isinstance(old, float) and isinstance(v, int)):
             raise ValueError('Type mismatch ({} vs. {}) for config key: {}'.format(type(old), type(v), path + k))
         b[k] = type(old)(v) if isinstance(old, float) else v

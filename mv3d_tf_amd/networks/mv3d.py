@@ -60,18 +60,24 @@ def draw_drop_path(rng, views):
 class MV3D:
     """One class for both graphs; `phase` is 'TEST' (MV3D_test) or 'TRAIN' (MV3D_train)."""
 
-    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2, fusion=None):
+    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2, fusion=None, roi_upsample=None):
         """views = 2: the reference's graphs (BEV + RGB towers).  views = 3 adds the front view the MV3D paper has and the
         reference leaves a TODO (`proposal_transform`, network.py:293-315): a third VGG16 trunk on `lidar_fv_data`
         (1, 64, 512, 3), `rois_fv` = mv3d_rois_3d_to_fv(rois_3d), a third RoiPool `pool_5_3` and tower fc6_3 / fc7_3, the
         three towers concatenated (6144 -> cls_score / bbox_pred).  Parity unpinned by construction.
         fusion = 'early' (the reference's head) | 'deep' (the paper's deep fusion: the views are joined by an element-wise mean after
-        fc6 and after fc7, cls_score / bbox_pred read the 2048-wide join); None = cfg.FUSION."""
+        fc6 and after fc7, cls_score / bbox_pred read the 2048-wide join); None = cfg.FUSION.
+        roi_upsample = (BEV, image, front view) factors, each 1, 2 or 4: the paper's bilinear upsampling of conv5_3* in front of RoiPool
+        (section 3.2: (4, 2, 4)); (1, 1, 1) = the reference's graphs; None = cfg.ROI_UPSAMPLE."""
         self.phase = phase
         self.views = int(views)
         self.fusion = cfg.FUSION if fusion is None else fusion
         if self.fusion not in ("early", "deep"):
             raise ValueError("fusion must be 'early' or 'deep', got %r" % (self.fusion,))
+        up = cfg.ROI_UPSAMPLE if roi_upsample is None else roi_upsample
+        if not isinstance(up, (tuple, list)) or len(up) != 3 or any(isinstance(s, bool) or s not in (1, 2, 4) for s in up):
+            raise ValueError("roi_upsample must be three factors (BEV, image, front view), each 1, 2 or 4, got %r" % (up,))
+        self.roi_upsample = tuple(int(s) for s in up)
         # drop-path draws of the deep head (cfg.TRAIN.DROP_PATH): the network's own generator, never numpy's global one (the
         # target layers' draw stream is the reference's); the same seed on every rank
         self.drop_path_rng = np.random.RandomState(cfg.RNG_SEED)
@@ -89,6 +95,7 @@ class MV3D:
         self.fused_head = True           # TRAIN phase: the fusion head as one autograd function (fused_head.py); False = op by op
         self.fixed_rois = False          # TEST phase: B x capacity ROI rows, no host sync (fast_rcnn.test_mv.ServeGraph)
         self._mfma = None
+        self._bev_interior = None        # the serving trunk's framed BEV conv5_3 without its frame, set by _mfma_trunks
         self._train_pool = None
         self._wcache = {}
         self._step_half = None      # {name: (w, b)} in amp_dtype for the current training step (amp_cast.cast_params)
@@ -191,6 +198,7 @@ class MV3D:
         maps = self._mfma.trunks([L[k] for _, k in keys], [sfx for sfx, _ in keys], [sfx == "" for sfx, _ in keys])
         bev = maps[0]
         L["conv5_3"] = bev[:, 1:-1, 1:-1].float().contiguous()       # the f32 NHWC map the RoiPool layer reads
+        self._bev_interior = bev[:, 1:-1, 1:-1]                      # (what an upsampling in front of RoiPool reads through strides)
         rpn = self._mfma.rpn_conv(bev)                               # (B, H, W, 512) f16
         L["rpn_conv/3x3"] = rpn
         heads = []
@@ -439,6 +447,7 @@ class MV3D:
         """feed: dict with the reference's placeholder names (Appendix C of SURVEY.md); numpy or tensors."""
         L = self.layers
         L.clear()
+        self._bev_interior = None
         dev = self.device
         to_dev = lambda a: a.to(dev) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32)).to(dev)
         self._stage_host_inputs(feed, L, dev, to_dev)
@@ -564,8 +573,27 @@ class MV3D:
             L["roi_data_fv"] = rois_fv
             views.append((L["conv5_3_3"], rois_fv))
             names.append("pool_5_3")
+        scale = 1.0 / 8
+        factors = self.roi_upsample[:len(views)]
+        if any(s > 1 for s in factors):
+            # (not in the reference) the paper's upsampling in front of ROI pooling: the views with a factor > 1
+            # in ONE launch; up-pixel s i is source pixel i, so the up-map is pooled at s / 8.  The serving trunk's framed 16-bit BEV map
+            # is read where it lies (the same values as the f32 L["conv5_3"], without reading that copy).
+            keys = ("conv5_3", "conv5_3_2", "conv5_3_3")
+            pick = [k for k, s in enumerate(factors) if s > 1]
+            src = [L[keys[k]] for k in pick]
+            if pick[0] == 0 and self._bev_interior is not None:
+                src[0] = self._bev_interior
+            if torch.is_grad_enabled() and any(x.requires_grad for x in src):
+                ups = ops.UpsampleBilinearViews.apply(tuple(factors[k] for k in pick), *src)
+            else:
+                ups = ops.upsample_bilinear_views([(x.detach(), factors[k]) for x, k in zip(src, pick)])
+            for k, y in zip(pick, ups):
+                L[keys[k] + "_up"] = y
+                views[k] = (y, views[k][1])
+            scale = tuple(s / 8 for s in factors)
         # (serving in 16-bit mode: the pooled maps in the head's type straight from the pooling launch -- no f32 copy, no cast launch)
-        for name, top in zip(names, roi_pool_views([(d.contiguous(), r.contiguous()) for d, r in views], 7, 7, 1.0 / 8, top_dtype=self.amp_dtype)):
+        for name, top in zip(names, roi_pool_views([(d.contiguous(), r.contiguous()) for d, r in views], 7, 7, scale, top_dtype=self.amp_dtype)):
             L[name] = top
         if self.fusion == "deep" and self.phase == "TRAIN":
             # deep fusion: P = 1 path, or 1 + views with the auxiliary paths; the step's keep tables are recorded

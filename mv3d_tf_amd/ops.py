@@ -616,6 +616,24 @@ def roi_pool_backward_views_pair(views, pooled_height, pooled_width, outs=None, 
     return res
 
 
+ROI_PAIR_MAX_PIXELS = 0xfffe         # roi_pair_shapes (csrc/roi_pool.hip): the pair's own kernels take maps of at most this many pixels
+
+
+def roi_pool_pair_workspace(views, pooled_height, pooled_width):
+    """The workspace roi_pool_backward_views_pair should be given for these backward views: None while every map fits the pair's own
+    kernels, which use none (mv3d_roi_pool_pair_workspace_bytes cannot tell: it answers with the indexed RoiPoolGrad's size for every
+    shape); for a larger map (a 4x upsampled 608 x 608 bird's-eye view) the reused buffer of roi_pool_backward_views, with which the
+    hand-over takes the index + gather backward.  Should the C side's condition ever differ from this one, only the choice between
+    two backward kernels with the same results differs: without a workspace the hand-over runs the unindexed RoiPoolGrad."""
+    if all(shape[1] * shape[2] <= ROI_PAIR_MAX_PIXELS for _, _, _, shape, _ in views):
+        return None
+    arr = (RoiGradView * len(views))()
+    for k, (_, rois, _, (B, H, W, Cc), scale) in enumerate(views):       # (the size query reads the shapes only)
+        arr[k] = RoiGradView(None, None, None, None, float(scale), B, rois.shape[0], H, W, Cc)
+    nbytes = lib().mv3d_roi_pool_pair_workspace_bytes(len(views), arr, pooled_height, pooled_width)
+    return _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
+
+
 def rois_3d_to_fv(rois_3d, out=None):
     """rois_3d (R,7) device f32 [b,x,y,z,l,w,h] -> rois_fv (R,5) [b,x1,y1,x2,y2] on the 64 x 512 front-view map."""
     r3 = rois_3d.contiguous()
@@ -717,6 +735,117 @@ class FusionJoin(torch.autograd.Function):
     def backward(ctx, g_out):
         h, drop = ctx.saved_tensors
         return fusion_join_backward(h, g_out.contiguous(), ctx.keep, drop, ctx.scale), None, None, None
+
+
+# ------------------------------------------------------------------ upsampled ROI features
+def _upsample_view_checks(x, factor, what):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _FJ_DTYPES:
+        raise TypeError("%s: a CUDA float32 / float16 / bfloat16 tensor is required, got %s"
+                        % (what, "%s on %s" % (x.dtype, x.device) if isinstance(x, torch.Tensor) else type(x).__name__))
+    if x.dim() != 4 or x.shape[1] < 1 or x.shape[2] < 1 or x.shape[3] < 1:
+        raise ValueError("%s: a (batch, height, width, channels) tensor with height, width, channels >= 1 is required, got shape %s"
+                         % (what, tuple(x.shape)))
+    if factor not in (2, 4):
+        raise ValueError("%s: the factor must be 2 or 4, got %r" % (what, factor))
+
+
+def _nhwc_strides(t):
+    """element strides (frame, row, pixel, channel) of a 4-D tensor; an axis of one element may carry any stride (it is never stepped
+    along), so it gets the stride a contiguous tensor would have"""
+    B, H, W, Cn = t.shape
+    if B == 0:
+        return H * W * Cn, W * Cn, Cn, 1
+    fs, rs, ps, cs = t.stride()
+    cs = 1 if Cn == 1 else cs
+    ps = Cn * cs if W == 1 else ps
+    rs = W * ps if H == 1 else rs
+    fs = H * rs if B <= 1 else fs
+    return fs, rs, ps, cs
+
+
+def _upsample_out(outs, k, shape, device):
+    if outs is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    y = outs[k]
+    if tuple(y.shape) != shape or y.dtype != torch.float32 or y.device != device or not y.is_contiguous():
+        raise ValueError("outs[%d] must be a contiguous float32 tensor of shape %s on %s" % (k, shape, device))
+    return y
+
+
+def upsample_bilinear_views(views, outs=None):
+    """views: [(x (B, H, W, C) device tensor f32 / f16 / bf16, factor 2 | 4), ...] -> [y (B, s H, s W, C) f32, ...]: the bilinear
+    upsampling in front of RoiPool (mv3d_upsample_bilinear_views: up-pixel o at source coordinate o / s, so up-pixel s i is source pixel
+    i), ONE launch for all views.  A strided x (unit channel stride, e.g. the interior y[:, 1:-1, 1:-1] of a framed map) is read where
+    it lies; anything else is made contiguous first.  outs: contiguous f32 tensors to write into instead of fresh ones.  Device tensors
+    only; there is no torch path."""
+    if not 1 <= len(views) <= _lib.MAX_ROI_VIEWS:
+        raise ValueError("upsample_bilinear_views: 1..%d views, got %d" % (_lib.MAX_ROI_VIEWS, len(views)))
+    arr = (_lib.UpsampleView * len(views))()
+    res, held = [], []
+    for k, (x, s) in enumerate(views):
+        _upsample_view_checks(x, s, "upsample_bilinear_views")
+        B, H, W, Cn = (int(n) for n in x.shape)
+        fs, rs, ps, cs = _nhwc_strides(x)
+        if not (cs == 1 and ps >= Cn and rs >= W * ps and fs >= H * rs):
+            x = x.contiguous()
+            fs, rs, ps, cs = _nhwc_strides(x)
+        held.append(x)
+        y = _upsample_out(outs, k, (B, s * H, s * W, Cn), x.device)
+        arr[k] = _lib.UpsampleView(x.data_ptr(), y.data_ptr(), fs, rs, ps, _FJ_DTYPES[x.dtype], B, H, W, Cn, s)
+        res.append(y)
+    with torch.cuda.device(res[0].device):
+        check(lib().mv3d_upsample_bilinear_views(len(views), arr, _stream()), "mv3d_upsample_bilinear_views")
+    return res
+
+
+def upsample_bilinear(x, factor):
+    """one view of upsample_bilinear_views"""
+    return upsample_bilinear_views([(x, factor)])[0]
+
+
+def upsample_bilinear_backward_views(views, outs=None):
+    """views: [(g_y (B, s H, s W, C) f32 device tensor, factor), ...] -> [g_x (B, H, W, C) f32, ...]: the exact transpose of
+    upsample_bilinear_views (mv3d_upsample_bilinear_backward_views), ONE launch, every element
+    written by the one thread that owns it (outs: tensors to write into; they need no zeroing)."""
+    if not 1 <= len(views) <= _lib.MAX_ROI_VIEWS:
+        raise ValueError("upsample_bilinear_backward_views: 1..%d views, got %d" % (_lib.MAX_ROI_VIEWS, len(views)))
+    arr = (_lib.UpsampleView * len(views))()
+    res, held = [], []
+    for k, (g, s) in enumerate(views):
+        _upsample_view_checks(g, s, "upsample_bilinear_backward_views")
+        if g.dtype != torch.float32 or g.shape[1] % s or g.shape[2] % s:
+            raise ValueError("upsample_bilinear_backward_views: g_y must be float32 of shape (B, %d H, %d W, C), got %s %s"
+                             % (s, s, g.dtype, tuple(g.shape)))
+        g = g.contiguous()
+        held.append(g)
+        B, H, W, Cn = int(g.shape[0]), int(g.shape[1]) // s, int(g.shape[2]) // s, int(g.shape[3])
+        gx = _upsample_out(outs, k, (B, H, W, Cn), g.device)
+        arr[k] = _lib.UpsampleView(g.data_ptr(), gx.data_ptr(), 0, 0, 0, 0, B, H, W, Cn, s)
+        res.append(gx)
+    with torch.cuda.device(res[0].device):
+        check(lib().mv3d_upsample_bilinear_backward_views(len(views), arr, _stream()), "mv3d_upsample_bilinear_backward_views")
+    return res
+
+
+class UpsampleBilinearViews(torch.autograd.Function):
+    """apply(factors, x_0, x_1, ...) -> (y_0, y_1, ...): upsample_bilinear_views, differentiable in every x; forward and backward are
+    ONE launch each for all views.  f32 gradients; a view whose output gets no gradient contributes zeros."""
+
+    @staticmethod
+    def forward(ctx, factors, *xs):
+        ctx.factors = tuple(int(s) for s in factors)
+        ctx.shapes = [tuple(x.shape) for x in xs]
+        ctx.device = xs[0].device
+        return tuple(upsample_bilinear_views([(x.detach(), s) for x, s in zip(xs, ctx.factors)]))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        views = []
+        for g, s, (B, H, W, Cn) in zip(grads, ctx.factors, ctx.shapes):
+            if g is None:
+                g = torch.zeros((B, s * H, s * W, Cn), dtype=torch.float32, device=ctx.device)
+            views.append((g.float(), s))
+        return (None,) + tuple(upsample_bilinear_backward_views(views))
 
 
 # ------------------------------------------------------------------ training losses (SURVEY §8(f) rank 4)

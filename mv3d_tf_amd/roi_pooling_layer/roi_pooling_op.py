@@ -36,7 +36,8 @@ class RoiPoolViewsFunction(torch.autograd.Function):
     """The RoiPool layers of one step (`pool_5`, `pool_5_2` [, `pool_5_3`]: network.py:199-213 called once per view) as the library's
     PAIR: ONE launch forward (mv3d_roi_pool_forward_views_pair: every view, the argmax plane kept as private one-byte codes) and one
     call backward (mv3d_roi_pool_backward_views_pair without a workspace: ONE launch, every view's map tiles in LDS, the ordered
-    sums of roi_pooling_op.cc:319-452).  apply(ph, pw, scale, data_0, rois_0, data_1, rois_1, ...) -> (top_0, top_1, ...);
+    sums of roi_pooling_op.cc:319-452).  apply(ph, pw, scale, data_0, rois_0, data_1, rois_1, ...) -> (top_0, top_1, ...); scale is a
+    float for all views or a tuple with one float per view (views upsampled by different factors, DESIGN.md section 3.20);
     gradients for the data tensors only (roi_pooling_op_grad.py:43).  A view whose output gets no gradient (unused in the loss)
     contributes zeros, like an unconnected tf.gradients branch."""
 
@@ -44,14 +45,15 @@ class RoiPoolViewsFunction(torch.autograd.Function):
     def forward(ctx, pooled_height, pooled_width, spatial_scale, *tensors):
         datas = [t.contiguous() for t in tensors[0::2]]
         rois = [t.contiguous() for t in tensors[1::2]]
-        res = ops.roi_pool_forward_views_pair([(d, r, spatial_scale) for d, r in zip(datas, rois)], pooled_height, pooled_width)
+        scales = _view_scales(spatial_scale, len(datas))
+        res = ops.roi_pool_forward_views_pair([(d, r, s) for d, r, s in zip(datas, rois, scales)], pooled_height, pooled_width)
         ctx.save_for_backward(*rois, *[am for _, am in res])
-        ctx.meta = ([tuple(d.shape) for d in datas], pooled_height, pooled_width, spatial_scale)
+        ctx.meta = ([tuple(d.shape) for d in datas], pooled_height, pooled_width, scales)
         return tuple(top for top, _ in res)
 
     @staticmethod
     def backward(ctx, *grads):
-        shapes, ph, pw, scale = ctx.meta
+        shapes, ph, pw, scales = ctx.meta
         n = len(shapes)
         saved = ctx.saved_tensors
         rois, argmax = saved[:n], saved[n:]
@@ -60,18 +62,31 @@ class RoiPoolViewsFunction(torch.autograd.Function):
             g = grads[k]
             if g is None:
                 g = torch.zeros((rois[k].shape[0], ph, pw, shapes[k][3]), dtype=torch.float32, device=rois[k].device)
-            views.append((g.contiguous(), rois[k], argmax[k], shapes[k], scale))
-        outs = ops.roi_pool_backward_views_pair(views, ph, pw)   # (one launch, no scratch memory)
+            views.append((g.contiguous(), rois[k], argmax[k], shapes[k], scales[k]))
+        # (one launch, no scratch memory) -- except for a map beyond the pair's own kernels (a 4x upsampled 608 x 608 bird's-eye view):
+        # the entries then hand every view to the plain forward and the index + gather backward, which takes a workspace
+        outs = ops.roi_pool_backward_views_pair(views, ph, pw, workspace=ops.roi_pool_pair_workspace(views, ph, pw))
         ret = [None, None, None]
         for k in range(n):
             ret += [outs[k], None]
         return tuple(ret)
 
 
+def _view_scales(spatial_scale, n):
+    """spatial_scale of roi_pool_views -> one float per view"""
+    if isinstance(spatial_scale, (list, tuple)):
+        if len(spatial_scale) != n:
+            raise ValueError("spatial_scale: one value per view is required (%d views), got %d" % (n, len(spatial_scale)))
+        return tuple(float(s) for s in spatial_scale)
+    return (float(spatial_scale),) * n
+
+
 def roi_pool_views(views, pooled_height, pooled_width, spatial_scale, top_dtype=None):
     """views: [(bottom_data NHWC device tensor, bottom_rois (R,5) device tensor), ...] -> [top, ...] (autograd-aware).
+    spatial_scale: a float for every view, or a sequence with one float per view (maps upsampled by different factors).
     top_dtype (inference only, torch.float16 / bfloat16, maps of 256 / 512 / 1024 channels): the pooled maps in that type -- what the
     16-bit head would cast them to anyway -- written by the pooling launch itself."""
+    scales = _view_scales(spatial_scale, len(views))
     flat = []
     for d, r in views:
         _check(d, r)
@@ -79,10 +94,10 @@ def roi_pool_views(views, pooled_height, pooled_width, spatial_scale, top_dtype=
     if not (torch.is_grad_enabled() and any(d.requires_grad for d, _ in views)):
         # inference: no gradient will be asked for, so the argmax planes (as many bytes again as the pooled output) are not written
         half = top_dtype if top_dtype in (torch.float16, torch.bfloat16) and all(d.shape[3] in (256, 512, 1024) for d, _ in views) else None
-        res = ops.roi_pool_forward_views([(d.contiguous(), r.contiguous(), float(spatial_scale)) for d, r in views], int(pooled_height),
+        res = ops.roi_pool_forward_views([(d.contiguous(), r.contiguous(), s) for (d, r), s in zip(views, scales)], int(pooled_height),
                                          int(pooled_width), want_argmax=False, top_dtype=half)
         return [top for top, _ in res]
-    return list(RoiPoolViewsFunction.apply(int(pooled_height), int(pooled_width), float(spatial_scale), *flat))
+    return list(RoiPoolViewsFunction.apply(int(pooled_height), int(pooled_width), scales, *flat))
 
 
 def _check(bottom_data, bottom_rois):
