@@ -276,6 +276,26 @@ int mv3d_ROIPoolBackwardLaucher(const float *top_diff, float spatial_scale, int 
  * is restated in oracle/mv3d_oracle.c and both agree bit for bit. */
 int mv3d_rois_3d_to_fv(const float *rois_3d_dev, int num_rois, float *rois_fv_dev, void *stream);
 
+/* ------------------------------------------------------------------ front-view input (csrc/front_view_raster.hip)
+ * Velodyne points -> the (64, 512, 3) f32 map [height, distance, intensity] the third trunk reads as `lidar_fv_data`, for
+ * `num_frames` clouds behind three launches (clear keys, one 64-bit atomicMin per point, resolve), whatever num_frames is.
+ * PARITY UNPINNED (no reference code); a point lands on the pixel mv3d_rois_3d_to_fv gives its position (same projection).
+ *   points_dev   (total_points, 4) f32 [x, y, z, reflectance], the frames' clouds concatenated, 16-byte aligned
+ *   offsets_dev  (num_frames + 1) int32 ON THE DEVICE: frame b owns rows offsets[b] .. offsets[b + 1]; equal neighbours = an empty
+ *                frame; rows no frame owns are ignored.  No value in it can make the call read or write out of bounds.  NULL with
+ *                num_frames == 1: the one frame owns every row.
+ *   fv_dev       (num_frames, 64, 512, 3) f32, 16-byte aligned: [z, d, reflectance] of the pixel's nearest point (d = the f64
+ *                norm rounded once to f32; among equal d the last point), [0, 0, 0] where no point falls.  Dropped: non-finite
+ *                x / y / z, x == y == 0, pixels outside the window (nothing is clipped into it).
+ *   workspace    mv3d_point_cloud_2_front_workspace(num_frames) bytes (one 64-bit key per pixel), 16-byte aligned, the caller's;
+ *                it needs no initialisation and holds nothing between calls.
+ * No allocation, no host synchronisation; a plain chain of launches on `stream` (capturable).  MV3D_ERR_INVALID_ARG: NULL or
+ * misaligned pointers, negative counts, num_frames > MV3D_FV_MAX_FRAMES (the size query then returns 0). */
+#define MV3D_FV_MAX_FRAMES 1024
+size_t mv3d_point_cloud_2_front_workspace(int num_frames);
+int mv3d_point_cloud_2_front(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points, float *fv_dev,
+                             void *workspace_dev, void *stream);
+
 /* ------------------------------------------------------------------ anchor_target_layer
  * Replaces the deterministic part of lib/rpn_msr/anchor_target_layer_tf.py:21-250 plus
  * lib/utils/bbox.pyx:15-55 and lib/fast_rcnn/bbox_transform.py:32-58 (one frame):

@@ -225,6 +225,8 @@ _SIGS = {
     "mv3d_ROIPoolForwardLaucher": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mv3d_ROIPoolBackwardLaucher": (C.c_int, [_P, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "mv3d_rois_3d_to_fv": (C.c_int, [_P, C.c_int, _P, _P]),
+    "mv3d_point_cloud_2_front_workspace": (C.c_size_t, [C.c_int]),
+    "mv3d_point_cloud_2_front": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "mv3d_legacy_permutation": (C.c_int, [_P, C.c_int32, _P]),
     "mv3d_draw_training_subsamples": (C.c_int, [_P, C.c_int, C.POINTER(DrawFrame), C.POINTER(DrawParams), _P, C.c_size_t, _P, _P,
                                                 C.c_size_t]),

@@ -3,6 +3,7 @@
   <kitti>/object/{training,testing}/calib/000000.txt     P0..P3, R0_rect, Tr_velo_to_cam, Tr_imu_to_velo
   <kitti>/object/training/label_2/000000.txt             type trunc occ alpha x1 y1 x2 y2 h w l tx ty tz ry
   <kitti>/object/training/{image_2/*.png, lidar_bv/*.npy}, <kitti>/ImageSets/<set>.txt
+  <kitti>/object/{training,testing}/velodyne/000000.bin  x y z reflectance, f32 (read only with cfg.FRONT_VIEW_INPUT / a 3-view net)
 
 Interface kept from the reference (lib/datasets/kitti_mv3d.py): class `kitti_mv3d(image_set, kitti_path)` with
 `image_index`, `num_classes`, `image_path_at`, `lidar_path_at`, `calib_at`, `gt_roidb`, and roidb entries with the same
@@ -138,6 +139,12 @@ class kitti_mv3d(object):
 
     def lidar_path_at(self, i):
         return self._file('lidar_bv', i, self._lidar_ext)
+
+    def velodyne_path_at(self, i):
+        """(not in the reference) the frame's raw scan, what the front-view map is rasterised from; a mirrored index names the source
+        frame's file, like lidar_path_at.  The file is not looked for here: prepare_roidb records the path for every frame, and a
+        tree without scans still serves the two-view model"""
+        return os.path.join(self._dir('velodyne'), self._image_index[i] + '.bin')
 
     def _load_kitti_calib(self, index):
         return load_kitti_calib(os.path.join(self._dir('calib'), index + '.txt'))

@@ -84,6 +84,10 @@ cfg.FUSION = 'early'
 # (4, 2, 4).  A view with factor s pools its conv5_3 upsampled s times at scale s / 8 (ops.upsample_bilinear_views, DESIGN.md section
 # 3.20); (1, 1, 1) = the reference: nothing is upsampled.  No parameters, so every checkpoint loads under every setting.
 cfg.ROI_UPSAMPLE = (1, 1, 1)
+# (not in the reference, which has no front view) True: the data layer adds `lidar_fv_data` (1, 64, 512, 3), the third view's input,
+# rasterised on the device from the frame's Velodyne scan (ops.point_cloud_2_front; the entry's 'lidar_fv' map,
+# 'velodyne' array or 'velodyne_path' file).  False = the reference's blobs.  train_net refuses a 3-view network with the key off.
+cfg.FRONT_VIEW_INPUT = False
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
 cfg.EXP_DIR = 'default'

@@ -11,7 +11,10 @@ ops.detect_post_oriented: the same cut, order and cap with the NMS judged by the
 'regressed' footprint the corner lists carry the regressed corners, the boxes the NMS judged.  The key sends test_net down the
 device route whatever BATCH_SIZE is.  The frame-by-frame loop has no oriented NMS: with the key on test_mv.test_net
 raises ValueError where it asks for its output directory (config.get_output_dir), before it loads a frame.
-fast_rcnn.test_mv keeps the reference's frame-by-frame entry points as they are."""
+fast_rcnn.test_mv keeps the reference's frame-by-frame entry points as they are: they feed two views.  The third view's input enters
+here: `box_detect(sess, net, im, bv, calib, boxes=None, fv=None)` is test_mv.box_detect with the frame's (64,512,3) front-view map fed
+as `lidar_fv_data`, and `test_net` rasterises the frames' Velodyne scans for a three-view network (`front_view_source`), which sends it
+down the device route whatever BATCH_SIZE is."""
 import os
 import pickle
 import time
@@ -72,6 +75,45 @@ class ServeGraph(test_mv.ServeGraph):
         return ops.detect_post_lists(self.out["post"])
 
 
+def front_view_source(net, imdb):
+    """None for a two-view network; for a three-view one (net.views == 3) the function i -> (P,4) f32 scan of frame i that its
+    `lidar_fv_data` is rasterised from: imdb.points_at(i) if the imdb has it, else the file imdb.velodyne_path_at(i) names.  An imdb
+    with neither raises ValueError here, before a loop loads its first frame."""
+    if getattr(net, "views", 2) != 3:
+        return None
+    if hasattr(imdb, "points_at"):
+        return lambda i: np.ascontiguousarray(np.asarray(imdb.points_at(i), np.float32)[:, :4])
+    if hasattr(imdb, "velodyne_path_at"):
+        from ..utils.read_lidar import load_velodyne
+        return lambda i: load_velodyne(imdb.velodyne_path_at(i))
+    raise ValueError("a three-view network needs `lidar_fv_data`: the imdb has neither points_at(i) nor velodyne_path_at(i) to "
+                     "rasterise it from")
+
+
+class _FeedsFrontView:
+    """a network whose forward adds one frame's `lidar_fv_data` to the feed (what box_detect hands test_mv.box_detect, whose feed has
+    two views)"""
+
+    def __init__(self, net, fv):
+        self.net, self.fv = net, fv
+
+    def forward(self, feed):
+        return self.net.forward(dict(feed, lidar_fv_data=self.fv))
+
+
+def box_detect(sess, net, im, bv, calib, boxes=None, fv=None):
+    """test_mv.box_detect (lib/fast_rcnn/test_mv.py:149-264) with `fv` (not in the reference), the frame's (64,512,3) front-view map
+    as numpy or a device tensor (ops.point_cloud_2_front), fed as `lidar_fv_data`.  A three-view network needs it: ValueError without.
+    fv=None on a two-view network is test_mv.box_detect itself."""
+    if fv is None:
+        if getattr(net, "views", 2) == 3:
+            raise ValueError("a three-view network needs `lidar_fv_data`: pass fv=, the frame's (64, 512, 3) front-view map "
+                             "(ops.point_cloud_2_front)")
+        return test_mv.box_detect(sess, net, im, bv, calib, boxes)
+    fv = fv.reshape((1,) + ops.FV_SHAPE) if isinstance(fv, torch.Tensor) else np.asarray(fv, np.float32).reshape((1,) + ops.FV_SHAPE)
+    return test_mv.box_detect(sess, _FeedsFrontView(net, fv), im, bv, calib, boxes)
+
+
 def _load_frame(imdb, i):
     """(image, BEV map, calib) of frame i of a duck-typed imdb (see test_mv.test_net)"""
     if hasattr(imdb, "image_at"):
@@ -108,13 +150,16 @@ def group_frames(keys, batch_size):
 def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
     """test_mv.test_net with cfg.TEST.BATCH_SIZE (not in the reference).  1: test_mv.test_net, untouched.  n > 1: one eager forward
     with fixed ROI rows per group of equally shaped consecutive frames (`iter_frame_groups`), the box tail and ops.detect_post on the
-    device, ONE read-back of the final detections per group.  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
+    device, ONE read-back of the final detections per group.  A three-view network takes the device route for any BATCH_SIZE and
+    gets `lidar_fv_data` from the frames' scans (`front_view_source`), a group's frames rasterised by ONE batched
+    ops.point_cloud_2_front call.  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
     ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
     group) and the evaluate_detections call are test_mv.test_net's."""
     batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
     oriented = bool(cfg.TEST.get("NMS_ORIENTED", False))
     footprint = cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed")
-    if batch_size <= 1 and not oriented:
+    points_of = front_view_source(net, imdb)
+    if batch_size <= 1 and not oriented and points_of is None:
         return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
     if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
         net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
@@ -127,22 +172,26 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
 
     def keys():
         for i in range(num_images):
-            pending[i] = _load_frame(imdb, i)
+            pending[i] = _load_frame(imdb, i) + ((None if points_of is None else points_of(i)),)
             yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
 
     t_detect = t_misc = 0.0
     for group in iter_frame_groups(keys(), max(batch_size, 1)):
-        ims, bvs, calibs = zip(*(pending.pop(i) for i in group))
+        ims, bvs, calibs, clouds = zip(*(pending.pop(i) for i in group))
         B = len(group)
         t0 = time.time()
         im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
         bv_blob = np.stack([np.asarray(bv, np.float32) for bv in bvs])
         im_info = np.array([[bv_blob.shape[1], bv_blob.shape[2], 1]] * B, dtype=np.float32)
+        feed = {"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
+                "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
+        if points_of is not None:                                      # the group's scans back to back: one upload, one call
+            feed["lidar_fv_data"] = ops.point_cloud_2_front(np.concatenate(clouds, 0),
+                                                            offsets=np.cumsum([0] + [len(c) for c in clouds]))
         net.fixed_rois = True
         try:
             with torch.no_grad():
-                L = net.forward({"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
-                                 "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0})
+                L = net.forward(feed)
                 cnr, pr, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
         finally:
             net.fixed_rois = False

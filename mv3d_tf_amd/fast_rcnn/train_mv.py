@@ -348,7 +348,11 @@ def filter_roidb(roidb):
 
 
 def train_net(network, imdb, roidb, output_dir, pretrained_model=None, max_iters=10000):
-    """Train a Fast R-CNN network (:373-383)."""
+    """Train a Fast R-CNN network (:373-383).  A three-view network reads `lidar_fv_data`, which the data layer produces only with
+    cfg.FRONT_VIEW_INPUT on: with the key off this raises ValueError here, before the first step."""
+    if getattr(network, "views", 2) == 3 and not cfg.FRONT_VIEW_INPUT:
+        raise ValueError("a three-view network needs `lidar_fv_data`, which the data layer adds only when cfg.FRONT_VIEW_INPUT is "
+                         "on (it rasterises the frames' Velodyne scans: roi_data_layer/minibatch_mv3d.py)")
     roidb = filter_roidb(roidb)
     sw = SolverWrapper(None, None, network, imdb, roidb, output_dir, pretrained_model=pretrained_model)
     print('Solving...')

@@ -644,6 +644,81 @@ def rois_3d_to_fv(rois_3d, out=None):
     return out
 
 
+FV_SHAPE = (64, 512, 3)              # rows x columns x [height, distance, intensity] (csrc/front_view.h: FV_H, FV_W)
+FV_MAX_FRAMES = 1024                 # MV3D_FV_MAX_FRAMES
+
+
+def point_cloud_2_front_workspace_bytes(num_frames=1):
+    return int(lib().mv3d_point_cloud_2_front_workspace(int(num_frames)))
+
+
+def point_cloud_2_front(points, offsets=None, out=None, workspace=None):
+    """points (P,4) f32 [x,y,z,reflectance] (a device tensor, or a numpy array, which is uploaded) -> the (64,512,3) f32 front-view
+    map [height, distance, intensity] on the device (csrc/front_view_raster.hip, DESIGN.md section 3.21: nearest point per pixel,
+    among equal distances the last; empty pixels 0).  offsets = (B + 1) ascending int32 row offsets (host sequence / array, or a device
+    tensor): `points` is B clouds back to back, frame b owns rows offsets[b]:offsets[b + 1], the result is (B,64,512,3).
+    out = a contiguous f32 device tensor of the result's shape to write into (a slice of a captured step's `lidar_fv_data`),
+    workspace = a uint8 device tensor of point_cloud_2_front_workspace_bytes(B) bytes (default: the reused per-stream buffer); with
+    both given and device inputs the call allocates nothing and can be captured.  Every argument is checked before anything is
+    launched: TypeError for a wrong dtype, ValueError for a wrong shape or device (the kernels take what they are handed as f32 /
+    int32 words on the device).  The VALUES of offsets are checked (ascending, within [0, P]) only when they come from the host:
+    reading a device tensor would synchronise.  Under malformed device offsets the call stays inside its buffers and silently skips
+    the rows no frame owns (include/mv3d_hip.h)."""
+    if isinstance(points, torch.Tensor):
+        if points.dtype != torch.float32:
+            raise TypeError("point_cloud_2_front: points must be float32, got {}".format(points.dtype))
+        if not points.is_cuda:
+            raise ValueError("point_cloud_2_front: a points tensor must live on the device (pass a numpy array to have it uploaded)")
+    else:
+        points = np.asarray(points)
+        if points.dtype != np.float32:
+            raise TypeError("point_cloud_2_front: points must be float32, got {}".format(points.dtype))
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("point_cloud_2_front: points must be (P, 4) [x, y, z, reflectance], got {}".format(tuple(points.shape)))
+    P = int(points.shape[0])
+    shape = FV_SHAPE
+    if offsets is not None:
+        if isinstance(offsets, torch.Tensor):
+            if offsets.dtype != torch.int32:
+                raise TypeError("point_cloud_2_front: an offsets tensor must be int32, got {}".format(offsets.dtype))
+        else:
+            offsets = np.asarray(offsets)
+            if not np.issubdtype(offsets.dtype, np.integer):
+                raise TypeError("point_cloud_2_front: offsets must be integers, got {}".format(offsets.dtype))
+            if offsets.ndim == 1 and offsets.size and (np.any(np.diff(offsets) < 0) or offsets[0] < 0 or offsets[-1] > P):
+                raise ValueError("point_cloud_2_front: offsets must ascend within [0, {}], got {}".format(P, offsets.tolist()))
+        if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
+            raise ValueError("point_cloud_2_front: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(FV_MAX_FRAMES, tuple(offsets.shape)))
+        shape = (int(offsets.shape[0]) - 1,) + FV_SHAPE
+    B = 1 if offsets is None else shape[0]
+    for name, t, dtype in (("out", out, torch.float32), ("workspace", workspace, torch.uint8)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype):
+            raise TypeError("point_cloud_2_front: {} must be a {} tensor".format(name, dtype))
+    # one device for every tensor handed in (a numpy cloud goes where they are; with none of them, to the current device)
+    tensors = [(n, t) for n, t in (("points", points), ("offsets", offsets), ("out", out), ("workspace", workspace)) if isinstance(t, torch.Tensor)]
+    for name, t in tensors:
+        if not t.is_cuda or t.device != tensors[0][1].device:
+            raise ValueError("point_cloud_2_front: {} on {}: every tensor must live on one HIP device".format(name, t.device))
+        if name in ("out", "workspace") and not t.is_contiguous():
+            raise ValueError("point_cloud_2_front: {} must be contiguous".format(name))
+    dev = tensors[0][1].device if tensors else "cuda"
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError("point_cloud_2_front: out must be {}, got {}".format(shape, tuple(out.shape)))
+    need = point_cloud_2_front_workspace_bytes(B)
+    if workspace is not None and workspace.numel() < need:
+        raise ValueError("point_cloud_2_front: workspace of {} bytes, {} needed".format(workspace.numel(), need))
+    pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    off = None                                                # (one frame: the entry takes NULL offsets, nothing to upload)
+    if offsets is not None:
+        off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if workspace is None:
+        workspace = _workspace(need, dev, "fv_raster")
+    check(lib().mv3d_point_cloud_2_front(_ptr(pts), _ptr(off), B, P, _ptr(out), _ptr(workspace), _stream()), "mv3d_point_cloud_2_front")
+    return out
+
+
 def gt_encode(box_cam, cos_sin, inv_rot, tr):
     """box_cam (G,6) f32, cos_sin (G,2) f64, inv_rot (9) f32, tr (12) f32 device tensors -> (corners_cam (G,24),
     corners_lidar (G,24), boxes_3d (G,6), boxes_bv (G,4)) f32 in ONE buffer (pack, views): a host caller fetches it with

@@ -7,7 +7,10 @@ im_info (1,3) = BEV size.  One numpy draw is kept for RNG-stream parity with the
 cfg.TRAIN.SCALES, :22-23, whose result the reference never uses either).  A roidb entry may carry the frame in memory
 ('image' (H,W,3) BGR array, 'lidar_bv' array) instead of 'image_path' / 'lidar_bv_path'; image files are read with
 numpy (.npy) or PIL -- cv2 is not a dependency here.  An entry with `flipped` true (cfg.TRAIN.USE_FLIPPED) returns its two maps as
-device tensors, mirrored left/right by ops.mirror_columns; every other entry returns numpy as the reference does."""
+device tensors, mirrored left/right by ops.mirror_columns; every other entry returns numpy as the reference does.
+
+cfg.FRONT_VIEW_INPUT (not in the reference; default off = the blobs above exactly) adds `lidar_fv_data` (1,64,512,3), the third view's
+input, as a device tensor: see `front_view_blob`."""
 import numpy as np
 import numpy.random as npr
 
@@ -21,6 +24,33 @@ def _read_image_bgr(path):
         return np.load(path)
     from PIL import Image                                    # what cv2.imread returns: uint8 BGR
     return np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
+
+
+def front_view_blob(entry):
+    """`lidar_fv_data` (1,64,512,3) f32 on the device for one roidb entry, from the first of: entry['lidar_fv'], a (64,512,3) map in
+    memory, used as is; entry['velodyne'], a (P,4) [x,y,z,reflectance] array; entry['velodyne_path'], a KITTI `.bin` scan or a `.npy`
+    (utils.read_lidar.load_velodyne) -- a cloud is rasterised by ops.point_cloud_2_front.
+    A `flipped` entry rasterises the cloud with y negated on the host (the mirror of the scene, datasets/mirror.py).  Its map is NOT
+    the column-reversed map of the source frame: the column is floor((45 deg - azimuth) / d_theta), and floor makes the bin edges
+    asymmetric -- a point exactly on an edge belongs to the bin on one fixed side of it before and after the mirror, and azimuth
+    +45 deg is column 0 while -45 deg is column 512, outside the map -- so reversing the columns is not the mirrored scene's raster.
+    An in-memory 'lidar_fv' is the caller's map for that entry and is not touched."""
+    if 'lidar_fv' in entry:
+        fv = ops._dev(entry['lidar_fv'])
+        if tuple(fv.shape) != ops.FV_SHAPE:
+            raise ValueError("entry['lidar_fv'] must be {}, got {}".format(ops.FV_SHAPE, tuple(fv.shape)))
+        return fv[None]
+    if 'velodyne' in entry:
+        pts = np.asarray(entry['velodyne'], np.float32)
+    elif 'velodyne_path' in entry:
+        from ..utils.read_lidar import load_velodyne
+        pts = load_velodyne(entry['velodyne_path'])
+    else:
+        raise ValueError("cfg.FRONT_VIEW_INPUT is on and the roidb entry has none of 'lidar_fv', 'velodyne', 'velodyne_path'")
+    pts = np.ascontiguousarray(pts.reshape(-1, pts.shape[-1])[:, :4])
+    if entry.get('flipped', False):
+        pts = pts * np.array([1, -1, 1, 1], np.float32)      # (a copy: the entry's own array stays)
+    return ops.point_cloud_2_front(pts)[None]
 
 
 def get_minibatch(roidb, num_classes):
@@ -44,4 +74,6 @@ def get_minibatch(roidb, num_classes):
                              "300), this one is {} wide".format(blobs['lidar_bv_data'].shape[2]))
         for k in ('image_data', 'lidar_bv_data'):
             blobs[k] = ops.mirror_columns(ops._dev(blobs[k]))
+    if cfg.FRONT_VIEW_INPUT:
+        blobs['lidar_fv_data'] = front_view_blob(entry)
     return blobs

@@ -10,6 +10,8 @@ def prepare_roidb(imdb):
         entry['image_path'] = imdb.image_path_at(i)
         entry['lidar_bv_path'] = imdb.lidar_path_at(i)
         entry['calib'] = imdb.calib_at(i)
+        if hasattr(imdb, 'velodyne_path_at'):                  # (not in the reference) the scan cfg.FRONT_VIEW_INPUT rasterises
+            entry['velodyne_path'] = imdb.velodyne_path_at(i)
         dense = entry['gt_overlaps'].toarray() if hasattr(entry['gt_overlaps'], 'toarray') else np.asarray(entry['gt_overlaps'])
         entry['max_overlaps'] = dense.max(axis=1) if dense.size else np.zeros((0,), dense.dtype)
         entry['max_classes'] = dense.argmax(axis=1) if dense.size else np.zeros((0,), np.int64)
