@@ -56,6 +56,13 @@ int mv3d_nms_device(const float *dets_dev, int n, double thresh, int max_keep,
                     int32_t *keep_dev, int32_t *num_keep_dev, int32_t *status_dev,
                     void *workspace, size_t workspace_bytes, void *stream);
 
+/* Host only (no device, no environment): the rounds every NMS launch of num_boxes boxes capped at max_keep runs -- the launcher
+ * walks this very plan.  rounds_out receives up to 7 triples (b0, b1, width): the round covers the 64-box column blocks
+ * [b0, b1); width 0 = round 1 (the tiles kernel + the LDS chain), else the later round's kernel width (32, 64 or 128 blocks).
+ * Returns the number of rounds (num_boxes == 0: the one round (0, 0)), or 0 for a count that the launches refuse
+ * (negative, above 32768) or a NULL rounds_out. */
+int mv3d_nms_round_plan(int num_boxes, int max_keep, int32_t *rounds_out);
+
 /* Diagnostics: mv3d_nms_device plus a per-64-box-block trace of the greedy chain,
  * trace_dev[4*b + 0..3] = {cycle at block start, cycle after waiting for the bulk workers,
  * cycle after the diagonal fixed point, (iterations << 32) | kept-in-block}, followed by 8
@@ -728,6 +735,14 @@ int mv3d_conv3x3_views_f32(int num_views, const mv3d_conv_view *views, int c_in,
  * by mv3d_maxpool2x2_*. */
 int mv3d_conv3x3_pool_views_f16(int num_views, const mv3d_conv_view *views, int c_in, int c_out, void *stream);
 int mv3d_conv3x3_pool_views_bf16(int num_views, const mv3d_conv_view *views, int c_in, int c_out, void *stream);
+/* Host only (no device, no environment): the name of the kernel path the entries above select for such a launch -- they launch
+ * what this very selection returns.  operand_bytes 2 = the f16 / bf16 entries, 4 = the f32 entries (f32 maps out whatever
+ * out_f32 says; no pool form); pixels[k] = batch * height * width of view k; gated = a gate_framed is given; pool = the
+ * *_pool_views_* entries.  One of "conv_input", "first_128x128", "first_256x64", "64x128", "128x128", "pp", "256x64",
+ * "pool_128x128", "pool_256x64", "f32_64x128", "f32_128x128", "f32_128x64" (a static string), or NULL where the entries
+ * return MV3D_ERR_INVALID_ARG for the channel counts or the flag combination (or for num_views, a pixel count <= 0). */
+const char *mv3d_conv3x3_path(int operand_bytes, int num_views, const int32_t *pixels, int c_in, int c_out, int out_f32, int gated,
+                              int pool);
 /* The 2x2 pools of several views in one launch.  Forward: x_framed = the map, y_framed = the pooled map (g_pooled_framed unused).
  * Backward (mv3d_maxpool2x2_bwd_*): x_framed = the pre-pool map y, g_pooled_framed = the gradient w.r.t. the pooled map,
  * y_framed = the gradient w.r.t. y's pre-activation (written). */

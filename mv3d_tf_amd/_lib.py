@@ -161,6 +161,7 @@ _SIGS = {
     "mv3d_version": (C.c_int, []),
     "mv3d_status_string": (C.c_char_p, [C.c_int]),
     "mv3d_nms_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "mv3d_nms_round_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "mv3d_nms_device": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_nms_device_trace": (C.c_int, [_P, C.c_int, C.c_double, C.c_int, _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "mv3d_nms_host": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int]),
@@ -258,6 +259,7 @@ _SIGS = {
     "mv3d_conv3x3_views_f32": (C.c_int, [C.c_int, C.POINTER(ConvView), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mv3d_conv3x3_pool_views_f16": (C.c_int, [C.c_int, C.POINTER(ConvView), C.c_int, C.c_int, _P]),
     "mv3d_conv3x3_pool_views_bf16": (C.c_int, [C.c_int, C.POINTER(ConvView), C.c_int, C.c_int, _P]),
+    "mv3d_conv3x3_path": (C.c_char_p, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "mv3d_maxpool2x2_views_f16": (C.c_int, [C.c_int, C.POINTER(PoolView), C.c_int, _P]),
     "mv3d_maxpool2x2_views_bf16": (C.c_int, [C.c_int, C.POINTER(PoolView), C.c_int, _P]),
     "mv3d_maxpool2x2_views_f32": (C.c_int, [C.c_int, C.POINTER(PoolView), C.c_int, _P]),

@@ -676,83 +676,157 @@ __global__ __launch_bounds__(256) void frame_pieces_kernel(const float *__restri
     }
 }
 
-template <typename T, int BM, int BN, int WP, int WC, int STAGES, bool FIRST>
-int launch_conv(ConvGroup &g, int out_f32, hipStream_t s)
-{
-    int grid = 0;
-    for (int k = 0; k < g.n; ++k) {
-        ConvArgs &b = g.v[k];
-        b.m_tiles = (b.M + BM - 1) / BM;
-        b.n_tiles = b.Cout / BN;
-        g.first[k] = grid;
-        grid += (b.m_tiles + 7) / 8 * 8 * b.n_tiles;
-    }
-    for (int k = g.n; k < CONV_MAX_VIEWS; ++k) { g.v[k] = g.v[0]; g.first[k] = grid; }
-    if constexpr (sizeof(T) == 4) {                               // f32 operands: f32 maps only
-        hipLaunchKernelGGL((conv3x3_f16_kernel<T, BM, BN, WP, WC, STAGES, true, FIRST>), dim3(grid), dim3(WP * WC * 64), 0, s, g);
-    } else {
-        if (out_f32)
-            hipLaunchKernelGGL((conv3x3_f16_kernel<T, BM, BN, WP, WC, STAGES, true, FIRST>), dim3(grid), dim3(WP * WC * 64), 0, s, g);
-        else
-            hipLaunchKernelGGL((conv3x3_f16_kernel<T, BM, BN, WP, WC, STAGES, false, FIRST>), dim3(grid), dim3(WP * WC * 64), 0, s, g);
-    }
-    return mv3d_launch_status();
-}
-
-// 16-bit output only (tiles whose f32 output image would not fit the LDS)
-template <typename T, int BM, int BN, int WP, int WC>
-int launch_conv16(ConvGroup &g, hipStream_t s)
-{
-    int grid = 0;
-    for (int k = 0; k < g.n; ++k) {
-        ConvArgs &b = g.v[k];
-        b.m_tiles = (b.M + BM - 1) / BM;
-        b.n_tiles = b.Cout / BN;
-        g.first[k] = grid;
-        grid += (b.m_tiles + 7) / 8 * 8 * b.n_tiles;
-    }
-    for (int k = g.n; k < CONV_MAX_VIEWS; ++k) { g.v[k] = g.v[0]; g.first[k] = grid; }
-    hipLaunchKernelGGL((conv3x3_f16_kernel<T, BM, BN, WP, WC, 2, false, false>), dim3(grid), dim3(WP * WC * 64), 0, s, g);
-    return mv3d_launch_status();
-}
-
-// the wave-specialised 256 x 256 workgroup (conv3x3_pp_kernel): 16-bit framed / bare output, ordinary layers
-template <typename T>
-int launch_conv_pp(ConvGroup &g, hipStream_t s)
-{
-    int grid = 0;
-    for (int k = 0; k < g.n; ++k) {
-        ConvArgs &b = g.v[k];
-        b.m_tiles = (b.M + 255) / 256;
-        b.n_tiles = b.Cout / 256;
-        g.first[k] = grid;
-        grid += (b.m_tiles + 7) / 8 * 8 * b.n_tiles;
-    }
-    for (int k = g.n; k < CONV_MAX_VIEWS; ++k) { g.v[k] = g.v[0]; g.first[k] = grid; }
-    hipLaunchKernelGGL((conv3x3_pp_kernel<T>), dim3(grid), dim3(512), 0, s, g);
-    return mv3d_launch_status();
-}
-
-template <typename T, int BM, int BN, int WP, int WC>
-int launch_conv_pool(ConvGroup &g, hipStream_t s)
-{
-    int grid = 0;
-    for (int k = 0; k < g.n; ++k) {
-        ConvArgs &b = g.v[k];
-        b.Ho = b.H / 2; b.Wo = b.W / 2;
-        b.xtiles = (2 * b.Wo + BM / 2 - 1) / (BM / 2);
-        b.m_tiles = b.Bn * b.Ho * b.xtiles;
-        b.n_tiles = b.Cout / BN;
-        g.first[k] = grid;
-        grid += (b.m_tiles + 7) / 8 * 8 * b.n_tiles;
-    }
-    for (int k = g.n; k < CONV_MAX_VIEWS; ++k) { g.v[k] = g.v[0]; g.first[k] = grid; }
-    hipLaunchKernelGGL((conv3x3_f16_kernel<T, BM, BN, WP, WC, 2, false, false, true>), dim3(grid), dim3(WP * WC * 64), 0, s, g);
-    return mv3d_launch_status();
-}
-
 }  // namespace mv3d_conv
 using namespace mv3d_conv;
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Which kernel a launch gets.  conv_select() is the whole decision, on plain values; the entries launch what it returns and
+// mv3d_conv3x3_path() reports it by the name below.
+enum ConvPath {
+    CONV_REFUSED = 0,                                             // channel counts / flags no entry accepts
+    CONV_INPUT, CONV_FIRST_128x128, CONV_FIRST_256x64,            // c_in == 16: conv_input.hip's kernel / the FIRST tiles
+    CONV_64x128, CONV_128x128, CONV_PP, CONV_256x64,
+    CONV_POOL_128x128, CONV_POOL_256x64,
+    CONV_F32_64x128, CONV_F32_128x128, CONV_F32_128x64,
+    CONV_X256x256_2x4, CONV_X256x256_4x2, CONV_X256x128_2x2, CONV_X256x128_4x2   // two-stage big tiles: experiment builds only
+};
+static const char *const CONV_PATH_NAMES[] = {
+    nullptr, "conv_input", "first_128x128", "first_256x64", "64x128", "128x128", "pp", "256x64", "pool_128x128", "pool_256x64",
+    "f32_64x128", "f32_128x128", "f32_128x64", "x256x256_2x4", "x256x256_4x2", "x256x128_2x2", "x256x128_4x2"};
+
+#define CONV_FIRST_CIN 16         // c_in of the input layer's packing (see the header)
+struct ConvThresholds {
+    // 16-bit operands, fewer than this many 128 x 128 tiles (one frame: 184 tiles of conv4_x / conv5_x on 512 workgroup slots):
+    // half-height tiles put twice as many CUs to work -- the latency of a batch-1 frame (BASELINE configs[1]) is these layers'
+    // tile time, not their throughput
+    int small_max;
+    // at least this many 256 x 256 tiles and 16-bit maps out: 256 x 256 workgroups of 8 waves, each wave a 128-pixel x 64-cout
+    // tile, with the wave-specialised K loop (conv3x3_pp_kernel) -- per matrix instruction half the DMA pieces and 3/4 of the LDS
+    // operand reads of the 128 x 128 / 64 x 64 form (one workgroup per CU: 128 KB of LDS).  Batch-16 serving layers: conv4_2
+    // 954 -> 1063 TFLOP/s, conv3_2 848 -> 911, image conv4_2 988 -> 1020; needs enough tiles for several rounds of 256
+    // workgroups (a training batch keeps the 128 x 128 form).
+    int big_min;
+    // f32 operands, fewer than this many 128 x 128 tiles (a training batch): the f32 kernel is MFMA-bound even with one wave per
+    // SIMD, so a CU that holds two workgroups just takes twice as long -- half-size tiles balance the last round (fp32 training
+    // step on one stream 58.7 -> 56 ms)
+    int f32_small_max;
+};
+constexpr ConvThresholds CONV_THRESHOLDS = {512, 640, 1024};
+
+// es: operand bytes (2 = f16 / bf16, 4 = f32: f32 maps in and out whatever out_f32 says); M[k] = batch * height * width of view k
+static ConvPath conv_select(int es, int n, const int *M, int c_in, int c_out, bool out_f32, bool gated, bool pool, const ConvThresholds &t)
+{
+    if ((es != 2 && es != 4) || n <= 0 || n > CONV_MAX_VIEWS || c_in <= 0 || c_out <= 0 || c_out % 64) return CONV_REFUSED;
+    long tiles128 = 0, tiles256 = 0;
+    for (int k = 0; k < n; ++k) {
+        if (M[k] <= 0) return CONV_REFUSED;
+        tiles128 += (long)((M[k] + 127) / 128) * (c_out / 128);
+        tiles256 += (long)((M[k] + 255) / 256) * (c_out / 256);
+    }
+    if (es == 4) {                                                // (no pool epilogue on f32 maps)
+        if (c_in % 32 || pool) return CONV_REFUSED;
+        if (c_out % 128) return CONV_F32_128x64;
+        return tiles128 < t.f32_small_max ? CONV_F32_64x128 : CONV_F32_128x128;
+    }
+    if (pool) {                                                   // the pooled map is 16-bit, framed, ungated, of an ordinary layer
+        if (c_in % 64 || out_f32 || gated) return CONV_REFUSED;
+        return c_out % 128 == 0 ? CONV_POOL_128x128 : CONV_POOL_256x64;
+    }
+    if (gated && out_f32) return CONV_REFUSED;
+    if (c_in == CONV_FIRST_CIN) {
+        if (c_out == 64 && !out_f32 && !gated) return CONV_INPUT;
+        return c_out % 128 == 0 ? CONV_FIRST_128x128 : CONV_FIRST_256x64;
+    }
+    if (c_in % 64) return CONV_REFUSED;
+    if (c_out % 128) return CONV_256x64;
+    // 128x128 / 4 waves / 2 stages, two workgroups per CU.  (256x128 / 8 waves / 3 stages, one workgroup per CU with the DMA two
+    // steps ahead, measured equal on the 512-channel layers and 3-5 % slower on the 128 / 256-channel ones: profiles/r03_conv_mfma.txt)
+    if (tiles128 < t.small_max) return CONV_64x128;
+    if (!out_f32 && c_out % 256 == 0 && tiles256 >= t.big_min) return CONV_PP;
+    return CONV_128x128;
+}
+
+// the shipped decision: conv_select() at CONV_THRESHOLDS.  Experiment builds read their hooks here, once: two thresholds, and
+// overrides of the selected path by the variant a hook names.
+static ConvPath conv_path(int es, int n, const int *M, int c_in, int c_out, bool out_f32, bool gated, bool pool)
+{
+#ifdef MV3D_TUNING
+    static const auto env = [](const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; };
+    static const ConvThresholds t = {env("MV3D_CONV_SMALL_MAX", CONV_THRESHOLDS.small_max), env("MV3D_CONV_BIG_MIN", CONV_THRESHOLDS.big_min),
+                                     CONV_THRESHOLDS.f32_small_max};
+    static const int input = env("MV3D_CONV_INPUT", 1), pp = env("MV3D_CONV_PP", 1), big_wp = env("MV3D_CONV_BIG_WP", 2);
+    static const int big = env("MV3D_CONV_TILE", 0);
+    const ConvPath p = conv_select(es, n, M, c_in, c_out, out_f32, gated, pool, t);
+    if (p == CONV_INPUT && !input) return CONV_FIRST_256x64;                      // the input layer on the FIRST tile
+    if (p == CONV_PP && !pp) return big_wp == 2 ? CONV_X256x256_2x4 : CONV_X256x256_4x2;   // the pp tile with the two-stage K loop
+    if (p == CONV_128x128 && !out_f32) {                          // the 256 x 256 workgroup, 8 waves of 128 x 64; 256 x 128
+        if (big == 256 && c_out % 256 == 0) return CONV_X256x256_2x4;
+        if (big == 2561) return CONV_X256x128_2x2;
+        if (big == 2562) return CONV_X256x128_4x2;
+    }
+    return p;
+#else
+    return conv_select(es, n, M, c_in, c_out, out_f32, gated, pool, CONV_THRESHOLDS);
+#endif
+}
+
+// lays out the grid of a path's tile over the views and launches its kernel (every path but CONV_INPUT, which has its own launcher)
+template <typename T>
+static int launch_conv(ConvPath path, ConvGroup &g, bool out_f32, hipStream_t s)
+{
+    // bm x bn: pixels x couts of a workgroup.  pool: an M tile is two map rows x bm / 2 columns (complete pooling windows)
+    auto go = [&](void (*kernel)(const ConvGroup), int bm, int bn, int threads, bool pool) {
+        int grid = 0;
+        for (int k = 0; k < g.n; ++k) {
+            ConvArgs &b = g.v[k];
+            if (pool) {
+                b.Ho = b.H / 2; b.Wo = b.W / 2;
+                b.xtiles = (2 * b.Wo + bm / 2 - 1) / (bm / 2);
+                b.m_tiles = b.Bn * b.Ho * b.xtiles;
+            } else {
+                b.m_tiles = (b.M + bm - 1) / bm;
+            }
+            b.n_tiles = b.Cout / bn;
+            g.first[k] = grid;
+            grid += (b.m_tiles + 7) / 8 * 8 * b.n_tiles;
+        }
+        for (int k = g.n; k < CONV_MAX_VIEWS; ++k) { g.v[k] = g.v[0]; g.first[k] = grid; }
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), 0, s, g);
+    };
+#define CONV_TILE(BM, BN, WP, WC, OUT_F32, FIRST, POOL) \
+    go(conv3x3_f16_kernel<T, BM, BN, WP, WC, 2, OUT_F32, FIRST, POOL>, BM, BN, WP * WC * 64, POOL)
+#define CONV_TILE_OUT(BM, BN, WP, WC, FIRST) \
+    (out_f32 ? CONV_TILE(BM, BN, WP, WC, true, FIRST, false) : CONV_TILE(BM, BN, WP, WC, false, FIRST, false))
+    if constexpr (sizeof(T) == 4) {                               // f32 operands: f32 maps only
+        switch (path) {
+        case CONV_F32_64x128: CONV_TILE(64, 128, 2, 2, true, false, false); break;
+        case CONV_F32_128x128: CONV_TILE(128, 128, 2, 2, true, false, false); break;
+        case CONV_F32_128x64: CONV_TILE(128, 64, 2, 2, true, false, false); break;
+        default: return MV3D_ERR_INVALID_ARG;
+        }
+    } else {
+        switch (path) {
+        case CONV_FIRST_128x128: CONV_TILE_OUT(128, 128, 2, 2, true); break;
+        case CONV_FIRST_256x64: CONV_TILE_OUT(256, 64, 4, 1, true); break;
+        case CONV_64x128: CONV_TILE_OUT(64, 128, 2, 2, false); break;
+        case CONV_128x128: CONV_TILE_OUT(128, 128, 2, 2, false); break;
+        case CONV_256x64: CONV_TILE_OUT(256, 64, 4, 1, false); break;
+        case CONV_PP: go(conv3x3_pp_kernel<T>, 256, 256, 512, false); break;
+        case CONV_POOL_128x128: CONV_TILE(128, 128, 2, 2, false, false, true); break;
+        case CONV_POOL_256x64: CONV_TILE(256, 64, 4, 1, false, false, true); break;
+#ifdef MV3D_TUNING                                                // 16-bit output only (their f32 output image would not fit the LDS)
+        case CONV_X256x256_2x4: CONV_TILE(256, 256, 2, 4, false, false, false); break;
+        case CONV_X256x256_4x2: CONV_TILE(256, 256, 4, 2, false, false, false); break;
+        case CONV_X256x128_2x2: CONV_TILE(256, 128, 2, 2, false, false, false); break;
+        case CONV_X256x128_4x2: CONV_TILE(256, 128, 4, 2, false, false, false); break;
+#endif
+        default: return MV3D_ERR_INVALID_ARG;
+        }
+    }
+#undef CONV_TILE_OUT
+#undef CONV_TILE
+    return mv3d_launch_status();
+}
 
 // fills one view's arguments; false = invalid
 static bool conv_view_args(ConvArgs &a, const mv3d_conv_view &w, int c_in, int c_out, int out_framed, int out_f32, int relu, int es, bool first,
@@ -772,90 +846,30 @@ static bool conv_view_args(ConvArgs &a, const mv3d_conv_view &w, int c_in, int c
     return true;
 }
 
-template <typename T>
+// Every convolution entry: T = the operand type (float: the exact-f32 variant, f32 framed maps and an f32 gate), POOL = convolution +
+// bias + ReLU + 2x2 max pool, y = the POOLED framed map (batch, height / 2 + 2, width / 2 + 2, c_out)
+template <typename T, bool POOL = false>
 static int conv3x3_views_entry(int num_views, const mv3d_conv_view *views, int c_in, int c_out, int out_framed, int out_f32, int relu, void *stream)
 {
     if (num_views <= 0 || num_views > CONV_MAX_VIEWS || !views) return MV3D_ERR_INVALID_ARG;
-    const bool first = c_in == 16;                                // the input layer's packing (see the header)
-    if (c_in <= 0 || (c_in % 64 && !first) || c_out <= 0 || c_out % 64) return MV3D_ERR_INVALID_ARG;
     const bool gated = views[0].gate_framed != nullptr;
-    if (gated && (!out_framed || out_f32)) return MV3D_ERR_INVALID_ARG;
+    if (gated && !out_framed) return MV3D_ERR_INVALID_ARG;
     ConvGroup g;
     g.n = num_views;
-    for (int k = 0; k < num_views; ++k)
-        if (!conv_view_args(g.v[k], views[k], c_in, c_out, out_framed, out_f32, relu, 2, first, gated)) return MV3D_ERR_INVALID_ARG;
+    int M[CONV_MAX_VIEWS];
+    for (int k = 0; k < num_views; ++k) {
+        if (POOL && (views[k].height < 2 || views[k].width < 2)) return MV3D_ERR_INVALID_ARG;
+        if (!conv_view_args(g.v[k], views[k], c_in, c_out, out_framed, out_f32, relu, sizeof(T), c_in == CONV_FIRST_CIN, gated)) return MV3D_ERR_INVALID_ARG;
+        M[k] = g.v[k].M;
+    }
     hipStream_t s = (hipStream_t)stream;
-#ifdef MV3D_TUNING
-    static const int input_env = getenv("MV3D_CONV_INPUT") ? atoi(getenv("MV3D_CONV_INPUT")) : 1;
-#else
-    const int input_env = 1;
-#endif
-    if (first && c_out == 64 && !out_f32 && !gated && input_env) {   // the input layer's own kernel (conv_input.hip)
+    const ConvPath path = conv_path(sizeof(T), num_views, M, c_in, c_out, out_f32 != 0, gated, POOL);
+    if (path == CONV_REFUSED) return MV3D_ERR_INVALID_ARG;
+    if constexpr (sizeof(T) == 2) if (path == CONV_INPUT) {       // the input layer's own kernel (conv_input.hip)
         if constexpr (__is_same(T, _Float16)) return mv3d_launch_conv_input_f16(num_views, views, out_framed, relu, s);
         else return mv3d_launch_conv_input_bf16(num_views, views, out_framed, relu, s);
     }
-    if (first) return c_out % 128 == 0 ? launch_conv<T, 128, 128, 2, 2, 2, true>(g, out_f32, s) : launch_conv<T, 256, 64, 4, 1, 2, true>(g, out_f32, s);
-    // 128x128 / 4 waves / 2 stages, two workgroups per CU.  (256x128 / 8 waves / 3 stages, one workgroup per CU with the DMA two
-    // steps ahead, measured equal on the 512-channel layers and 3-5 % slower on the 128 / 256-channel ones: profiles/r03_conv_mfma.txt)
-    if (c_out % 128 == 0) {
-        // few tiles (one frame: 184 tiles of conv4_x / conv5_x on 512 workgroup slots): half-height tiles put twice as many CUs to
-        // work -- the latency of a batch-1 frame (BASELINE configs[1]) is these layers' tile time, not their throughput
-        long tiles128 = 0;
-        for (int k = 0; k < num_views; ++k) tiles128 += (long)((g.v[k].M + 127) / 128) * (c_out / 128);
-#ifdef MV3D_TUNING
-        static const int small_max = getenv("MV3D_CONV_SMALL_MAX") ? atoi(getenv("MV3D_CONV_SMALL_MAX")) : 512;
-#else
-        const int small_max = 512;
-#endif
-        if (tiles128 < small_max) return launch_conv<T, 64, 128, 2, 2, 2, false>(g, out_f32, s);
-        // many tiles and 16-bit maps out: 256 x 256 workgroups of 8 waves, each wave a 128-pixel x 64-cout tile -- per matrix
-        // instruction half the DMA pieces and 3/4 of the LDS operand reads of the 128 x 128 / 64 x 64 form (one workgroup per CU:
-        // 128 KB of LDS).  Batch-16 serving layers: conv4_2 954 -> 1063 TFLOP/s, conv3_2 848 -> 911, image conv4_2 988 -> 1020;
-        // needs enough tiles for several rounds of 256 workgroups (a training batch keeps the 128 x 128 form).
-        long tiles256 = 0;
-        for (int k = 0; k < num_views; ++k) tiles256 += (long)((g.v[k].M + 255) / 256) * (c_out / 256);
-#ifdef MV3D_TUNING
-        static const int big_min = getenv("MV3D_CONV_BIG_MIN") ? atoi(getenv("MV3D_CONV_BIG_MIN")) : 640;
-        static const int big_wp = getenv("MV3D_CONV_BIG_WP") ? atoi(getenv("MV3D_CONV_BIG_WP")) : 2;
-#else
-        const int big_min = 640, big_wp = 2;
-#endif
-        if (!out_f32 && c_out % 256 == 0 && tiles256 >= big_min) {
-#ifdef MV3D_TUNING
-            static const int pp = getenv("MV3D_CONV_PP") ? atoi(getenv("MV3D_CONV_PP")) : 1;
-#else
-            const int pp = 1;
-#endif
-            // the same tile with the wave-specialised K loop (two groups of four waves one barrier interval apart, counted waits)
-            if (pp) return launch_conv_pp<T>(g, s);
-            return big_wp == 2 ? launch_conv16<T, 256, 256, 2, 4>(g, s) : launch_conv16<T, 256, 256, 4, 2>(g, s);
-        }
-#ifdef MV3D_TUNING                                                // experiment builds: the 256 x 256 workgroup, 8 waves of 128 x 64
-        static const int big = getenv("MV3D_CONV_TILE") ? atoi(getenv("MV3D_CONV_TILE")) : 0;
-        if (big == 256 && c_out % 256 == 0 && !out_f32) return launch_conv16<T, 256, 256, 2, 4>(g, s);
-        if (big == 2561 && c_out % 128 == 0 && !out_f32) return launch_conv16<T, 256, 128, 2, 2>(g, s);
-        if (big == 2562 && c_out % 128 == 0 && !out_f32) return launch_conv16<T, 256, 128, 4, 2>(g, s);
-#endif
-        return launch_conv<T, 128, 128, 2, 2, 2, false>(g, out_f32, s);
-    }
-    return launch_conv<T, 256, 64, 4, 1, 2, false>(g, out_f32, s);
-}
-
-// convolution + bias + ReLU + 2x2 max pool: y = the POOLED framed map (batch, height / 2 + 2, width / 2 + 2, c_out)
-template <typename T>
-static int conv3x3_pool_views_entry(int num_views, const mv3d_conv_view *views, int c_in, int c_out, void *stream)
-{
-    if (num_views <= 0 || num_views > CONV_MAX_VIEWS || !views) return MV3D_ERR_INVALID_ARG;
-    if (c_in <= 0 || c_in % 64 || c_out <= 0 || c_out % 64) return MV3D_ERR_INVALID_ARG;
-    ConvGroup g;
-    g.n = num_views;
-    for (int k = 0; k < num_views; ++k) {
-        if (views[k].height < 2 || views[k].width < 2 || views[k].gate_framed) return MV3D_ERR_INVALID_ARG;
-        if (!conv_view_args(g.v[k], views[k], c_in, c_out, 1, 0, 1, 2, false, false)) return MV3D_ERR_INVALID_ARG;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (c_out % 128 == 0) return launch_conv_pool<T, 128, 128, 2, 2>(g, s);
-    return launch_conv_pool<T, 256, 64, 4, 1>(g, s);
+    return launch_conv<T>(path, g, out_f32 != 0, s);
 }
 
 template <typename T>
@@ -868,35 +882,11 @@ static int conv3x3_entry(const void *x_framed, const void *w_packed, const float
     return conv3x3_views_entry<T>(1, &w, c_in, c_out, out_framed, out_f32, relu, stream);
 }
 
-// exact-f32 variant: f32 framed activations (c_in a multiple of 32), f32 packed weights, f32 output
-static int conv3x3_f32_views_entry(int num_views, const mv3d_conv_view *views, int c_in, int c_out, int out_framed, int relu, void *stream)
+extern "C" const char *mv3d_conv3x3_path(int operand_bytes, int num_views, const int32_t *pixels, int c_in, int c_out, int out_f32, int gated,
+                                         int pool)
 {
-    if (num_views <= 0 || num_views > CONV_MAX_VIEWS || !views) return MV3D_ERR_INVALID_ARG;
-    if (c_in <= 0 || c_in % 32 || c_out <= 0 || c_out % 64) return MV3D_ERR_INVALID_ARG;
-    const bool gated = views[0].gate_framed != nullptr;          // (an f32 gate map, framed like the output)
-    if (gated && !out_framed) return MV3D_ERR_INVALID_ARG;
-    ConvGroup g;
-    g.n = num_views;
-    long tiles128 = 0;
-    for (int k = 0; k < num_views; ++k) {
-        if (!conv_view_args(g.v[k], views[k], c_in, c_out, out_framed, 1, relu, 4, false, gated)) return MV3D_ERR_INVALID_ARG;
-        tiles128 += (long)((g.v[k].M + 127) / 128) * (c_out / 128);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    // few tiles (a training batch): the f32 kernel is MFMA-bound even with one wave per SIMD, so a CU that holds two workgroups
-    // just takes twice as long -- half-size tiles balance the last round (fp32 training step on one stream 58.7 -> 56 ms)
-    if (c_out % 128 == 0 && tiles128 < 1024) return launch_conv<float, 64, 128, 2, 2, 2, false>(g, 1, s);
-    if (c_out % 128 == 0) return launch_conv<float, 128, 128, 2, 2, 2, false>(g, 1, s);
-    return launch_conv<float, 128, 64, 2, 2, 2, false>(g, 1, s);
-}
-
-static int conv3x3_f32_entry(const void *x_framed, const void *w_packed, const float *bias, void *y, int batch, int height, int width, int c_in,
-                             int c_out, int out_framed, int relu, void *stream)
-{
-    mv3d_conv_view w;
-    w.x_framed = x_framed; w.w_packed = w_packed; w.bias = bias; w.gate_framed = nullptr; w.y = y;
-    w.batch = batch; w.height = height; w.width = width; w.reserved0 = 0;
-    return conv3x3_f32_views_entry(1, &w, c_in, c_out, out_framed, relu, stream);
+    if (!pixels) return nullptr;
+    return CONV_PATH_NAMES[conv_path(operand_bytes, num_views, pixels, c_in, c_out, out_f32 != 0, gated != 0, pool != 0)];
 }
 
 // x = the map to pool (forward) / the pre-pool map y (backward); g = gradient w.r.t. the pooled map (backward only)
@@ -972,7 +962,7 @@ extern "C" int mv3d_conv3x3_gated_bf16(const void *x, const void *w, const float
 extern "C" int mv3d_conv3x3_f32(const void *x, const void *w, const float *bias, void *y, int batch, int height, int width, int c_in, int c_out,
                                 int out_framed, int relu, void *stream)
 {
-    return conv3x3_f32_entry(x, w, bias, y, batch, height, width, c_in, c_out, out_framed, relu, stream);
+    return conv3x3_entry<float>(x, w, bias, y, batch, height, width, c_in, c_out, out_framed, 1, relu, stream);
 }
 extern "C" int mv3d_conv3x3_views_f16(int num_views, const mv3d_conv_view *views, int c_in, int c_out, int out_framed, int out_f32, int relu,
                                       void *stream)
@@ -986,15 +976,15 @@ extern "C" int mv3d_conv3x3_views_bf16(int num_views, const mv3d_conv_view *view
 }
 extern "C" int mv3d_conv3x3_views_f32(int num_views, const mv3d_conv_view *views, int c_in, int c_out, int out_framed, int relu, void *stream)
 {
-    return conv3x3_f32_views_entry(num_views, views, c_in, c_out, out_framed, relu, stream);
+    return conv3x3_views_entry<float>(num_views, views, c_in, c_out, out_framed, 1, relu, stream);
 }
 extern "C" int mv3d_conv3x3_pool_views_f16(int num_views, const mv3d_conv_view *views, int c_in, int c_out, void *stream)
 {
-    return conv3x3_pool_views_entry<_Float16>(num_views, views, c_in, c_out, stream);
+    return conv3x3_views_entry<_Float16, true>(num_views, views, c_in, c_out, 1, 0, 1, stream);
 }
 extern "C" int mv3d_conv3x3_pool_views_bf16(int num_views, const mv3d_conv_view *views, int c_in, int c_out, void *stream)
 {
-    return conv3x3_pool_views_entry<__bf16>(num_views, views, c_in, c_out, stream);
+    return conv3x3_views_entry<__bf16, true>(num_views, views, c_in, c_out, 1, 0, 1, stream);
 }
 extern "C" int mv3d_maxpool2x2_f32(const void *x, void *y, int batch, int height, int width, int channels, void *stream)
 {

@@ -782,6 +782,29 @@ size_t mv3d_nms_ws_bytes(int n_cap, int batch)
            mv3d_align_up((size_t)batch * 4 * 4);
 }
 
+// Rounds over column-block ranges [b0, b1) of a frame of nbw blocks; a later round returns at once for a frame that is already
+// finished (a frame with no boxes is finished by the first round).  The first round is 32 blocks: the greedy pass almost always
+// reaches a small max_keep (TEST: 300) inside it and the rest is one skipped launch.  A large or absent max_keep (TRAIN: 2000 =
+// at least 32 blocks) gets narrow later rounds, so that the chain only ever pulls the tiles of its own round and little is
+// computed past the stopping point.  width: 0 = round 1 (nms_tiles_kernel + nms_chain_lds_kernel), else the later round's
+// nms_round_kernel<width> (a later round is at most 128 blocks wide: chain1_round<128>).
+struct NmsRound { int b0, b1, width; };
+#define NMS_MAX_ROUNDS 7
+static int nms_round_plan(int nbw, int max_keep, NmsRound *rounds)
+{
+    int bounds[NMS_MAX_ROUNDS + 1] = {0, 32, nbw, nbw, nbw, nbw, nbw, nbw};
+    if (max_keep <= 0 || max_keep > 512) { bounds[2] = 64; bounds[3] = 128; bounds[4] = 256; bounds[5] = 384; bounds[6] = nbw; }
+    else if (nbw > 128) { bounds[2] = 128; bounds[3] = 256; bounds[4] = 384; bounds[5] = nbw; }
+    int n = 0;
+    for (int r = 0; r < NMS_MAX_ROUNDS; ++r) {
+        const int b0 = bounds[r] < nbw ? bounds[r] : nbw, b1 = bounds[r + 1] < nbw ? bounds[r + 1] : nbw;
+        if (r > 0 && b0 >= b1) break;
+        const int w = b1 - b0;
+        rounds[n++] = {b0, b1, r == 0 ? 0 : w <= 32 ? 32 : w <= 64 ? 64 : 128};
+    }
+    return n;
+}
+
 int mv3d_launch_nms(const NmsLaunch &L, hipStream_t stream)
 {
     if (L.n_cap < 0 || L.batch <= 0) return MV3D_ERR_INVALID_ARG;
@@ -805,19 +828,11 @@ int mv3d_launch_nms(const NmsLaunch &L, hipStream_t stream)
     d.keep = L.keep; d.keep_frame_stride = L.keep_frame_stride; d.num_keep = L.num_keep; d.status = L.status;
     d.emit = L.emit;
     d.trace = L.trace;
-    // Rounds over column-block ranges; a later round returns at once for a frame that is already finished
-    // (a frame with no boxes is finished by the first round).  The first round is 32 blocks: the greedy pass
-    // almost always reaches a small max_keep (TEST: 300) inside it and the rest is one skipped launch.  A
-    // large or absent max_keep (TRAIN: 2000 = at least 32 blocks) gets narrow later rounds, so that the
-    // chain only ever pulls the tiles of its own round and little is computed past the stopping point.
-    // (a later round is at most 128 blocks wide: chain1_round<128>)
-    int bounds[8] = {0, 32, nbw, nbw, nbw, nbw, nbw, nbw};
-    if (L.max_keep <= 0 || L.max_keep > 512) { bounds[2] = 64; bounds[3] = 128; bounds[4] = 256; bounds[5] = 384; bounds[6] = nbw; }
-    else if (nbw > 128) { bounds[2] = 128; bounds[3] = 256; bounds[4] = 384; bounds[5] = nbw; }
-    for (int r = 0; r < 7; ++r) {
-        d.b0 = bounds[r] < nbw ? bounds[r] : nbw; d.b1 = bounds[r + 1] < nbw ? bounds[r + 1] : nbw;
+    NmsRound rounds[NMS_MAX_ROUNDS];
+    const int nr = nms_round_plan(nbw, L.max_keep, rounds);
+    for (int r = 0; r < nr; ++r) {
+        d.b0 = rounds[r].b0; d.b1 = rounds[r].b1;
         d.first_round = (r == 0);
-        if (r > 0 && d.b0 >= d.b1) break;
         const int ntr = d.b1 * (d.b1 + 1) / 2 - d.b0 * (d.b0 + 1) / 2;
         if (r == 0) {
             if (ntr > 0) hipLaunchKernelGGL(nms_tiles_kernel, dim3(ntr, 1, L.batch), dim3(256), 0, stream, d);
@@ -825,10 +840,11 @@ int mv3d_launch_nms(const NmsLaunch &L, hipStream_t stream)
             continue;
         }
         const int wgs = (ntr + 3) / 4 < 256 ? (ntr + 3) / 4 : 256;
-        const int width = d.b1 - d.b0;                         // <= 128 by construction
-        if (width <= 32) hipLaunchKernelGGL(nms_round_kernel<32>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d);
-        else if (width <= 64) hipLaunchKernelGGL(nms_round_kernel<64>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d);
-        else hipLaunchKernelGGL(nms_round_kernel<128>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d);
+        switch (rounds[r].width) {
+        case 32: hipLaunchKernelGGL(nms_round_kernel<32>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d); break;
+        case 64: hipLaunchKernelGGL(nms_round_kernel<64>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d); break;
+        default: hipLaunchKernelGGL(nms_round_kernel<128>, dim3(wgs, 1, L.batch), dim3(256), 0, stream, d);
+        }
     }
     return mv3d_launch_status();
 }
@@ -852,6 +868,15 @@ extern "C" size_t mv3d_nms_workspace_bytes(int max_boxes)
 {
     if (max_boxes < 0 || (max_boxes + 63) / 64 > NMS_MAX_WORDS) return 0;
     return mv3d_nms_ws_bytes(max_boxes, 1);
+}
+
+extern "C" int mv3d_nms_round_plan(int num_boxes, int max_keep, int32_t *rounds_out)
+{
+    if (num_boxes < 0 || (num_boxes + 63) / 64 > NMS_MAX_WORDS || !rounds_out) return 0;
+    NmsRound rounds[NMS_MAX_ROUNDS];
+    const int nr = nms_round_plan((num_boxes + 63) / 64, max_keep, rounds);
+    for (int r = 0; r < nr; ++r) { rounds_out[3 * r] = rounds[r].b0; rounds_out[3 * r + 1] = rounds[r].b1; rounds_out[3 * r + 2] = rounds[r].width; }
+    return nr;
 }
 
 static int nms_device_impl(const float *dets_dev, int n, double thresh, int max_keep, int32_t *keep_dev,

@@ -2,8 +2,11 @@
 select it, against a float64 reference that cannot share the kernels' bugs.
 
 The host code picks a kernel by the launch's tile count.  `select_path` below restates those rules and constants; every case of the
-table names the path it is meant to reach and asserts that the restatement sends it there, and `test_selection_constants_match_the_sources`
-(no GPU) reads the constants out of the .hip sources, so that a retuned threshold cannot silently move a case to another path.
+table names the path it is meant to reach and asserts that the restatement sends it there.  The library answers for itself:
+`mv3d_conv3x3_path` (host only) returns the selection the launch entries call, and `test_the_library_selects_what_the_rules_say`
+(no GPU) compares it with the restatement for every case and from both sides of every threshold, so that a retuned threshold cannot
+silently move a case to another path; every GPU case asks it again before it launches.  Only the weight gradient's constants, whose
+plan depends on the device, are still read out of its .hip source (`test_selection_constants_match_the_sources`).
 
 Two kinds of operands:
   * exact integers: x in {0..7} (non-negative, as after a ReLU), w in {-1..3} (positively biased), integer biases, dy in {-1..2},
@@ -18,6 +21,7 @@ Two kinds of operands:
 
 The reference is nine shifted float64 GEMMs (rocBLAS dgemm on the device, not MIOpen), a frame chunk at a time.  Every output's
 interior is NaN before the launch (a skipped tile stays NaN), and its frame must stay zero (the next layer reads it as padding)."""
+import ctypes as C
 import os
 import re
 import zlib
@@ -145,25 +149,104 @@ def _source(name):
         return re.sub(r"\s+", " ", f.read())
 
 
+def refused(dt, cin, cout, out_f32=False, gated=False, pool=False):
+    """the channel counts and flag combinations the launch entries answer with MV3D_ERR_INVALID_ARG"""
+    if cin <= 0 or cout <= 0 or cout % 64:
+        return True
+    if dt == "f32":
+        return cin % 32 != 0 or pool                            # (no f32 pool entry; f32 maps out whatever out_f32 says)
+    if pool:
+        return cin % 64 != 0 or out_f32 or gated
+    return (cin % 64 != 0 and cin != FIRST_CIN) or (gated and out_f32)
+
+
+@pytest.fixture(scope="module")
+def hiplib():
+    from mv3d_tf_amd import build
+    build.build()
+    from mv3d_tf_amd import _lib
+    return _lib.lib()
+
+
+def library_path(L, dt, Ms, cin, cout, out_f32=False, gated=False, pool=False):
+    """what the library decides for such a launch: mv3d_conv3x3_path (host only; the selection the launch entries themselves call)
+    plus this file's output tag; None = refused"""
+    name = L.mv3d_conv3x3_path(4 if dt == "f32" else 2, len(Ms), (C.c_int32 * max(1, len(Ms)))(*Ms), cin, cout, int(out_f32), int(gated), int(pool))
+    if name is None:
+        return None
+    tagged = dt != "f32" and not pool                           # (as select_path tags)
+    return name.decode() + (("_f32out" if out_f32 else "") + ("_gated" if gated else "") if tagged else "")
+
+
+def _edge_views(cout):
+    """[(Ms, threshold, tile, side)]: view sizes one tile below (side 0) and at (side 1) each threshold of the selection, in one
+    view and in three views of which only the sum crosses; plus sizes far from every threshold"""
+    out = [([1], None, None, None), ([5000], None, None, None), ([2 * 608 * 608, 2 * 96 * 320, 2 * 64 * 512], None, None, None)]
+    for T, b in ((SMALL_MAX, 128), (F32_SMALL_MAX, 128), (BIG_MIN, 256)):
+        f = cout // b
+        if f:
+            m = (T - 1) // f                                    # m-tiles: m * f < T <= (m + 1) * f
+            for side in (0, 1):
+                out.append(([b * m + side], T, b, side))
+                out.append(([b * (m // 3), b * (m // 3), b * (m - 2 * (m // 3)) + side], T, b, side))
+    return out
+
+
+def test_the_library_selects_what_the_rules_say(hiplib):
+    """no GPU: mv3d_conv3x3_path -- the selection the launch entries call -- equals select_path for every case of the table, and on
+    a sweep that stands one tile below and exactly at every threshold (in one view, and in three views whose sum alone crosses),
+    for every channel class, output type, gate and pool flag; what the entries refuse is NULL"""
+    L = hiplib
+    for c in CASES:
+        for dt in c.dts:
+            assert library_path(L, dt, _Ms(c.views), c.cin, c.cout, c.out_f32, c.gated, c.pool) == c.path, (c.name, dt)
+    seen = set()
+    for dt, cins in (("f16", (16, 64, 48)), ("bf16", (16, 64, 48)), ("f32", (32, 64, 16))):
+        for cin in cins:
+            for cout in (64, 128, 256, 512, 96):
+                for Ms, T, b, side in _edge_views(cout):
+                    if T is not None:                            # the sizes are where they claim to be
+                        lo = _tiles(Ms, cout, b, b) - side * (cout // b)
+                        assert lo < T <= lo + cout // b, (Ms, cout, T)
+                        assert len(Ms) == 1 or all(_tiles([M], cout, b, b) < T for M in Ms)
+                    for out_f32 in (False, True):
+                        for gated in (False, True):
+                            for pool in (False, True):
+                                want = None if refused(dt, cin, cout, out_f32, gated, pool) else select_path(dt, Ms, cin, cout, out_f32, gated, pool)
+                                got = library_path(L, dt, Ms, cin, cout, out_f32, gated, pool)
+                                assert got == want, (dt, Ms, cin, cout, out_f32, gated, pool, got, want)
+                                seen.add(got)
+    assert set(PATHS) | {None} <= seen
+    # the thresholds in plain numbers, from both sides
+    P = lambda dt, Ms, cin, cout, **kw: library_path(L, dt, Ms, cin, cout, **kw)
+    assert P("f16", [128 * 511], 64, 128) == "64x128" and P("f16", [128 * 511 + 1], 64, 128) == "128x128"
+    assert P("bf16", [128 * 170, 128 * 170, 128 * 171], 64, 128) == "64x128" and P("bf16", [128 * 170, 128 * 170, 128 * 171 + 1], 64, 128) == "128x128"
+    assert P("f16", [256 * 639], 64, 256) == "128x128" and P("f16", [256 * 639 + 1], 64, 256) == "pp"
+    assert P("bf16", [256 * 213, 256 * 213, 256 * 213], 64, 256) == "128x128" and P("bf16", [256 * 213, 256 * 213, 256 * 213 + 1], 64, 256) == "pp"
+    assert P("f16", [256 * 639 + 1], 64, 256, out_f32=True) == "128x128_f32out"          # the pp tile has no f32 form
+    assert P("bf16", [256 * 639 + 1], 64, 256, gated=True) == "pp_gated"
+    assert P("f32", [128 * 1023], 32, 128) == "f32_64x128" and P("f32", [128 * 1023 + 1], 32, 128) == "f32_128x128"
+    assert P("f32", [128 * 341, 128 * 341, 128 * 341], 32, 128) == "f32_64x128" and P("f32", [128 * 341, 128 * 341, 128 * 341 + 1], 32, 128) == "f32_128x128"
+    assert P("f16", [10 ** 6], 16, 64) == "conv_input" and P("f16", [10 ** 6], 16, 64, out_f32=True) == "first_256x64_f32out"
+    assert P("bf16", [10 ** 6], 16, 64, gated=True) == "first_256x64_gated" and P("f16", [10 ** 6], 16, 128) == "first_128x128"
+    # refused: channel counts, pool on the input layer's packing, a gate with f32 maps out, a gated or f32 pool, view counts, empty views
+    assert P("f16", [5000], 64, 96) is None and P("f16", [5000], 48, 64) is None and P("f32", [5000], 16, 64) is None
+    assert P("f16", [5000], 16, 64, pool=True) is None and P("bf16", [5000], 64, 64, out_f32=True, gated=True) is None
+    assert P("bf16", [5000], 64, 64, gated=True, pool=True) is None and P("f32", [5000], 32, 64, pool=True) is None
+    assert P("f16", [], 64, 64) is None and P("f16", [5000] * 4, 64, 64) is None and P("f16", [5000, 0], 64, 64) is None
+    assert L.mv3d_conv3x3_path(2, 1, None, 64, 64, 0, 0, 0) is None and L.mv3d_conv3x3_path(3, 1, (C.c_int32 * 1)(5000), 64, 64, 0, 0, 0) is None
+
+
+def _source(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return re.sub(r"\s+", " ", f.read())
+
+
 def test_selection_constants_match_the_sources():
-    """no GPU: the thresholds and conditions select_path restates are the ones compiled into the product (the MV3D_TUNING
-    overrides are not built into it)"""
-    fwd, wg = _source("conv3x3_mfma.hip"), _source("conv3x3_wgrad.hip")
+    """no GPU: the weight gradient's constants and conditions restated above are the ones compiled into the product (its plan depends
+    on the device's occupancy and is not a pure function; the forward selection is asked of the library, above)"""
+    wg = _source("conv3x3_wgrad.hip")
     checks = [
-        (fwd, r"const bool first = c_in == {n};", FIRST_CIN),
-        (fwd, r"if \(first && c_out == {n} && !out_f32 && !gated && input_env\)", INPUT_KERNEL_COUT),
-        (fwd, r"if \(first\) return c_out % 128 == 0 \? launch_conv<T, 128, 128, 2, 2, 2, true>\(g, out_f32, s\) : "
-              r"launch_conv<T, 256, 64, 4, 1, 2, true>\(g, out_f32, s\);", None),
-        (fwd, r"tiles128 \+= \(long\)\(\(g\.v\[k\]\.M \+ 127\) / 128\) \* \(c_out / 128\);", None),
-        (fwd, r"tiles256 \+= \(long\)\(\(g\.v\[k\]\.M \+ 255\) / 256\) \* \(c_out / 256\);", None),
-        (fwd, r"#else const int small_max = {n}; #endif if \(tiles128 < small_max\) return launch_conv<T, 64, 128, 2, 2, 2, false>", SMALL_MAX),
-        (fwd, r"#else const int big_min = {n}, big_wp = 2; #endif if \(!out_f32 && c_out % 256 == 0 && tiles256 >= big_min\)", BIG_MIN),
-        (fwd, r"#else const int pp = 1; #endif .{0,200}if \(pp\) return launch_conv_pp<T>\(g, s\);", None),
-        (fwd, r"#endif return launch_conv<T, 128, 128, 2, 2, 2, false>\(g, out_f32, s\); \} return launch_conv<T, 256, 64, 4, 1, 2, false>", None),
-        (fwd, r"if \(c_out % 128 == 0 && tiles128 < {n}\) return launch_conv<float, 64, 128, 2, 2, 2, false>\(g, 1, s\); "
-              r"if \(c_out % 128 == 0\) return launch_conv<float, 128, 128, 2, 2, 2, false>\(g, 1, s\); "
-              r"return launch_conv<float, 128, 64, 2, 2, 2, false>", F32_SMALL_MAX),
-        (fwd, r"if \(c_out % 128 == 0\) return launch_conv_pool<T, 128, 128, 2, 2>\(g, s\); return launch_conv_pool<T, 256, 64, 4, 1>", None),
         (wg, r"#define RED_G {n}", RED_G),
         (wg, r"#define WG_PIX {n}", WG_PIX),
         (wg, r"#define WGF_PIX {n}", WGF_PIX),
@@ -302,10 +385,11 @@ def _interior(y, framed):
 
 @gpu_mark
 @pytest.mark.parametrize("c,dt", _CASE_PARAMS)
-def test_forward_path_exact_on_integer_operands(gpu, c, dt):
+def test_forward_path_exact_on_integer_operands(gpu, hiplib, c, dt):
     """integer operands: f32 outputs EQUAL the float64 reference, 16-bit outputs equal its round-to-nearest-even"""
     torch = gpu
     assert select_path(dt, _Ms(c.views), c.cin, c.cout, c.out_f32, c.gated, c.pool) == c.path
+    assert library_path(hiplib, dt, _Ms(c.views), c.cin, c.cout, c.out_f32, c.gated, c.pool) == c.path
     ops_views = _operands(torch, c, dt, True, seed=_seed(c.name))
     outs = _launch(torch, c, dt, ops_views)
     framed = c.framed or c.pool
@@ -344,9 +428,10 @@ def _bound_check(torch, got, ref, S, L, out_dt, what):
 
 @gpu_mark
 @pytest.mark.parametrize("c,dt", _CASE_PARAMS)
-def test_forward_path_within_float64_bound_on_random_operands(gpu, c, dt):
+def test_forward_path_within_float64_bound_on_random_operands(gpu, hiplib, c, dt):
     """He-scaled random operands rounded to the operand type: per element |got - ref| <= 2^-p |ref| + 1.01 (9 Cin + 1) 2^-24 S"""
     torch = gpu
+    assert library_path(hiplib, dt, _Ms(c.views), c.cin, c.cout, c.out_f32, c.gated, c.pool) == c.path
     ops_views = _operands(torch, c, dt, False, seed=_seed(c.name) + 1)
     outs = _launch(torch, c, dt, ops_views)
     framed = c.framed or c.pool
@@ -372,7 +457,7 @@ def test_forward_path_within_float64_bound_on_random_operands(gpu, c, dt):
 
 @gpu_mark
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
-def test_batch_invariance_across_paths(gpu, dt):
+def test_batch_invariance_across_paths(gpu, hiplib, dt):
     """A frame's result does not depend on the path its launch takes: frame 5 of a batch-16 launch (conv3x3_pp_kernel), of a
     batch-4 launch (128 x 128, 2 stages) and alone (64 x 128, few tiles), random operands -- bit for bit, as the pp kernel's header
     claims (the three tiles walk a pixel's K steps in the same order through the same MFMA fragments)."""
@@ -383,6 +468,7 @@ def test_batch_invariance_across_paths(gpu, dt):
     B, H, W, C = 16, 76, 76, 512
     assert select_path(dt, [B * H * W], C, C) == "pp" and select_path(dt, [4 * H * W], C, C) == "128x128"
     assert select_path(dt, [H * W], C, C) == "64x128"
+    assert [library_path(hiplib, dt, [b * H * W], C, C) for b in (B, 4, 1)] == ["pp", "128x128", "64x128"]
     x = ops.frame_nhwc_f16(torch.randn((B, H, W, C), device="cuda", generator=g), ops.framed_buffer(B, H, W, C, "cuda", T))
     w = ops.pack_conv3x3_weights(torch.randn((C, C, 3, 3), device="cuda", generator=g) * (2.0 / (9 * C)) ** 0.5, dtype=T)
     b = torch.randn(C, device="cuda", generator=g) * 0.5

@@ -2,8 +2,10 @@
 the library's limit of 32768 boxes per frame, against references that cannot share the kernels' bugs.
 
 The host code picks the sort by the key stride and the round layout by the box count and the cap.  `sort_path` and `rounds`
-below restate those rules; every case names what it must reach, and `test_selection_constants_match_the_sources` (no GPU) reads
-the constants and the `bounds` tables out of the .hip sources, so that a retuned limit cannot silently move a case to another path.
+below restate those rules; every case names what it must reach.  The round layout is asked of the library: `mv3d_nms_round_plan`
+(host only) returns the plan the launcher walks, and `test_the_library_plans_the_rounds_the_rules_say` (no GPU) compares it with
+`rounds` for every frame size and both layouts; `test_selection_constants_match_the_sources` (no GPU) reads the remaining constants
+out of the .hip sources, so that a retuned limit cannot silently move a case to another path.
 
   * the sort: `nms_host` with a threshold that suppresses nothing returns the whole processing order.  It must equal a numpy
     `lexsort` (descending score, NaN largest, -0.0 == +0.0, ties by descending index) over tied, NaN, infinite, signed-zero,
@@ -16,6 +18,7 @@ the constants and the `bounds` tables out of the .hip sources, so that a retuned
     diagonal tile, an off-diagonal tile of round 1, a tile of round 2 and a tile reduced through `rem`.
   * proposal_3d over 24576 anchors: the 24-run merge and the counting sort with the record gather, batched frames that finish
     in different rounds, against the oracle's ROI blobs bit for bit."""
+import ctypes as C
 import functools
 import os
 import re
@@ -147,49 +150,52 @@ def _define(src, name):
     return int(m.group(1))
 
 
-def _bounds_from_source(src, nbw, max_keep):
-    """evaluates the bounds[] initialiser and the two overrides of mv3d_launch_nms for one (nbw, max_keep)"""
-    init = re.search(r"int bounds\[8\] = \{([^}]*)\};", src)
-    big = re.search(r"if \(L\.max_keep <= 0 \|\| L\.max_keep > (\d+)\) \{([^}]*)\}", src)
-    wide = re.search(r"else if \(nbw > (\d+)\) \{([^}]*)\}", src)
-    assert init and big and wide
-    val = lambda tok: nbw if tok.strip() == "nbw" else int(tok)
-    b = [val(t) for t in init.group(1).split(",")]
-    assigns = lambda body: [(int(i), val(v)) for i, v in re.findall(r"bounds\[(\d)\] = (\w+);", body)]
-    if max_keep <= 0 or max_keep > int(big.group(1)):
-        for i, v in assigns(big.group(2)):
-            b[i] = v
-    elif nbw > int(wide.group(1)):
-        for i, v in assigns(wide.group(2)):
-            b[i] = v
-    return b
+@functools.lru_cache(maxsize=None)
+def _hiplib():
+    from mv3d_tf_amd import build
+    build.build()
+    from mv3d_tf_amd import _lib
+    return _lib.lib()
+
+
+def library_rounds(n, max_keep):
+    """what the library decides: mv3d_nms_round_plan (host only; the plan function mv3d_launch_nms itself walks), in the form of
+    `rounds`; None = refused"""
+    out = (C.c_int32 * 21)(*([-1] * 21))
+    nr = _hiplib().mv3d_nms_round_plan(n, max_keep, out)
+    assert 0 <= nr <= 7 and all(v == -1 for v in out[3 * nr:])
+    return [(out[3 * r], out[3 * r + 1], out[3 * r + 2] or "chain_lds") for r in range(nr)] or None
+
+
+def test_the_library_plans_the_rounds_the_rules_say():
+    """no GPU: the library's round plan equals the restated one, kernel widths included, for every frame size in blocks and on both
+    sides of the cap that switches the layout; an empty frame, box counts that fill no whole block, and counts it refuses"""
+    for nbw in range(1, NMS_MAX_WORDS + 1):
+        for cap in (0, 1, SMALL_CAP_MAX, SMALL_CAP_MAX + 1):
+            assert library_rounds(64 * nbw, cap) == rounds(64 * nbw, cap), (nbw, cap)
+    assert library_rounds(0, 0) == library_rounds(0, 300) == [(0, 0, "chain_lds")] == rounds(0, 0)
+    for n in (1, 63, 65, 2049, 64 * CAP_SMALL_NBW + 1, 13000, 16385, MAX_BOXES - 63, MAX_BOXES - 1):
+        for cap in (-1, 0, 300, SMALL_CAP_MAX, SMALL_CAP_MAX + 1, 2000):
+            assert library_rounds(n, cap) == rounds(n, cap), (n, cap)
+    # the layouts in plain numbers, at the edges of the cap and of the small cap layout
+    assert library_rounds(64 * 128, 512) == [(0, 32, "chain_lds"), (32, 128, 128)]
+    assert library_rounds(64 * 128 + 1, 512) == [(0, 32, "chain_lds"), (32, 128, 128), (128, 129, 32)]
+    assert library_rounds(64 * 128, 513) == [(0, 32, "chain_lds"), (32, 64, 32), (64, 128, 64)]
+    assert library_rounds(32768, 0) == [(0, 32, "chain_lds"), (32, 64, 32), (64, 128, 64), (128, 256, 128), (256, 384, 128), (384, 512, 128)]
+    assert library_rounds(64 * 97, 300) == [(0, 32, "chain_lds"), (32, 97, 128)] and library_rounds(64 * 96, 300)[1] == (32, 96, 64)
+    assert library_rounds(64 * 65, 0)[2] == (64, 65, 32) and library_rounds(64 * 64, 300)[1] == (32, 64, 32)
+    assert library_rounds(MAX_BOXES + 1, 0) is None and library_rounds(-1, 0) is None and library_rounds(10 ** 6, 300) is None
 
 
 def test_selection_constants_match_the_sources():
-    """no GPU: the constants restated above are the ones rank.hip / nms.hip compile, and the restated round layout equals
-    the one the source's bounds tables produce, for every frame size and both layouts"""
+    """no GPU: the constants restated above are the ones rank.hip / nms.hip compile (the round layout is asked of the library,
+    above)"""
     rank, nms = _src("rank.hip"), _src("nms.hip")
     assert _define(rank, "RANK_LDS_KEYS") == RANK_LDS_KEYS and _define(rank, "RANK_SEG") == RANK_SEG
     assert _define(rank, "RANK_RUN") == RANK_SEG
     assert re.search(r"if \(key_stride <= RANK_LDS_KEYS\)", rank)
     assert re.search(r"return \(N \+ RANK_SEG - 1\) / RANK_SEG \* RANK_SEG;", rank)
     assert _define(nms, "NMS_MAX_WORDS") == NMS_MAX_WORDS and _define(nms, "CHL_ARENA") == CHL_ARENA
-    assert re.search(r"if \(width <= 32\) hipLaunchKernelGGL\(nms_round_kernel<32>", nms)
-    assert re.search(r"else if \(width <= 64\) hipLaunchKernelGGL\(nms_round_kernel<64>", nms)
-    assert re.search(r"else hipLaunchKernelGGL\(nms_round_kernel<128>", nms)
-    assert re.search(r"L\.max_keep <= 0 \|\| L\.max_keep > %d\)" % SMALL_CAP_MAX, nms)
-    assert re.search(r"else if \(nbw > %d\)" % CAP_SMALL_NBW, nms)
-    for nbw in range(1, NMS_MAX_WORDS + 1):
-        for cap in (0, 1, SMALL_CAP_MAX, SMALL_CAP_MAX + 1):
-            b = _bounds_from_source(nms, nbw, cap)
-            want, r = [], 0
-            while r < 7:
-                b0, b1 = min(b[r], nbw), min(b[r + 1], nbw)
-                if r > 0 and b0 >= b1:
-                    break
-                want.append((b0, b1))
-                r += 1
-            assert [(b0, b1) for b0, b1, _ in rounds(64 * nbw, cap)] == want, (nbw, cap)
     # the fast path's gates
     m = re.search(r"d\.fast_ok = \(d\.tf >= (0x1p-?\d+f) && d\.tf <= (0x1p-?\d+f)\)", nms)
     assert m and float.fromhex(m.group(1)[:-1]) == FAST_TF_MIN and float.fromhex(m.group(2)[:-1]) == FAST_TF_MAX
