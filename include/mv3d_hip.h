@@ -471,6 +471,37 @@ int mv3d_point_cloud_2_top_ranges(const float *points_dev, int num_points, doubl
                                   double fwd_lo, double fwd_hi, double height_lo, double height_hi, float *top_dev,
                                   int *status_dev, void *stream);
 
+/* The same rasteriser for `num_frames` clouds behind three launches (clear, scatter, resolve; the clear alone with total_points == 0),
+ * whatever num_frames is (csrc/bev_raster_batch.hip).  Frame b of the output equals, bit for bit, what
+ * mv3d_point_cloud_2_top (ranges8_host == NULL) or mv3d_point_cloud_2_top_ranges writes for that frame's rows alone.
+ *   points_dev    (total_points, 4) f32 [x, y, z, reflectance], the frames' clouds concatenated, 16-byte aligned (rows are read as
+ *                 16-byte vectors); total_points up to INT_MAX
+ *   offsets_dev   (num_frames + 1) int32 ON THE DEVICE, mv3d_point_cloud_2_front's rule: frame b owns rows offsets[b] .. offsets[b + 1];
+ *                 the frame of a row is the last b with offsets[b] <= row; equal neighbours = an empty frame; rows no frame owns --
+ *                 in front of offsets[0], behind offsets[num_frames], anything under offsets that do not ascend -- are ignored, and
+ *                 so is a row more than 2^27 - 2 rows into its frame (mv3d_point_cloud_2_top's limit, per frame).  No value in it
+ *                 can make the call read or write out of bounds.  NULL with num_frames == 1: the one frame owns every row.
+ *   ranges8_host  NULL = the call MV3D makes -> (601, 601, 9) per frame; else res, zres, side_lo, side_hi, fwd_lo, fwd_hi, height_lo,
+ *                 height_hi on the HOST, read before the call returns -> the shape mv3d_point_cloud_2_top_shape gives
+ *   top_dev       (num_frames, H, W, C) f32 contiguous, 4-byte aligned: it may be any run of frames inside a larger batch buffer
+ *                 (one MV3D frame is 13 003 236 bytes = 4 mod 16, so such a run is 16-byte aligned for one frame in four only)
+ *   status_dev    required iff ranges8_host: ONE int32 for the whole batch, cleared by the call and set to 1 where
+ *                 mv3d_point_cloud_2_top_ranges sets it; ignored without ranges (no cell of MV3D's map can fall outside)
+ * Captured in a graph that replays on clouds of changing size (the front view's rule): points_dev is a static buffer of
+ * `total_points` rows -- the capacity, which fixes the grid at capture -- and offsets_dev is rewritten before each replay; the rows
+ * behind offsets[num_frames] belong to no frame, whatever they hold.
+ * No allocation, no host synchronisation; num_frames == 0 returns MV3D_OK without a launch.  MV3D_ERR_INVALID_ARG: num_frames
+ * outside [0, MV3D_FV_MAX_FRAMES], negative total_points, NULL or misaligned pointers, offsets_dev == NULL with num_frames != 1,
+ * ranges mv3d_point_cloud_2_top_shape refuses, ranges without status_dev.
+ * mv3d_point_cloud_2_top_batch is the entry: its resolve stores only the 16-byte vectors a point fell into (an empty key is
+ * already 0.0f).  mv3d_point_cloud_2_top_batch_dense is the same call with a resolve that stores every element, as the single-cloud
+ * kernel's does: the same bits, 1.5 - 3 % slower where it was measured, and there for tools/bev_batch_bench.py to
+ * time against the entry -- nothing else calls it. */
+int mv3d_point_cloud_2_top_batch(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
+                                 const double *ranges8_host, float *top_dev, int32_t *status_dev, void *stream);
+int mv3d_point_cloud_2_top_batch_dense(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
+                                       const double *ranges8_host, float *top_dev, int32_t *status_dev, void *stream);
+
 /* ------------------------------------------------------------------ the target layers' random subsamplings (HOST code)
  * The reference subsamples with `npr.choice(inds, size=k, replace=False)` on the numpy GLOBAL legacy RandomState
  * (lib/rpn_msr/anchor_target_layer_tf.py:146-159,178-183; lib/rpn_msr/proposal_target_layer_tf.py:246-269) = 

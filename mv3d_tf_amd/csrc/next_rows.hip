@@ -6,6 +6,7 @@
 //           (lib/utils/transform.py:342-366)
 #include <math.h>
 #include "geometry.h"
+#include "bev_params.h"
 
 // ---------------------------------------------------------------------------- BEV rasteriser
 // The reference assigns top[y, x, i] = z - height_range[0] and top[y, x, z_max] = reflectance slice by slice with numpy fancy
@@ -17,13 +18,7 @@
 // (a height written to channel z_max -- possible when (h1 - h0) / zres is not an integer -- is always overwritten by the same
 // iteration's reflectance, read_lidar.py:109-112, so that channel only ever shows the reflectance).
 // HBM-bound: one clear of the map, P scattered atomics, one read-modify-write of the map.
-// The dtypes numpy gives every step (f32 range tests against Python floats, f64 slice tests against np.arange's values, which are
-// h0, h0 + zres, h0 + i * ((h0 + zres) - h0), ...) are spelled out in oracle/mv3d_oracle.c:mv3d_ref_point_cloud_2_top_ranges.
-struct BevParams {
-    float fwd0f, fwd1f, ylo, yhi, resf, h0f;
-    double h0, next, delta, zres;
-    int xoff, yoff, Hd, Wd, Cd, nslice, zmax;
-};
+// BevParams / bev_params (bev_params.h) are shared with the batched entry of bev_raster_batch.hip.
 
 // zero keys: four 16-byte stores per thread, a workgroup clears 16 KB contiguous (hipMemsetAsync splits the 13 MB
 // clear into two 6 us fills)
@@ -76,20 +71,6 @@ __global__ __launch_bounds__(256) void bev_resolve_kernel(const float *__restric
         out = (c == q.zmax) ? pts[4 * (long long)p + 3] : (pts[4 * (long long)p + 2] - q.h0f);   // z - height_range[0] in f32 (:106)
     }
     top[e] = out;
-}
-
-static bool bev_params(double res, double zres, double side0, double side1, double fwd0, double fwd1, double h0, double h1, BevParams &q)
-{
-    if (!(res > 0.0) || !(zres > 0.0) || !(side1 > side0) || !(fwd1 > fwd0) || !(h1 >= h0)) return false;
-    const double nx = (side1 - side0) / res, ny = (fwd1 - fwd0) / res, nz = (h1 - h0) / zres;
-    if (!(nx < 32768.0) || !(ny < 32768.0) || !(nz < 31.0)) return false;       // (the key of the last channel holds 5 bits of slice)
-    const int x_max = (int)nx, y_max = (int)ny, z_max = (int)nz;                 // read_lidar.py:49-51
-    q.Wd = x_max + 1; q.Hd = y_max + 1; q.Cd = z_max + 1; q.zmax = z_max;
-    q.xoff = (int)floor(side0 / res); q.yoff = (int)floor(fwd1 / res);
-    q.nslice = (int)ceil(nz);
-    q.h0 = h0; q.next = h0 + zres; q.delta = q.next - h0; q.zres = zres;
-    q.fwd0f = (float)fwd0; q.fwd1f = (float)fwd1; q.ylo = (float)(-side1); q.yhi = (float)(-side0); q.resf = (float)res; q.h0f = (float)h0;
-    return true;
 }
 
 static int bev_launch(const float *points_dev, int num_points, const BevParams &q, float *top_dev, int *status_dev, hipStream_t s)

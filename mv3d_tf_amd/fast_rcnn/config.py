@@ -88,6 +88,12 @@ cfg.ROI_UPSAMPLE = (1, 1, 1)
 # rasterised on the device from the frame's Velodyne scan (ops.point_cloud_2_front; the entry's 'lidar_fv' map,
 # 'velodyne' array or 'velodyne_path' file).  False = the reference's blobs.  train_net refuses a 3-view network with the key off.
 cfg.FRONT_VIEW_INPUT = False
+# (not in the reference, which reads every frame's bird's-eye-view map from <kitti>/object/training/lidar_bv/*.npy, 13 MB a frame that
+# KITTI does not ship) True: `lidar_bv_data` is rasterised on the device from the frame's Velodyne scan (ops.point_cloud_2_top_batch,
+# DESIGN.md section 3.22; the entry's 'lidar_bv' map if it has one, else its 'velodyne' array or 'velodyne_path' file): prepare_roidb
+# records no lidar_bv_path, and get_minibatch, detect_batch.test_net and rpn_msr.generate.imdb_proposals never open a stored map.  With
+# FRONT_VIEW_INPUT also on, both rasters read one upload of the scan.  False = the stored maps, every blob and code path as before.
+cfg.LIDAR_BV_FROM_SCAN = False
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
 cfg.EXP_DIR = 'default'

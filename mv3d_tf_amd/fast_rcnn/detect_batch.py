@@ -79,15 +79,42 @@ def front_view_source(net, imdb):
     """None for a two-view network; for a three-view one (net.views == 3) the function i -> (P,4) f32 scan of frame i that its
     `lidar_fv_data` is rasterised from: imdb.points_at(i) if the imdb has it, else the file imdb.velodyne_path_at(i) names.  An imdb
     with neither raises ValueError here, before a loop loads its first frame."""
-    if getattr(net, "views", 2) != 3:
-        return None
+    return scan_source(imdb, "a three-view network (`lidar_fv_data`)") if getattr(net, "views", 2) == 3 else None
+
+
+def scan_source(imdb, needed_by):
+    """The loops' one source of scans, for any network: the function i -> (P,4) f32 scan of frame i, imdb.points_at(i) if the imdb
+    has it, else the file imdb.velodyne_path_at(i) names.  An imdb with neither raises ValueError here, before a loop loads its first frame;
+    `needed_by` says in that message what asked for the scans."""
     if hasattr(imdb, "points_at"):
         return lambda i: np.ascontiguousarray(np.asarray(imdb.points_at(i), np.float32)[:, :4])
     if hasattr(imdb, "velodyne_path_at"):
         from ..utils.read_lidar import load_velodyne
         return lambda i: load_velodyne(imdb.velodyne_path_at(i))
-    raise ValueError("a three-view network needs `lidar_fv_data`: the imdb has neither points_at(i) nor velodyne_path_at(i) to "
-                     "rasterise it from")
+    raise ValueError("{} needs the frames' Velodyne scans: the imdb has neither points_at(i) nor velodyne_path_at(i)".format(needed_by))
+
+
+def loop_scan_source(net, imdb):
+    """(i -> scan or None, maps_from_scans) for a detection loop: a three-view network needs the scans for `lidar_fv_data`,
+    cfg.LIDAR_BV_FROM_SCAN for `lidar_bv_data` of any network; None when neither asks"""
+    from_scan = bool(cfg.LIDAR_BV_FROM_SCAN)
+    points_of = front_view_source(net, imdb)
+    return (scan_source(imdb, "cfg.LIDAR_BV_FROM_SCAN") if points_of is None and from_scan else points_of), from_scan
+
+
+def scan_feed(clouds, bev, fv):
+    """the feed entries a group of frames gets from its scans: the clouds are concatenated and uploaded ONCE, and `lidar_bv_data`
+    (bev true: one ops.point_cloud_2_top_batch call) and `lidar_fv_data` (fv true: one ops.point_cloud_2_front call) are rasterised
+    from that one device tensor"""
+    feed = {}
+    if bev or fv:
+        pts = ops._dev(np.concatenate(clouds, 0))
+        offsets = np.cumsum([0] + [len(c) for c in clouds])
+        if bev:
+            feed["lidar_bv_data"] = ops.point_cloud_2_top_batch(pts, offsets=offsets)
+        if fv:
+            feed["lidar_fv_data"] = ops.point_cloud_2_front(pts, offsets=offsets)
+    return feed
 
 
 class _FeedsFrontView:
@@ -114,12 +141,13 @@ def box_detect(sess, net, im, bv, calib, boxes=None, fv=None):
     return test_mv.box_detect(sess, _FeedsFrontView(net, fv), im, bv, calib, boxes)
 
 
-def _load_frame(imdb, i):
-    """(image, BEV map, calib) of frame i of a duck-typed imdb (see test_mv.test_net)"""
+def _load_frame(imdb, i, stored_bv=True):
+    """(image, BEV map, calib) of frame i of a duck-typed imdb (see test_mv.test_net); stored_bv=False (cfg.LIDAR_BV_FROM_SCAN): the
+    map is None and neither imdb.bv_at nor imdb.lidar_path_at is touched"""
     if hasattr(imdb, "image_at"):
-        im, bv = imdb.image_at(i), imdb.bv_at(i)
+        im, bv = imdb.image_at(i), (imdb.bv_at(i) if stored_bv else None)
     else:
-        bv = np.load(imdb.lidar_path_at(i))
+        bv = np.load(imdb.lidar_path_at(i)) if stored_bv else None
         path = imdb.image_path_at(i)
         if path.endswith(".npy"):
             im = np.load(path)
@@ -152,13 +180,16 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
     with fixed ROI rows per group of equally shaped consecutive frames (`iter_frame_groups`), the box tail and ops.detect_post on the
     device, ONE read-back of the final detections per group.  A three-view network takes the device route for any BATCH_SIZE and
     gets `lidar_fv_data` from the frames' scans (`front_view_source`), a group's frames rasterised by ONE batched
-    ops.point_cloud_2_front call.  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
+    ops.point_cloud_2_front call.  cfg.LIDAR_BV_FROM_SCAN: the device route for any BATCH_SIZE, no stored BEV map is opened (`_load_frame`
+    touches neither imdb.bv_at nor imdb.lidar_path_at), frames group by image shape and ops.BEV_SHAPE, and a group's `lidar_bv_data` is
+    ONE ops.point_cloud_2_top_batch call on the group's scans (`scan_feed`: one upload for both rasters).  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
     ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
     group) and the evaluate_detections call are test_mv.test_net's."""
     batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
     oriented = bool(cfg.TEST.get("NMS_ORIENTED", False))
     footprint = cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed")
-    points_of = front_view_source(net, imdb)
+    points_of, from_scan = loop_scan_source(net, imdb)
+    three_views = getattr(net, "views", 2) == 3
     if batch_size <= 1 and not oriented and points_of is None:
         return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
     if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
@@ -172,8 +203,8 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
 
     def keys():
         for i in range(num_images):
-            pending[i] = _load_frame(imdb, i) + ((None if points_of is None else points_of(i)),)
-            yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
+            pending[i] = _load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
+            yield (np.shape(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
 
     t_detect = t_misc = 0.0
     for group in iter_frame_groups(keys(), max(batch_size, 1)):
@@ -181,13 +212,11 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
         B = len(group)
         t0 = time.time()
         im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
-        bv_blob = np.stack([np.asarray(bv, np.float32) for bv in bvs])
-        im_info = np.array([[bv_blob.shape[1], bv_blob.shape[2], 1]] * B, dtype=np.float32)
-        feed = {"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
-                "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
-        if points_of is not None:                                      # the group's scans back to back: one upload, one call
-            feed["lidar_fv_data"] = ops.point_cloud_2_front(np.concatenate(clouds, 0),
-                                                            offsets=np.cumsum([0] + [len(c) for c in clouds]))
+        feed = {"image_data": im_blob, "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
+        if not from_scan:
+            feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
+        feed.update(scan_feed(clouds, from_scan, three_views))         # the group's scans back to back: one upload, one call per view
+        feed["im_info"] = np.array([[feed["lidar_bv_data"].shape[1], feed["lidar_bv_data"].shape[2], 1]] * B, dtype=np.float32)
         net.fixed_rois = True
         try:
             with torch.no_grad():

@@ -719,6 +719,87 @@ def point_cloud_2_front(points, offsets=None, out=None, workspace=None):
     return out
 
 
+BEV_SHAPE = (601, 601, 9)            # the map of the call MV3D makes (tools/read_lidar.py:121-133): rows x columns x (8 slices + reflectance)
+BEV_MAX_FRAME_POINTS = (1 << 27) - 1  # rows per frame (the winner key holds the row's index within its frame in 27 bits)
+
+
+def point_cloud_2_top_batch(points, offsets=None, ranges=None, out=None):
+    """point_cloud_2_top for B clouds behind three launches (csrc/bev_raster_batch.hip), argument for argument
+    ops.point_cloud_2_front: points (P,4) f32 [x,y,z,reflectance] (a device tensor, or a numpy array, which is uploaded) is B clouds
+    back to back, offsets = (B + 1) ascending int32 row offsets (host sequence / array, or a device tensor), frame b owns rows
+    offsets[b]:offsets[b + 1]; the result is (B,601,601,9) f32 on the device -- (601,601,9) without offsets, one frame -- and frame b
+    of it equals point_cloud_2_top(that frame's rows) bit for bit.  ranges = (res, zres, side_lo, side_hi, fwd_lo, fwd_hi, height_lo,
+    height_hi): the frames' shape is mv3d_point_cloud_2_top_shape's, and ONE status word for the batch is read back (a
+    synchronisation) to raise IndexError where numpy's fancy assignment would.  out = a contiguous f32 device tensor of the result's
+    shape to write into; it may be any slice of frames of a larger batch buffer (4-byte alignment is all it needs).  With device
+    inputs, out= and no ranges the call allocates nothing and can be captured.
+    Every argument is checked before anything is launched: TypeError for a wrong dtype, ValueError for a wrong shape or device.  The
+    VALUES of offsets are checked (ascending, within [0, P], at most 2^27 - 1 rows a frame) only when they come from the host:
+    reading a device tensor would synchronise.  Under malformed device offsets the call stays inside its buffers and silently skips
+    the rows no frame owns (include/mv3d_hip.h)."""
+    if isinstance(points, torch.Tensor):
+        if points.dtype != torch.float32:
+            raise TypeError("point_cloud_2_top_batch: points must be float32, got {}".format(points.dtype))
+        if not points.is_cuda:
+            raise ValueError("point_cloud_2_top_batch: a points tensor must live on the device (pass a numpy array to have it uploaded)")
+    else:
+        points = np.asarray(points)
+        if points.dtype != np.float32:
+            raise TypeError("point_cloud_2_top_batch: points must be float32, got {}".format(points.dtype))
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("point_cloud_2_top_batch: points must be (P, 4) [x, y, z, reflectance], got {}".format(tuple(points.shape)))
+    P = int(points.shape[0])
+    frame, r = BEV_SHAPE, None
+    if ranges is not None:
+        r = (C.c_double * 8)(*[float(v) for v in ranges])     # (anything but 8 numbers: ctypes / float raise TypeError or ValueError here)
+        dims = (C.c_int * 3)()
+        if lib().mv3d_point_cloud_2_top_shape(*r, dims) != _lib.OK:
+            raise ValueError("point_cloud_2_top_batch: ranges {} are empty, inverted or beyond 32767 cells / 31 slices".format(tuple(r)))
+        frame = tuple(dims)
+    shape = frame
+    if offsets is not None:
+        if isinstance(offsets, torch.Tensor):
+            if offsets.dtype != torch.int32:
+                raise TypeError("point_cloud_2_top_batch: an offsets tensor must be int32, got {}".format(offsets.dtype))
+        else:
+            offsets = np.asarray(offsets)
+            if not np.issubdtype(offsets.dtype, np.integer):
+                raise TypeError("point_cloud_2_top_batch: offsets must be integers, got {}".format(offsets.dtype))
+            if offsets.ndim == 1 and offsets.size and (np.any(np.diff(offsets) < 0) or offsets[0] < 0 or offsets[-1] > P):
+                raise ValueError("point_cloud_2_top_batch: offsets must ascend within [0, {}], got {}".format(P, offsets.tolist()))
+            if offsets.ndim == 1 and offsets.size > 1 and np.diff(offsets).max() > BEV_MAX_FRAME_POINTS:
+                raise ValueError("point_cloud_2_top_batch: a frame holds at most {} rows".format(BEV_MAX_FRAME_POINTS))
+        if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
+            raise ValueError("point_cloud_2_top_batch: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(FV_MAX_FRAMES, tuple(offsets.shape)))
+        shape = (int(offsets.shape[0]) - 1,) + frame
+    elif P > BEV_MAX_FRAME_POINTS:
+        raise ValueError("point_cloud_2_top_batch: a frame holds at most {} rows".format(BEV_MAX_FRAME_POINTS))
+    B = 1 if offsets is None else shape[0]
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
+        raise TypeError("point_cloud_2_top_batch: out must be a {} tensor".format(torch.float32))
+    # one device for every tensor handed in (a numpy cloud goes where they are; with none of them, to the current device)
+    tensors = [(n, t) for n, t in (("points", points), ("offsets", offsets), ("out", out)) if isinstance(t, torch.Tensor)]
+    for name, t in tensors:
+        if not t.is_cuda or t.device != tensors[0][1].device:
+            raise ValueError("point_cloud_2_top_batch: {} on {}: every tensor must live on one HIP device".format(name, t.device))
+        if name == "out" and not t.is_contiguous():
+            raise ValueError("point_cloud_2_top_batch: out must be contiguous")
+    dev = tensors[0][1].device if tensors else "cuda"
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError("point_cloud_2_top_batch: out must be {}, got {}".format(shape, tuple(out.shape)))
+    pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    off = None                                                # (one frame: the entry takes NULL offsets, nothing to upload)
+    if offsets is not None:
+        off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    status = None if r is None else torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().mv3d_point_cloud_2_top_batch(_ptr(pts), _ptr(off), B, P, r, _ptr(out), _ptr(status), _stream()), "mv3d_point_cloud_2_top_batch")
+    if status is not None and int(status.item()):
+        raise IndexError("point_cloud_2_top_batch: a point's cell lies outside the map (numpy raises IndexError there)")
+    return out
+
+
 def gt_encode(box_cam, cos_sin, inv_rot, tr):
     """box_cam (G,6) f32, cos_sin (G,2) f64, inv_rot (9) f32, tr (12) f32 device tensors -> (corners_cam (G,24),
     corners_lidar (G,24), boxes_3d (G,6), boxes_bv (G,4)) f32 in ONE buffer (pack, views): a host caller fetches it with

@@ -10,7 +10,10 @@ numpy (.npy) or PIL -- cv2 is not a dependency here.  An entry with `flipped` tr
 device tensors, mirrored left/right by ops.mirror_columns; every other entry returns numpy as the reference does.
 
 cfg.FRONT_VIEW_INPUT (not in the reference; default off = the blobs above exactly) adds `lidar_fv_data` (1,64,512,3), the third view's
-input, as a device tensor: see `front_view_blob`."""
+input, as a device tensor: see `front_view_blob`.
+cfg.LIDAR_BV_FROM_SCAN (not in the reference; default off) takes `lidar_bv_data` of an entry without an in-memory 'lidar_bv' from its
+scan ('velodyne' array or 'velodyne_path' file) instead of 'lidar_bv_path': a (1,601,601,9) device tensor rasterised by
+ops.point_cloud_2_top_batch, im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters."""
 import numpy as np
 import numpy.random as npr
 
@@ -26,7 +29,24 @@ def _read_image_bgr(path):
     return np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
 
 
-def front_view_blob(entry):
+def _entry_cloud(entry, key, own_map):
+    """the (P,4) f32 [x,y,z,reflectance] scan of a roidb entry as a contiguous host array: entry['velodyne'], an array in memory, else
+    the file entry['velodyne_path'] names (a KITTI `.bin` scan or a `.npy`, utils.read_lidar.load_velodyne).  A `flipped` entry gets
+    the cloud with y negated (the mirror of the scene, datasets/mirror.py), as a copy: the entry's own array stays."""
+    if 'velodyne' in entry:
+        pts = np.asarray(entry['velodyne'], np.float32)
+    elif 'velodyne_path' in entry:
+        from ..utils.read_lidar import load_velodyne
+        pts = load_velodyne(entry['velodyne_path'])
+    else:
+        raise ValueError("cfg.{} is on and the roidb entry has none of '{}', 'velodyne', 'velodyne_path'".format(key, own_map))
+    pts = np.ascontiguousarray(pts.reshape(-1, pts.shape[-1])[:, :4])
+    if entry.get('flipped', False):
+        pts = pts * np.array([1, -1, 1, 1], np.float32)
+    return pts
+
+
+def front_view_blob(entry, cloud=None):
     """`lidar_fv_data` (1,64,512,3) f32 on the device for one roidb entry, from the first of: entry['lidar_fv'], a (64,512,3) map in
     memory, used as is; entry['velodyne'], a (P,4) [x,y,z,reflectance] array; entry['velodyne_path'], a KITTI `.bin` scan or a `.npy`
     (utils.read_lidar.load_velodyne) -- a cloud is rasterised by ops.point_cloud_2_front.
@@ -34,23 +54,15 @@ def front_view_blob(entry):
     the column-reversed map of the source frame: the column is floor((45 deg - azimuth) / d_theta), and floor makes the bin edges
     asymmetric -- a point exactly on an edge belongs to the bin on one fixed side of it before and after the mirror, and azimuth
     +45 deg is column 0 while -45 deg is column 512, outside the map -- so reversing the columns is not the mirrored scene's raster.
-    An in-memory 'lidar_fv' is the caller's map for that entry and is not touched."""
+    An in-memory 'lidar_fv' is the caller's map for that entry and is not touched.
+    cloud = the entry's scan already on the device, (P,4) f32 with y negated if the entry is `flipped` (what get_minibatch uploaded
+    for the bird's-eye view under cfg.LIDAR_BV_FROM_SCAN): rasterised in place of a second read and upload of the scan."""
     if 'lidar_fv' in entry:
         fv = ops._dev(entry['lidar_fv'])
         if tuple(fv.shape) != ops.FV_SHAPE:
             raise ValueError("entry['lidar_fv'] must be {}, got {}".format(ops.FV_SHAPE, tuple(fv.shape)))
         return fv[None]
-    if 'velodyne' in entry:
-        pts = np.asarray(entry['velodyne'], np.float32)
-    elif 'velodyne_path' in entry:
-        from ..utils.read_lidar import load_velodyne
-        pts = load_velodyne(entry['velodyne_path'])
-    else:
-        raise ValueError("cfg.FRONT_VIEW_INPUT is on and the roidb entry has none of 'lidar_fv', 'velodyne', 'velodyne_path'")
-    pts = np.ascontiguousarray(pts.reshape(-1, pts.shape[-1])[:, :4])
-    if entry.get('flipped', False):
-        pts = pts * np.array([1, -1, 1, 1], np.float32)      # (a copy: the entry's own array stays)
-    return ops.point_cloud_2_front(pts)[None]
+    return ops.point_cloud_2_front(_entry_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv') if cloud is None else cloud)[None]
 
 
 def get_minibatch(roidb, num_classes):
@@ -62,10 +74,20 @@ def get_minibatch(roidb, num_classes):
     entry = roidb[0]
     image = entry['image'] if 'image' in entry else _read_image_bgr(entry['image_path'])
     image = image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS
-    bev = entry['lidar_bv'] if 'lidar_bv' in entry else np.load(entry['lidar_bv_path'])
-    blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': np.asarray(bev)[None], 'calib': entry['calib']}
-    blobs.update(gt_blobs(entry, np.asarray(bev).shape))
-    if entry.get('flipped', False):
+    cloud = None
+    if cfg.LIDAR_BV_FROM_SCAN and 'lidar_bv' not in entry:
+        # no stored map: the scan is uploaded once (a mirrored frame's with y negated, whose raster IS the column-reversed map:
+        # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror) and rasterised on the device
+        cloud = ops._dev(_entry_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv'))
+        blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': ops.point_cloud_2_top_batch(cloud)[None], 'calib': entry['calib']}
+        blobs.update(gt_blobs(entry, ops.BEV_SHAPE))
+        if entry.get('flipped', False):
+            blobs['image_data'] = ops.mirror_columns(ops._dev(blobs['image_data']))
+    else:
+        bev = entry['lidar_bv'] if 'lidar_bv' in entry else np.load(entry['lidar_bv_path'])
+        blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': np.asarray(bev)[None], 'calib': entry['calib']}
+        blobs.update(gt_blobs(entry, np.asarray(bev).shape))
+    if cloud is None and entry.get('flipped', False):
         # a mirrored frame (kitti_mv3d.append_flipped_images): the files are the source frame's, the entry's ground truth and
         # calibration are the mirror's already; the two maps are uploaded and mirrored on the device (ops.mirror_columns) and
         # go to the network as device tensors.  The BEV raster's mirror axis is its column 300 (datasets/mirror.py).
@@ -75,5 +97,5 @@ def get_minibatch(roidb, num_classes):
         for k in ('image_data', 'lidar_bv_data'):
             blobs[k] = ops.mirror_columns(ops._dev(blobs[k]))
     if cfg.FRONT_VIEW_INPUT:
-        blobs['lidar_fv_data'] = front_view_blob(entry)
+        blobs['lidar_fv_data'] = front_view_blob(entry, cloud)
     return blobs

@@ -3,15 +3,18 @@ per image and keeps `rois[:, 1:]`).  Here the network runs over groups of equall
 (fast_rcnn.detect_batch.iter_frame_groups, cfg.TEST.BATCH_SIZE frames per forward, fixed ROI rows), every frame's first num_rois
 rows of rois[0] (BEV) and rois[1] (image) stay on the device until the last forward is queued; only then are they read back.  The result feeds datasets.proposal_recall.evaluate_recall.
 With `with_3d=True` the rows of rois[2] (the x, y, z, l, w, h LIDAR boxes) are kept as well, for
-datasets.proposal_recall_3d.evaluate_recall_3d."""
+datasets.proposal_recall_3d.evaluate_recall_3d.
+The frames' scans enter as in detect_batch.test_net: a three-view network gets `lidar_fv_data` rasterised from them, and with
+cfg.LIDAR_BV_FROM_SCAN `lidar_bv_data` is rasterised from them too and no stored BEV map is opened (`detect_batch.scan_feed`)."""
 import os
 import pickle
 
 import numpy as np
 import torch
 
+from .. import ops
 from ..fast_rcnn.config import cfg, get_output_dir
-from ..fast_rcnn.detect_batch import _load_frame, iter_frame_groups
+from ..fast_rcnn.detect_batch import _load_frame, iter_frame_groups, loop_scan_source, scan_feed
 
 
 def imdb_proposals(sess, net, imdb, with_3d=False):
@@ -24,25 +27,29 @@ def imdb_proposals(sess, net, imdb, with_3d=False):
         net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
         net.mfma_trunk = bool(cfg.TEST.get("MFMA_TRUNK", False))
     num_images = len(imdb.image_index)
+    points_of, from_scan = loop_scan_source(net, imdb)
+    three_views = getattr(net, "views", 2) == 3
     pending = {}
 
     def keys():
         for i in range(num_images):
-            pending[i] = _load_frame(imdb, i)
-            yield (np.shape(pending[i][0]), np.shape(pending[i][1]))
+            pending[i] = _load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
+            yield (np.shape(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
 
     kept = []                                                  # per group: (frames, cap, rois_bv, rois_img, num_rois, status, rois_3d), on the device
     for group in iter_frame_groups(keys(), batch_size):
-        ims, bvs, calibs = zip(*(pending.pop(i) for i in group))
+        ims, bvs, calibs, clouds = zip(*(pending.pop(i) for i in group))
         B = len(group)
         im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
-        bv_blob = np.stack([np.asarray(bv, np.float32) for bv in bvs])
-        im_info = np.array([[bv_blob.shape[1], bv_blob.shape[2], 1]] * B, dtype=np.float32)
+        feed = {"image_data": im_blob, "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
+        if not from_scan:
+            feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
+        feed.update(scan_feed(clouds, from_scan, three_views))  # the group's scans back to back: one upload, one call per view
+        feed["im_info"] = np.array([[feed["lidar_bv_data"].shape[1], feed["lidar_bv_data"].shape[2], 1]] * B, dtype=np.float32)
         net.fixed_rois = True
         try:
             with torch.no_grad():
-                L = net.forward({"image_data": im_blob, "lidar_bv_data": bv_blob, "im_info": im_info,
-                                 "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0})
+                L = net.forward(feed)
         finally:
             net.fixed_rois = False
         kept.append((group, int(L["rois_per_frame"]), L["rois"][0][:, 1:5].clone(), L["rois"][1][:, 1:5].clone(), L["num_rois"].clone(),
