@@ -456,7 +456,12 @@ int mv3d_proposal_target_stage2_batch_devn(int batch, const float *const *rois_b
  * res=0.1, zres=0.3, side_range=(-30,30), fwd_range=(0,60), height_range=(-2,0.4):
  * tools/read_lidar.py:121-133).  points_dev (P,4) f32 [x,y,z,reflectance], 16-byte aligned;
  * top_dev (601,601,9) f32: channels 0-7 = z + 2 of the last point of each height slice, channel
- * 8 = reflectance of the last point of the highest slice (numpy fancy-assignment order). */
+ * 8 = reflectance of the last point of the highest slice (numpy fancy-assignment order).
+ * This entry and mv3d_point_cloud_2_top_ranges are the body of mv3d_point_cloud_2_top_batch below on ONE frame (offsets_dev == NULL,
+ * num_frames == 1; csrc/bev_raster.hip): the same three launches, the clear alone with num_points == 0.  Their own refusals, decided
+ * before any launch (MV3D_ERR_INVALID_ARG): num_points < 0 or >= 2^27 (a refusal, where the batched entry skips the rows behind),
+ * NULL top_dev, NULL points_dev with num_points > 0, points_dev or top_dev not 16-byte aligned (the batched entry takes a 4-byte
+ * aligned top_dev). */
 int mv3d_point_cloud_2_top(const float *points_dev, int num_points, float *top_dev, void *stream);
 
 /* The same function with its own parameters (lib/utils/read_lidar.py:10-16: res, zres, side_range, fwd_range, height_range).
@@ -464,7 +469,7 @@ int mv3d_point_cloud_2_top(const float *points_dev, int num_points, float *top_d
  * mv3d_point_cloud_2_top_ranges: top_dev of that shape; *status_dev (one int32 on the device, written by the call) becomes 1 when a
  * point's cell falls outside the map after numpy's wrap of negative indices -- where the reference's fancy assignment raises
  * IndexError (the point is skipped here; the host mirror raises).  MV3D_ERR_INVALID_ARG: empty or inverted ranges, more than
- * 32767 cells per axis or more than 31 height slices, P >= 2^27. */
+ * 32767 cells per axis or more than 31 height slices, NULL status_dev, and what mv3d_point_cloud_2_top refuses. */
 int mv3d_point_cloud_2_top_shape(double res, double zres, double side_lo, double side_hi, double fwd_lo, double fwd_hi,
                                  double height_lo, double height_hi, int *dims);
 int mv3d_point_cloud_2_top_ranges(const float *points_dev, int num_points, double res, double zres, double side_lo, double side_hi,
@@ -472,7 +477,7 @@ int mv3d_point_cloud_2_top_ranges(const float *points_dev, int num_points, doubl
                                   int *status_dev, void *stream);
 
 /* The same rasteriser for `num_frames` clouds behind three launches (clear, scatter, resolve; the clear alone with total_points == 0),
- * whatever num_frames is (csrc/bev_raster_batch.hip).  Frame b of the output equals, bit for bit, what
+ * whatever num_frames is (csrc/bev_raster.hip).  Frame b of the output equals, bit for bit, what
  * mv3d_point_cloud_2_top (ranges8_host == NULL) or mv3d_point_cloud_2_top_ranges writes for that frame's rows alone.
  *   points_dev    (total_points, 4) f32 [x, y, z, reflectance], the frames' clouds concatenated, 16-byte aligned (rows are read as
  *                 16-byte vectors); total_points up to INT_MAX
@@ -494,8 +499,8 @@ int mv3d_point_cloud_2_top_ranges(const float *points_dev, int num_points, doubl
  * outside [0, MV3D_FV_MAX_FRAMES], negative total_points, NULL or misaligned pointers, offsets_dev == NULL with num_frames != 1,
  * ranges mv3d_point_cloud_2_top_shape refuses, ranges without status_dev.
  * mv3d_point_cloud_2_top_batch is the entry: its resolve stores only the 16-byte vectors a point fell into (an empty key is
- * already 0.0f).  mv3d_point_cloud_2_top_batch_dense is the same call with a resolve that stores every element, as the single-cloud
- * kernel's does: the same bits, 1.5 - 3 % slower where it was measured, and there for tools/bev_batch_bench.py to
+ * already 0.0f).  mv3d_point_cloud_2_top_batch_dense is the same call with a resolve that stores every element:
+ * the same bits, 1.5 - 3 % slower where it was measured, and there for tools/bev_batch_bench.py to
  * time against the entry -- nothing else calls it. */
 int mv3d_point_cloud_2_top_batch(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
                                  const double *ranges8_host, float *top_dev, int32_t *status_dev, void *stream);

@@ -1,14 +1,17 @@
-// Batched BEV rasteriser: `num_frames` Velodyne clouds back to back -> (num_frames, H, W, C) maps behind three
-// launches -- clear, scatter, resolve -- whatever the batch.  Frame b of the output equals, bit for bit, what the single-cloud
-// kernels of next_rows.hip (point_cloud_2_top, lib/utils/read_lidar.py:10-115) write for that frame's rows alone: the filters,
-// the cell arithmetic and the slice tests below are theirs, statement for statement, and so is the winner rule,
-//   channels < z_max : key = index + 1                         atomicMax: the LAST point in point order wins
-//   channel z_max    : key = slice << 27 | (index + 1)         the last slice, then the last point
-// with keys living in the output buffer itself (as u32) until the resolve replaces them by values.  What differs:
-//   frames   frame b owns rows offsets[b] .. offsets[b + 1] of the concatenated clouds.  The rule is fv_scatter_kernel's
-//            (front_view_raster.hip): the offsets are staged in LDS, the frame of row p is the LAST b with offsets[b] <= p, and a row
-//            outside [offsets[b], offsets[b + 1]) -- in front of offsets[0], behind offsets[num_frames], or anything under offsets
-//            that do not ascend -- belongs to no frame and is skipped.
+// BEV rasteriser: point_cloud_2_top (lib/utils/read_lidar.py:10-115 == tools/read_lidar.py:10-115, ranges
+// tools/read_lidar.py:121-123) for `num_frames` Velodyne clouds back to back -> (num_frames, H, W, C) maps behind three launches --
+// clear, scatter, resolve -- whatever the batch.  The single-cloud entries are this body with one frame and no offsets.
+// The reference assigns top[y, x, i] = z - height_range[0] and top[y, x, z_max] = reflectance slice by slice with numpy fancy
+// indexing: among the points that hit the same (cell, slice) the LAST one in point order wins, and for the reflectance channel the
+// last slice then the last point.  Deterministic here via atomicMax on keys written into the output buffer itself (as u32) until the
+// resolve replaces them by values:
+//   channels < z_max : key = index + 1
+//   channel z_max    : key = slice << 27 | (index + 1)         (at most 32 slices)
+// (a height written to channel z_max -- possible when (h1 - h0) / zres is not an integer -- is always overwritten by the same
+// iteration's reflectance, read_lidar.py:109-112, so that channel only ever shows the reflectance).
+// HBM-bound: one clear of the maps, P scattered atomics, one read of the maps and a write of the vectors a point fell into.
+//   frames   frame b owns rows offsets[b] .. offsets[b + 1] of the concatenated clouds; frame_rows.h has the rule, and a row that
+//            belongs to no frame is skipped.  Frame b of the output equals, bit for bit, the map of that frame's rows alone.
 //   index    the key holds the row's index WITHIN ITS FRAME, p - offsets[b], so the order is per frame and the 27 bits bound a
 //            frame (2^27 - 2 rows: a row further into its frame than that is skipped), not the batch: total_points goes to INT_MAX.
 //   resolve  turns a key back into the global row offsets[b] + index.  A key is only ever written by a row p that passed
@@ -19,16 +22,39 @@
 //            make the call read or write out of bounds.
 //   traffic  an empty key is already the bit pattern of 0.0f, so the resolve stores only where a key is not zero (at 120 000 points
 //            at most 240 000 of 3 250 809 elements), at the granularity it loads at: a 16-byte vector of four keys is stored whole when
-//            any of the four is set and not at all otherwise -- 13 MB less written per frame than the single-cloud kernel's resolve.
-//            DENSE stores every vector, that kernel's way at four times its width, and gives the same bits; measured with the output
-//            buffers traded between the two it is 1.5 - 3 % slower.  It is exported as
-//            mv3d_point_cloud_2_top_batch_dense for tools/bev_batch_bench.py alone, which times the two against each other.
+//            any of the four is set and not at all otherwise -- 13 MB less written per frame than a resolve that stores every element.
+//            DENSE stores every vector and gives the same bits; measured with the output buffers traded between the two it is
+//            1.5 - 3 % slower.  It is exported as mv3d_point_cloud_2_top_batch_dense for tools/bev_batch_bench.py
+//            alone, which times the two against each other.
 //   layout   one frame of the MV3D map is 13 003 236 bytes = 4 mod 16, so inside a batch only every fourth frame starts on a
 //            16-byte boundary.  Clear and resolve therefore run over the FLAT range of num_frames * H * W * C elements: `head` scalar
-//            elements up to the first 16-byte boundary of top_dev, 16-byte vectors, `tail` scalar elements.  top_dev needs 4-byte
-//            alignment only.  All element indices are 64-bit (1024 frames x 3 250 809 elements > 2^31).
+//            elements up to the first 16-byte boundary of top_dev, 16-byte vectors, `tail` scalar elements.  The body needs 4-byte
+//            alignment of top_dev only.  All element indices are 64-bit (1024 frames x 3 250 809 elements > 2^31).
 #include "common.h"
-#include "bev_params.h"
+#include "frame_rows.h"
+
+// The rasteriser's parameters, host arithmetic; the kernels take the struct by value.  The dtypes numpy gives every step (f32 range
+// tests against Python floats, f64 slice tests against np.arange's values, which are h0, h0 + zres, h0 + i * ((h0 + zres) - h0), ...)
+// are spelled out in oracle/mv3d_oracle.c:mv3d_ref_point_cloud_2_top_ranges.
+struct BevParams {
+    float fwd0f, fwd1f, ylo, yhi, resf, h0f;
+    double h0, next, delta, zres;
+    int xoff, yoff, Hd, Wd, Cd, nslice, zmax;
+};
+
+static bool bev_params(double res, double zres, double side0, double side1, double fwd0, double fwd1, double h0, double h1, BevParams &q)
+{
+    if (!(res > 0.0) || !(zres > 0.0) || !(side1 > side0) || !(fwd1 > fwd0) || !(h1 >= h0)) return false;
+    const double nx = (side1 - side0) / res, ny = (fwd1 - fwd0) / res, nz = (h1 - h0) / zres;
+    if (!(nx < 32768.0) || !(ny < 32768.0) || !(nz < 31.0)) return false;       // (the key of the last channel holds 5 bits of slice)
+    const int x_max = (int)nx, y_max = (int)ny, z_max = (int)nz;                 // read_lidar.py:49-51
+    q.Wd = x_max + 1; q.Hd = y_max + 1; q.Cd = z_max + 1; q.zmax = z_max;
+    q.xoff = (int)floor(side0 / res); q.yoff = (int)floor(fwd1 / res);
+    q.nslice = (int)ceil(nz);
+    q.h0 = h0; q.next = h0 + zres; q.delta = q.next - h0; q.zres = zres;
+    q.fwd0f = (float)fwd0; q.fwd1f = (float)fwd1; q.ylo = (float)(-side1); q.yhi = (float)(-side0); q.resf = (float)res; q.h0f = (float)h0;
+    return true;
+}
 
 #define BEVB_MAX_INDEX ((1u << 27) - 2u)       // largest index within a frame: index + 1 stays below 2^27, as mv3d_point_cloud_2_top requires
 
@@ -56,16 +82,11 @@ __global__ __launch_bounds__(256) void bevb_scatter_kernel(const float *__restri
                                                            unsigned *keys, long long n, const BevParams q, int *status)
 {
     __shared__ int s_off[MV3D_FV_MAX_FRAMES + 1];
-    for (int i = threadIdx.x; i <= nf; i += 256) s_off[i] = offsets ? offsets[i] : i * P;      // (no offsets: ONE frame of P rows)
-    __syncthreads();
+    frame_rows_stage(s_off, offsets, nf, P);
     const unsigned p = blockIdx.x * 256u + threadIdx.x;
     if (p >= (unsigned)P) return;
-    int lo = 0, hi = nf - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (s_off[mid] <= (int)p) lo = mid; else hi = mid - 1;
-    }
-    if (!(s_off[lo] <= (int)p && (int)p < s_off[lo + 1])) return;
+    int lo;
+    if (!frame_of_row(s_off, nf, p, lo)) return;
     const unsigned idx = p - (unsigned)s_off[lo];
     if (idx > BEVB_MAX_INDEX) return;
     const float4 v = reinterpret_cast<const float4 *>(pts)[p];
@@ -179,4 +200,35 @@ extern "C" int mv3d_point_cloud_2_top_batch_dense(const float *points_dev, const
                                                   const double *ranges8_host, float *top_dev, int32_t *status_dev, void *stream)
 {
     return bevb_launch(points_dev, offsets_dev, num_frames, total_points, ranges8_host, top_dev, status_dev, (hipStream_t)stream, true);
+}
+
+// The single-cloud entries: the body above on ONE frame of num_points rows, no offsets.  What they refuse beyond it is their own
+// contract (include/mv3d_hip.h), decided here before any launch: a cloud of 2^27 rows or more (the body would skip the rows behind
+// 2^27 - 2), and a map that is not 16-byte aligned.
+static int bev_single(const float *points_dev, int num_points, const double *r, float *top_dev, int *status_dev, void *stream)
+{
+    if (num_points < 0 || num_points >= (1 << 27) || ((uintptr_t)top_dev & 15) != 0) return MV3D_ERR_INVALID_ARG;
+    return bevb_launch(points_dev, nullptr, 1, num_points, r, top_dev, status_dev, (hipStream_t)stream, false);
+}
+
+extern "C" int mv3d_point_cloud_2_top(const float *points_dev, int num_points, float *top_dev, void *stream)
+{
+    return bev_single(points_dev, num_points, nullptr, top_dev, nullptr, stream);
+}
+
+extern "C" int mv3d_point_cloud_2_top_shape(double res, double zres, double side_lo, double side_hi, double fwd_lo, double fwd_hi,
+                                            double height_lo, double height_hi, int *dims)
+{
+    BevParams q;
+    if (!dims || !bev_params(res, zres, side_lo, side_hi, fwd_lo, fwd_hi, height_lo, height_hi, q)) return MV3D_ERR_INVALID_ARG;
+    dims[0] = q.Hd; dims[1] = q.Wd; dims[2] = q.Cd;
+    return MV3D_OK;
+}
+
+extern "C" int mv3d_point_cloud_2_top_ranges(const float *points_dev, int num_points, double res, double zres, double side_lo, double side_hi,
+                                             double fwd_lo, double fwd_hi, double height_lo, double height_hi, float *top_dev,
+                                             int *status_dev, void *stream)
+{
+    const double r[8] = {res, zres, side_lo, side_hi, fwd_lo, fwd_hi, height_lo, height_hi};
+    return bev_single(points_dev, num_points, r, top_dev, status_dev, stream);
 }

@@ -17,6 +17,7 @@
 // depend on the order of arrival, so the map does not depend on scheduling.  Keys live in the caller's workspace (one per
 // pixel and frame, 256 KB a frame); 0xFFFF... (a NaN distance, which no point has) marks an empty pixel.
 #include "front_view.h"
+#include "frame_rows.h"
 
 #define FV_PIXELS (FV_H * FV_W)
 #define FV_EMPTY 0xFFFFFFFFFFFFFFFFull
@@ -29,25 +30,18 @@ __global__ __launch_bounds__(256) void fv_clear_kernel(unsigned long long *keys)
     for (int u = 0; u < 4; ++u) k2[u * 256] = make_ulonglong2(FV_EMPTY, FV_EMPTY);
 }
 
-// One thread per point of the concatenated clouds.  The frame of point p is the LAST b with offsets[b] <= p (a binary search over the
-// offsets staged in LDS; equal neighbours = an empty frame, skipped by that rule); a point outside [offsets[b], offsets[b + 1]) --
-// in front of offsets[0], behind offsets[num_frames], or anything under offsets that do not ascend -- belongs to no frame and is
-// skipped: whatever the offsets hold, p stays below P and the key index inside the workspace.
+// One thread per point of the concatenated clouds; a point that belongs to no frame (frame_rows.h) is skipped: whatever the offsets
+// hold, p stays below P and the key index inside the workspace.
 __global__ __launch_bounds__(256) void fv_scatter_kernel(const float *__restrict__ pts, const int *__restrict__ offsets, int nf, int P,
                                                          unsigned long long *keys)
 {
     __shared__ int s_off[MV3D_FV_MAX_FRAMES + 1];
-    for (int i = threadIdx.x; i <= nf; i += 256) s_off[i] = offsets ? offsets[i] : i * P;      // (no offsets: ONE frame of P rows)
-    __syncthreads();
+    frame_rows_stage(s_off, offsets, nf, P);
     const unsigned p = blockIdx.x * 256u + threadIdx.x;
     if (p >= (unsigned)P) return;
     const float4 v = reinterpret_cast<const float4 *>(pts)[p];
-    int lo = 0, hi = nf - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (s_off[mid] <= (int)p) lo = mid; else hi = mid - 1;
-    }
-    if (!(s_off[lo] <= (int)p && (int)p < s_off[lo + 1])) return;
+    int lo;
+    if (!frame_of_row(s_off, nf, p, lo)) return;
     if (!(fabsf(v.x) <= 3.402823466e+38f && fabsf(v.y) <= 3.402823466e+38f && fabsf(v.z) <= 3.402823466e+38f)) return;   // NaN, +-inf
     if (v.x == 0.0f && v.y == 0.0f) return;
     const double x = (double)v.x, y = (double)v.y, z = (double)v.z;

@@ -652,6 +652,72 @@ def point_cloud_2_front_workspace_bytes(num_frames=1):
     return int(lib().mv3d_point_cloud_2_front_workspace(int(num_frames)))
 
 
+def _scan_args(fn, points, offsets, frame, out, workspace=None, workspace_bytes=None, frame_rows=None):
+    """The argument checks and uploads that the rasterisers of B clouds back to back share (point_cloud_2_front,
+    point_cloud_2_top_batch; `fn` is the name the messages carry): points (P,4) f32, a device tensor or a numpy array; offsets None
+    (one frame) or (B + 1) int32, whose VALUES are checked only when they come from the host (ascending within [0, P], at most
+    `frame_rows` rows a frame where that is given); every tensor on one HIP device; out (optional) a contiguous f32 tensor of the
+    result's shape; workspace (optional) contiguous uint8 of at least workspace_bytes(B) bytes.  `frame` is the shape of one frame
+    of the result, or a function that gives it, called once the points have passed (the caller's own checks keep their place among
+    these).  TypeError for a wrong dtype, ValueError for a wrong shape, value or device, all before anything is uploaded or
+    allocated.  -> (points on the device, offsets on the device or None, B, P, out, device)"""
+    if isinstance(points, torch.Tensor):
+        if points.dtype != torch.float32:
+            raise TypeError("{}: points must be float32, got {}".format(fn, points.dtype))
+        if not points.is_cuda:
+            raise ValueError("{}: a points tensor must live on the device (pass a numpy array to have it uploaded)".format(fn))
+    else:
+        points = np.asarray(points)
+        if points.dtype != np.float32:
+            raise TypeError("{}: points must be float32, got {}".format(fn, points.dtype))
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("{}: points must be (P, 4) [x, y, z, reflectance], got {}".format(fn, tuple(points.shape)))
+    P = int(points.shape[0])
+    if callable(frame):
+        frame = frame()
+    shape = frame
+    if offsets is not None:
+        if isinstance(offsets, torch.Tensor):
+            if offsets.dtype != torch.int32:
+                raise TypeError("{}: an offsets tensor must be int32, got {}".format(fn, offsets.dtype))
+        else:
+            offsets = np.asarray(offsets)
+            if not np.issubdtype(offsets.dtype, np.integer):
+                raise TypeError("{}: offsets must be integers, got {}".format(fn, offsets.dtype))
+            if offsets.ndim == 1 and offsets.size and (np.any(np.diff(offsets) < 0) or offsets[0] < 0 or offsets[-1] > P):
+                raise ValueError("{}: offsets must ascend within [0, {}], got {}".format(fn, P, offsets.tolist()))
+            if frame_rows is not None and offsets.ndim == 1 and offsets.size > 1 and np.diff(offsets).max() > frame_rows:
+                raise ValueError("{}: a frame holds at most {} rows".format(fn, frame_rows))
+        if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
+            raise ValueError("{}: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(fn, FV_MAX_FRAMES, tuple(offsets.shape)))
+        shape = (int(offsets.shape[0]) - 1,) + frame
+    elif frame_rows is not None and P > frame_rows:
+        raise ValueError("{}: a frame holds at most {} rows".format(fn, frame_rows))
+    B = 1 if offsets is None else shape[0]
+    for name, t, dtype in (("out", out, torch.float32), ("workspace", workspace, torch.uint8)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype):
+            raise TypeError("{}: {} must be a {} tensor".format(fn, name, dtype))
+    # one device for every tensor handed in (a numpy cloud goes where they are; with none of them, to the current device)
+    tensors = [(n, t) for n, t in (("points", points), ("offsets", offsets), ("out", out), ("workspace", workspace)) if isinstance(t, torch.Tensor)]
+    for name, t in tensors:
+        if not t.is_cuda or t.device != tensors[0][1].device:
+            raise ValueError("{}: {} on {}: every tensor must live on one HIP device".format(fn, name, t.device))
+        if name in ("out", "workspace") and not t.is_contiguous():
+            raise ValueError("{}: {} must be contiguous".format(fn, name))
+    dev = tensors[0][1].device if tensors else "cuda"
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError("{}: out must be {}, got {}".format(fn, shape, tuple(out.shape)))
+    if workspace is not None and workspace.numel() < workspace_bytes(B):
+        raise ValueError("{}: workspace of {} bytes, {} needed".format(fn, workspace.numel(), workspace_bytes(B)))
+    pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
+    off = None                                                # (one frame: the entries take NULL offsets, nothing to upload)
+    if offsets is not None:
+        off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    return pts, off, B, P, out, dev
+
+
 def point_cloud_2_front(points, offsets=None, out=None, workspace=None):
     """points (P,4) f32 [x,y,z,reflectance] (a device tensor, or a numpy array, which is uploaded) -> the (64,512,3) f32 front-view
     map [height, distance, intensity] on the device (csrc/front_view_raster.hip, DESIGN.md section 3.21: nearest point per pixel,
@@ -664,57 +730,9 @@ def point_cloud_2_front(points, offsets=None, out=None, workspace=None):
     int32 words on the device).  The VALUES of offsets are checked (ascending, within [0, P]) only when they come from the host:
     reading a device tensor would synchronise.  Under malformed device offsets the call stays inside its buffers and silently skips
     the rows no frame owns (include/mv3d_hip.h)."""
-    if isinstance(points, torch.Tensor):
-        if points.dtype != torch.float32:
-            raise TypeError("point_cloud_2_front: points must be float32, got {}".format(points.dtype))
-        if not points.is_cuda:
-            raise ValueError("point_cloud_2_front: a points tensor must live on the device (pass a numpy array to have it uploaded)")
-    else:
-        points = np.asarray(points)
-        if points.dtype != np.float32:
-            raise TypeError("point_cloud_2_front: points must be float32, got {}".format(points.dtype))
-    if points.ndim != 2 or points.shape[1] != 4:
-        raise ValueError("point_cloud_2_front: points must be (P, 4) [x, y, z, reflectance], got {}".format(tuple(points.shape)))
-    P = int(points.shape[0])
-    shape = FV_SHAPE
-    if offsets is not None:
-        if isinstance(offsets, torch.Tensor):
-            if offsets.dtype != torch.int32:
-                raise TypeError("point_cloud_2_front: an offsets tensor must be int32, got {}".format(offsets.dtype))
-        else:
-            offsets = np.asarray(offsets)
-            if not np.issubdtype(offsets.dtype, np.integer):
-                raise TypeError("point_cloud_2_front: offsets must be integers, got {}".format(offsets.dtype))
-            if offsets.ndim == 1 and offsets.size and (np.any(np.diff(offsets) < 0) or offsets[0] < 0 or offsets[-1] > P):
-                raise ValueError("point_cloud_2_front: offsets must ascend within [0, {}], got {}".format(P, offsets.tolist()))
-        if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
-            raise ValueError("point_cloud_2_front: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(FV_MAX_FRAMES, tuple(offsets.shape)))
-        shape = (int(offsets.shape[0]) - 1,) + FV_SHAPE
-    B = 1 if offsets is None else shape[0]
-    for name, t, dtype in (("out", out, torch.float32), ("workspace", workspace, torch.uint8)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype):
-            raise TypeError("point_cloud_2_front: {} must be a {} tensor".format(name, dtype))
-    # one device for every tensor handed in (a numpy cloud goes where they are; with none of them, to the current device)
-    tensors = [(n, t) for n, t in (("points", points), ("offsets", offsets), ("out", out), ("workspace", workspace)) if isinstance(t, torch.Tensor)]
-    for name, t in tensors:
-        if not t.is_cuda or t.device != tensors[0][1].device:
-            raise ValueError("point_cloud_2_front: {} on {}: every tensor must live on one HIP device".format(name, t.device))
-        if name in ("out", "workspace") and not t.is_contiguous():
-            raise ValueError("point_cloud_2_front: {} must be contiguous".format(name))
-    dev = tensors[0][1].device if tensors else "cuda"
-    if out is not None and tuple(out.shape) != shape:
-        raise ValueError("point_cloud_2_front: out must be {}, got {}".format(shape, tuple(out.shape)))
-    need = point_cloud_2_front_workspace_bytes(B)
-    if workspace is not None and workspace.numel() < need:
-        raise ValueError("point_cloud_2_front: workspace of {} bytes, {} needed".format(workspace.numel(), need))
-    pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
-    off = None                                                # (one frame: the entry takes NULL offsets, nothing to upload)
-    if offsets is not None:
-        off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    pts, off, B, P, out, dev = _scan_args("point_cloud_2_front", points, offsets, FV_SHAPE, out, workspace, point_cloud_2_front_workspace_bytes)
     if workspace is None:
-        workspace = _workspace(need, dev, "fv_raster")
+        workspace = _workspace(point_cloud_2_front_workspace_bytes(B), dev, "fv_raster")
     check(lib().mv3d_point_cloud_2_front(_ptr(pts), _ptr(off), B, P, _ptr(out), _ptr(workspace), _stream()), "mv3d_point_cloud_2_front")
     return out
 
@@ -724,7 +742,7 @@ BEV_MAX_FRAME_POINTS = (1 << 27) - 1  # rows per frame (the winner key holds the
 
 
 def point_cloud_2_top_batch(points, offsets=None, ranges=None, out=None):
-    """point_cloud_2_top for B clouds behind three launches (csrc/bev_raster_batch.hip), argument for argument
+    """point_cloud_2_top for B clouds behind three launches (csrc/bev_raster.hip), argument for argument
     ops.point_cloud_2_front: points (P,4) f32 [x,y,z,reflectance] (a device tensor, or a numpy array, which is uploaded) is B clouds
     back to back, offsets = (B + 1) ascending int32 row offsets (host sequence / array, or a device tensor), frame b owns rows
     offsets[b]:offsets[b + 1]; the result is (B,601,601,9) f32 on the device -- (601,601,9) without offsets, one frame -- and frame b
@@ -737,62 +755,19 @@ def point_cloud_2_top_batch(points, offsets=None, ranges=None, out=None):
     VALUES of offsets are checked (ascending, within [0, P], at most 2^27 - 1 rows a frame) only when they come from the host:
     reading a device tensor would synchronise.  Under malformed device offsets the call stays inside its buffers and silently skips
     the rows no frame owns (include/mv3d_hip.h)."""
-    if isinstance(points, torch.Tensor):
-        if points.dtype != torch.float32:
-            raise TypeError("point_cloud_2_top_batch: points must be float32, got {}".format(points.dtype))
-        if not points.is_cuda:
-            raise ValueError("point_cloud_2_top_batch: a points tensor must live on the device (pass a numpy array to have it uploaded)")
-    else:
-        points = np.asarray(points)
-        if points.dtype != np.float32:
-            raise TypeError("point_cloud_2_top_batch: points must be float32, got {}".format(points.dtype))
-    if points.ndim != 2 or points.shape[1] != 4:
-        raise ValueError("point_cloud_2_top_batch: points must be (P, 4) [x, y, z, reflectance], got {}".format(tuple(points.shape)))
-    P = int(points.shape[0])
-    frame, r = BEV_SHAPE, None
-    if ranges is not None:
+    r = None
+
+    def frame():
+        nonlocal r
+        if ranges is None:
+            return BEV_SHAPE
         r = (C.c_double * 8)(*[float(v) for v in ranges])     # (anything but 8 numbers: ctypes / float raise TypeError or ValueError here)
         dims = (C.c_int * 3)()
         if lib().mv3d_point_cloud_2_top_shape(*r, dims) != _lib.OK:
             raise ValueError("point_cloud_2_top_batch: ranges {} are empty, inverted or beyond 32767 cells / 31 slices".format(tuple(r)))
-        frame = tuple(dims)
-    shape = frame
-    if offsets is not None:
-        if isinstance(offsets, torch.Tensor):
-            if offsets.dtype != torch.int32:
-                raise TypeError("point_cloud_2_top_batch: an offsets tensor must be int32, got {}".format(offsets.dtype))
-        else:
-            offsets = np.asarray(offsets)
-            if not np.issubdtype(offsets.dtype, np.integer):
-                raise TypeError("point_cloud_2_top_batch: offsets must be integers, got {}".format(offsets.dtype))
-            if offsets.ndim == 1 and offsets.size and (np.any(np.diff(offsets) < 0) or offsets[0] < 0 or offsets[-1] > P):
-                raise ValueError("point_cloud_2_top_batch: offsets must ascend within [0, {}], got {}".format(P, offsets.tolist()))
-            if offsets.ndim == 1 and offsets.size > 1 and np.diff(offsets).max() > BEV_MAX_FRAME_POINTS:
-                raise ValueError("point_cloud_2_top_batch: a frame holds at most {} rows".format(BEV_MAX_FRAME_POINTS))
-        if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
-            raise ValueError("point_cloud_2_top_batch: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(FV_MAX_FRAMES, tuple(offsets.shape)))
-        shape = (int(offsets.shape[0]) - 1,) + frame
-    elif P > BEV_MAX_FRAME_POINTS:
-        raise ValueError("point_cloud_2_top_batch: a frame holds at most {} rows".format(BEV_MAX_FRAME_POINTS))
-    B = 1 if offsets is None else shape[0]
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
-        raise TypeError("point_cloud_2_top_batch: out must be a {} tensor".format(torch.float32))
-    # one device for every tensor handed in (a numpy cloud goes where they are; with none of them, to the current device)
-    tensors = [(n, t) for n, t in (("points", points), ("offsets", offsets), ("out", out)) if isinstance(t, torch.Tensor)]
-    for name, t in tensors:
-        if not t.is_cuda or t.device != tensors[0][1].device:
-            raise ValueError("point_cloud_2_top_batch: {} on {}: every tensor must live on one HIP device".format(name, t.device))
-        if name == "out" and not t.is_contiguous():
-            raise ValueError("point_cloud_2_top_batch: out must be contiguous")
-    dev = tensors[0][1].device if tensors else "cuda"
-    if out is not None and tuple(out.shape) != shape:
-        raise ValueError("point_cloud_2_top_batch: out must be {}, got {}".format(shape, tuple(out.shape)))
-    pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
-    off = None                                                # (one frame: the entry takes NULL offsets, nothing to upload)
-    if offsets is not None:
-        off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        return tuple(dims)
+
+    pts, off, B, P, out, dev = _scan_args("point_cloud_2_top_batch", points, offsets, frame, out, frame_rows=BEV_MAX_FRAME_POINTS)
     status = None if r is None else torch.empty(1, dtype=torch.int32, device=dev)
     check(lib().mv3d_point_cloud_2_top_batch(_ptr(pts), _ptr(off), B, P, r, _ptr(out), _ptr(status), _stream()), "mv3d_point_cloud_2_top_batch")
     if status is not None and int(status.item()):

@@ -11,7 +11,7 @@ import front_view_raster_restatement as R
 from mv3d_tf_amd import synth
 
 F32 = np.float32
-P_GROUP = 256                      # threads per workgroup of the scatter kernel (csrc/bev_raster_batch.hip)
+P_GROUP = 256                      # threads per workgroup of the scatter kernel (csrc/bev_raster.hip)
 NAN, INF = float("nan"), float("inf")
 
 
@@ -181,6 +181,24 @@ def test_point_cloud_2_top_batch_refuses_bad_arguments_before_any_launch():
         assert fn(None, None, 0, 0, None, None, None, None) == lib.OK                # no frame: nothing to do
 
 
+def test_single_cloud_entries_refuse_bad_arguments_before_any_launch():
+    """mv3d_point_cloud_2_top / _ranges are the batched body on one frame and keep their own refusals (include/mv3d_hip.h): 2^27 rows
+    or more, and a map that is not 16-byte aligned, which the batched entry takes"""
+    from mv3d_tf_amd import build
+    build.build()
+    from mv3d_tf_amd import ops
+    L, lib = ops.lib(), ops._lib
+    A = 4096                                                                         # a non-NULL, aligned "pointer" (never dereferenced)
+    odd = ranges_args(synth.BEV_RANGE_CASES["odd"])
+    cases = ((A, -1, A), (A, 1 << 27, A), (None, 4, A), (A, 4, None), (A + 4, 4, A), (A, 4, A + 4))
+    for pts, P, top in cases:
+        assert L.mv3d_point_cloud_2_top(pts, P, top, None) == lib.ERR_INVALID_ARG, (pts, P, top)
+        assert L.mv3d_point_cloud_2_top_ranges(pts, P, *odd, top, A, None) == lib.ERR_INVALID_ARG, (pts, P, top)
+    assert L.mv3d_point_cloud_2_top_ranges(A, 4, *odd, A, None, None) == lib.ERR_INVALID_ARG             # no status word
+    for bad in ((0.1, 0.3, 30., -30., 0., 60., -2., 0.4), (0.1, 0.001, -30., 30., 0., 60., -2., 0.4)):   # inverted; 2400 slices
+        assert L.mv3d_point_cloud_2_top_ranges(A, 4, *bad, A, A, None) == lib.ERR_INVALID_ARG, bad
+
+
 # ---------------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
 @pytest.mark.parametrize("P", [0, 1, P_GROUP - 1, P_GROUP, P_GROUP + 1])
@@ -312,6 +330,34 @@ def test_keys_in_the_scalar_head_and_tail(gpu, oracle):
         assert np.array_equal(bits(host[lo:hi]), bits(want[lo:hi])) and (host[:lo] == -7).all() and (host[hi:] == -7).all()
 
 
+def outside_case(oracle):
+    """(ranges, a handful of rows inside them, the same rows and one whose cell lies outside the map: numpy's IndexError)"""
+    # fwd_range = (0.05, 10): y_max = int(9.95 / 0.1) = 99, but a point with 0.05 < x < 0.1 lands on row int(-x / 0.1) + 100 = 100
+    case = (0.1, 0.3, (-10., 10.), (0.05, 10.), (-2., 0.4))
+    inside = kept_rows(9, 400)
+    inside = inside[(inside[:, 0] > 0.2) & (inside[:, 0] < 10) & (np.abs(inside[:, 1]) < 10)]
+    assert len(inside) >= 8
+    outside = np.concatenate([inside, F32([[0.07, 1.0, -1.0, 0.5]])])
+    assert oracle.point_cloud_2_top(inside, *case).any()
+    with pytest.raises(IndexError):
+        oracle.point_cloud_2_top(outside, *case)
+    return case, inside, outside
+
+
+@pytest.mark.gpu
+def test_single_ranges_entry_resolves_the_scalar_tail(gpu, oracle):
+    """ops.point_cloud_2_top(ranges=...) into its own 16-byte aligned (81, 39, 5) map: 15 795 elements = no head, 3 948 vectors and a
+    tail of 3, which holds keys (channels 2-4 of the last cell) that are resolved, not only cleared"""
+    torch, ops = gpu["torch"], gpu["ops"]
+    pts = corner_frame(90)
+    want = oracle.point_cloud_2_top(pts, *CORNER_CASE)
+    assert want.shape == (81, 39, 5) and want.size % 4 == 3
+    assert (want.reshape(-1)[:3] != 0).all() and (want.reshape(-1)[-3:] != 0).all()
+    got = ops.point_cloud_2_top(torch.from_numpy(pts).cuda(), ranges=ranges_args(CORNER_CASE))
+    assert got.data_ptr() % 16 == 0 and tuple(got.shape) == (81, 39, 5)
+    assert np.array_equal(bits(got.cpu().numpy()), bits(want))
+
+
 @pytest.mark.gpu
 def test_ranges(gpu, oracle):
     torch, ops = gpu["torch"], gpu["ops"]
@@ -322,21 +368,24 @@ def test_ranges(gpu, oracle):
     assert want.shape[-1] == 12
     got = device_maps(gpu, pts, offsets, ranges=ranges_args(case))
     assert got.shape == want.shape and np.array_equal(bits(got), bits(want))
-    # fwd_range = (0.05, 10): y_max = int(9.95 / 0.1) = 99, but a point with 0.05 < x < 0.1 lands on row int(-x / 0.1) + 100 = 100
-    case = (0.1, 0.3, (-10., 10.), (0.05, 10.), (-2., 0.4))
-    inside = kept_rows(9, 400)
-    inside = inside[(inside[:, 0] > 0.2) & (inside[:, 0] < 10) & (np.abs(inside[:, 1]) < 10)]
-    assert len(inside) >= 8
-    outside = np.concatenate([inside, F32([[0.07, 1.0, -1.0, 0.5]])])
-    assert oracle.point_cloud_2_top(inside, *case).any()
-    with pytest.raises(IndexError):
-        oracle.point_cloud_2_top(outside, *case)
+    case, inside, outside = outside_case(oracle)
     pts, offsets = np.concatenate([inside, outside]), np.array([0, len(inside), 2 * len(inside) + 1], np.int32)
     got = device_maps(gpu, inside, ranges=ranges_args(case))                        # (the status word is cleared by every call)
     assert np.array_equal(bits(got), bits(oracle.point_cloud_2_top(inside, *case)))
     with pytest.raises(IndexError, match="point_cloud_2_top_batch"):
         device_maps(gpu, pts, offsets, ranges=ranges_args(case))
     assert np.array_equal(bits(device_maps(gpu, inside, ranges=ranges_args(case))), bits(got))
+
+
+@pytest.mark.gpu
+def test_single_ranges_entry_raises_index_error(gpu, oracle):
+    """ops.point_cloud_2_top(ranges=...) is the batched body on one frame: the status word raises, and every call clears it"""
+    torch, ops = gpu["torch"], gpu["ops"]
+    case, inside, outside = outside_case(oracle)
+    with pytest.raises(IndexError, match="point_cloud_2_top:"):
+        ops.point_cloud_2_top(torch.from_numpy(outside).cuda(), ranges=ranges_args(case))
+    got = ops.point_cloud_2_top(torch.from_numpy(inside).cuda(), ranges=ranges_args(case)).cpu().numpy()
+    assert np.array_equal(bits(got), bits(oracle.point_cloud_2_top(inside, *case)))
 
 
 @pytest.mark.gpu

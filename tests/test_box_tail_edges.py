@@ -1,4 +1,4 @@
-"""The test-time tail of box_detect at its edges: `mv3d_box_detect_tail` (csrc/next_rows.hip), which restates
+"""The test-time tail of box_detect at its edges: `mv3d_box_detect_tail` (csrc/box_tail.hip), which restates
 lib/fast_rcnn/test_mv.py:240-261 = lidar_3d_to_corners, bbox_transform_inv_cnr and corners_to_bv.
 
 One case table (`cases`) feeds three descriptions of the same thing:

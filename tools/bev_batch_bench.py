@@ -1,5 +1,6 @@
-"""Batched BEV rasteriser (ops.point_cloud_2_top_batch, csrc/bev_raster_batch.hip) against what was here
-before it: the single-cloud entry once per frame, and the stored (601, 601, 9) maps a loop used to read from disk.  Scans are
+"""Batched BEV rasteriser (ops.point_cloud_2_top_batch, csrc/bev_raster.hip) against what was here
+before it: the single-cloud entry once per frame (the same body on one frame: three launches a call), and the stored (601, 601, 9)
+maps a loop used to read from disk.  Scans are
 synth.point_cloud(seed, 120000) (the size of a KITTI scan), batches of 1, 2 and 16 frames.  In ONE process, every variant warmed
 up and then timed over --reps windows of >= --seconds each, the variants of a batch alternating and their order rotating from
 window to window:
