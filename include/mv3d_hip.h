@@ -1017,6 +1017,32 @@ int mv3d_proposal_recall_3d_match(const mv3d_recall3d_split *split, const double
  * data with rows > 0, rows < 0, width < 1, channels < 1, or a row of 2^31 elements or more. */
 int mv3d_mirror_columns(float *data_dev, long long rows, int width, int channels, void *stream);
 
+/* ------------------------------------------------------------------ image input (csrc/image_blob.hip)
+ * `num_frames` uint8 BGR frames of their own sizes -> the (num_frames, canvas_h, canvas_w, 3) f32 blob of the image trunk, mean
+ * subtracted, every frame at the top-left corner of a zero canvas (lib/utils/blob.py:14-27, im_list_to_blob), in ONE launch
+ * whatever num_frames is.
+ *   pixels_dev    uint8: the frames' (h_b, w_b, 3) pixels back to back, total_bytes bytes in all (up to INT_MAX).  Byte alignment
+ *                 is all it needs: a frame may start at any byte, and a row is 3 w_b bytes.
+ *   frames_dev    (num_frames, 4) int32 ON THE DEVICE, a row is [byte offset, h, w, flip]: under a captured graph the pixels, the
+ *                 shapes and the flags may change before every replay (total_bytes, the capacity of pixels_dev, stays).
+ *   means3_host   three doubles on the HOST, the per-channel means, read before the call returns
+ *   out_dev       (num_frames, canvas_h, canvas_w, 3) f32 contiguous, 4-byte aligned: it may be any run of frames inside a larger
+ *                 batch buffer (a 375 x 1242 x 3 frame is 8 mod 16 bytes)
+ * For y < h_b and x < w_b: out[b][y][x][c] = (float)((double)src_b[y][x'][c] - means[c]), ONE rounding from f64, with x' = x when
+ * flip is 0 and x' = w_b - 1 - x otherwise (the mirror within the frame's own width: mv3d_mirror_columns of the unpadded frame).
+ * Every other element of the frame's canvas is +0.0f.  Every element of out is written exactly once, padding included: nothing has
+ * to be cleared in front.
+ * A table row is used only if offset >= 0, 1 <= h <= canvas_h, 1 <= w <= canvas_w and offset + 3 h w <= total_bytes (in 64 bits);
+ * the canvas of any other frame is all zeros and its neighbours are what they would be without it.  No value in frames_dev can make
+ * the call read outside pixels_dev[0 : total_bytes] or write outside out.
+ * No allocation, no workspace, no host synchronisation; num_frames == 0 returns MV3D_OK without a launch.  MV3D_ERR_INVALID_ARG
+ * before any launch: num_frames outside [0, MV3D_IMAGE_MAX_FRAMES], negative total_bytes, a canvas side < 1, a canvas of 2^31
+ * elements or more, num_frames * canvas_h above 2^31 - 1 workgroup rows, and with num_frames > 0 a NULL frames_dev, means3_host or
+ * out_dev, a NULL pixels_dev with total_bytes > 0, frames_dev or out_dev not 4-byte aligned. */
+#define MV3D_IMAGE_MAX_FRAMES 1024
+int mv3d_image_blob(const uint8_t *pixels_dev, int total_bytes, const int32_t *frames_dev, int num_frames, const double *means3_host,
+                    int canvas_h, int canvas_w, float *out_dev, void *stream);
+
 /* ------------------------------------------------------------------ the deep-fusion join (csrc/fusion_join.hip)
  * The element-wise mean that joins the views after a fully connected layer of the deep-fusion head (MV3D paper §3.3, Fig. 3c), with
  * the layer's ReLU in front and the join's dropout behind, for `paths` networks at once (the main one and the auxiliary paths).

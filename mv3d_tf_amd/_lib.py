@@ -291,6 +291,7 @@ _SIGS = {
     "mv3d_proposal_recall_3d_overlaps": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P]),
     "mv3d_proposal_recall_3d_match": (C.c_int, [C.POINTER(Recall3dSplit), _P, _P, _P, _P, _P]),
     "mv3d_mirror_columns": (C.c_int, [_P, C.c_longlong, C.c_int, C.c_int, _P]),
+    "mv3d_image_blob": (C.c_int, [_P, C.c_int, _P, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, _P, _P]),
     "mv3d_fusion_join_forward": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P]),
     "mv3d_fusion_join_backward": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, _P, _P]),
     "mv3d_upsample_bilinear_views": (C.c_int, [C.c_int, C.POINTER(UpsampleView), _P]),

@@ -94,6 +94,14 @@ cfg.FRONT_VIEW_INPUT = False
 # records no lidar_bv_path, and get_minibatch, detect_batch.test_net and rpn_msr.generate.imdb_proposals never open a stored map.  With
 # FRONT_VIEW_INPUT also on, both rasters read one upload of the scan.  False = the stored maps, every blob and code path as before.
 cfg.LIDAR_BV_FROM_SCAN = False
+# (not in the reference, which subtracts PIXEL_MEANS on the host, frame by frame, and uploads f32) True: `image_data` is built on the
+# device from ONE upload of the frames' uint8 pixels (ops.image_blob) by get_minibatch, detect_batch.test_net
+# and rpn_msr.generate.imdb_proposals; the two loops then group frames by BEV shape only and pad a group's frames to one canvas, the
+# reference's im_list_to_blob (lib/utils/blob.py:14-27).  IMAGE_CANVAS: None = the group's maximal image shape (get_minibatch: the
+# frame's own), or a fixed (H, W) such as (376, 1242) that every frame is padded to -- what a captured graph and the frames of one
+# training step need; a larger frame raises ValueError.  False = the host expression, every blob and code path as before.
+cfg.IMAGE_BLOB_ON_DEVICE = False
+cfg.IMAGE_CANVAS = None
 cfg.RNG_SEED = 3
 cfg.EPS = 1e-14
 cfg.EXP_DIR = 'default'
@@ -121,6 +129,8 @@ def _merge(a, b, path=""):
             v = np.array(v, dtype=old.dtype)
         elif path + k == "ROI_UPSAMPLE" and isinstance(v, list):  # (YAML has no tuples: its sequence for this one key)
             v = tuple(v)
+        elif path + k == "IMAGE_CANVAS":                          # None or (H, W), a YAML sequence
+            v = None if v is None else tuple(int(s) for s in v)
         elif type(old) is not type(v) and not (isinstance(old, float) and isinstance(v, int)):
             raise ValueError('Type mismatch ({} vs. {}) for config key: {}'.format(type(old), type(v), path + k))
         b[k] = type(old)(v) if isinstance(old, float) else v
@@ -147,7 +157,7 @@ def cfg_from_list(cfg_list):
             value = ast.literal_eval(v)
         except Exception:
             value = v
-        assert type(value) == type(d[keys[-1]]), 'type {} does not match original type {}'.format(
+        assert type(value) == type(d[keys[-1]]) or k == 'IMAGE_CANVAS', 'type {} does not match original type {}'.format(
             type(value), type(d[keys[-1]]))
         d[keys[-1]] = value
 

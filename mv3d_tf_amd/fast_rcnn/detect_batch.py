@@ -117,6 +117,30 @@ def scan_feed(clouds, bev, fv):
     return feed
 
 
+def image_feed(ims, out=None):
+    """`image_data` of a group of frames on the device (cfg.IMAGE_BLOB_ON_DEVICE): the (h, w, 3) uint8 BGR images are packed into ONE
+    byte buffer, uploaded ONCE, and ONE ops.image_blob call subtracts cfg.PIXEL_MEANS and pads every frame at the top-left corner of a
+    zero canvas (lib/utils/blob.py:14-27, im_list_to_blob) -> (B, H, W, 3) f32.  The canvas is cfg.IMAGE_CANVAS, or else the group's
+    maximal height and width; with equally shaped frames and no fixed canvas the result is bit for bit the host expression's blob.
+    out = a contiguous (B, H, W, 3) f32 device tensor to write into; its H and W are then the canvas.  That is the way into a captured
+    ServeGraph, whose image shape is fixed: `image_feed(ims, out=graph.static["image_data"])` under `with torch.cuda.stream(graph.stream):`
+    (the stream the replay runs on) in front of `graph.replay()` serves frames of any size up to the captured one.  TypeError for an image that is not a uint8 array, ValueError for one that is not (h, w, 3)
+    or is larger than the canvas, before anything is uploaded."""
+    canvas = cfg.IMAGE_CANVAS if out is None else tuple(out.shape[1:3])
+    return ops.image_blob(list(ims), canvas=canvas, out=out)
+
+
+def _image_key(im):
+    """what a frame's image adds to its group key: its shape, or nothing under cfg.IMAGE_BLOB_ON_DEVICE (frames are padded to the
+    group's canvas, `image_feed`, so a change of image shape no longer ends a group)"""
+    return None if cfg.IMAGE_BLOB_ON_DEVICE else np.shape(im)
+
+
+def host_image_blob(ims):
+    """the (B, H, W, 3) f32 blob of equally shaped frames as the host builds it (lib/fast_rcnn/test_mv.py:162 per frame)"""
+    return np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
+
+
 class _FeedsFrontView:
     """a network whose forward adds one frame's `lidar_fv_data` to the feed (what box_detect hands test_mv.box_detect, whose feed has
     two views)"""
@@ -183,14 +207,18 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
     ops.point_cloud_2_front call.  cfg.LIDAR_BV_FROM_SCAN: the device route for any BATCH_SIZE, no stored BEV map is opened (`_load_frame`
     touches neither imdb.bv_at nor imdb.lidar_path_at), frames group by image shape and ops.BEV_SHAPE, and a group's `lidar_bv_data` is
     ONE ops.point_cloud_2_top_batch call on the group's scans (`scan_feed`: one upload for both rasters).  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
-    ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
+    ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.
+    cfg.IMAGE_BLOB_ON_DEVICE: the device route for any BATCH_SIZE; frames group by BEV shape only, and a group's `image_data` is ONE
+    uint8 upload and ONE ops.image_blob call that pads the frames to cfg.IMAGE_CANVAS or the group's maximal image shape (`image_feed`;
+    a frame larger than IMAGE_CANVAS raises ValueError before the forward).  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
     group) and the evaluate_detections call are test_mv.test_net's."""
     batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
     oriented = bool(cfg.TEST.get("NMS_ORIENTED", False))
     footprint = cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed")
     points_of, from_scan = loop_scan_source(net, imdb)
     three_views = getattr(net, "views", 2) == 3
-    if batch_size <= 1 and not oriented and points_of is None:
+    on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)
+    if batch_size <= 1 and not oriented and points_of is None and not on_device:
         return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
     if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
         net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
@@ -204,14 +232,14 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
     def keys():
         for i in range(num_images):
             pending[i] = _load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
-            yield (np.shape(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
+            yield (_image_key(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
 
     t_detect = t_misc = 0.0
     for group in iter_frame_groups(keys(), max(batch_size, 1)):
         ims, bvs, calibs, clouds = zip(*(pending.pop(i) for i in group))
         B = len(group)
         t0 = time.time()
-        im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
+        im_blob = image_feed(ims) if on_device else host_image_blob(ims)
         feed = {"image_data": im_blob, "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
         if not from_scan:
             feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])

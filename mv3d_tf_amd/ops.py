@@ -803,6 +803,141 @@ def mirror_columns(t):
     return t
 
 
+# ------------------------------------------------------------------ image input
+IMAGE_MAX_FRAMES = 1024              # MV3D_IMAGE_MAX_FRAMES
+
+
+def pack_image_frames(images):
+    """A list of (h, w, 3) uint8 images -> (pixels, frames, (H, W)): ONE contiguous uint8 host buffer with the frames' pixels back to
+    back, the (B, 4) int32 table [byte offset, h, w, flip = 0] that ops.image_blob takes, and the maximal height and width.
+    TypeError for anything that is not a uint8 array, ValueError for another shape, an empty list or more than INT_MAX bytes."""
+    images = list(images)
+    if not images:
+        raise ValueError("pack_image_frames: no image")
+    for k, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8:
+            raise TypeError("pack_image_frames: image {} must be a uint8 numpy array, got {}".format(
+                k, im.dtype if isinstance(im, np.ndarray) else type(im).__name__))
+        if im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("pack_image_frames: image {} must be (h, w, 3) with h, w >= 1, got {}".format(k, im.shape))
+    frames = np.zeros((len(images), 4), np.int64)
+    frames[:, 1] = [im.shape[0] for im in images]
+    frames[:, 2] = [im.shape[1] for im in images]
+    sizes = 3 * frames[:, 1] * frames[:, 2]
+    frames[1:, 0] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    if total > 0x7fffffff:
+        raise ValueError("pack_image_frames: {} bytes of pixels, at most 2^31 - 1 go into one call".format(total))
+    pixels = np.empty((total,), np.uint8)
+    for im, o, n in zip(images, frames[:, 0], sizes):
+        pixels[o:o + n] = im.reshape(-1)
+    return pixels, frames.astype(np.int32), (int(frames[:, 1].max()), int(frames[:, 2].max()))
+
+
+def _pixel_means():
+    from .fast_rcnn.config import cfg                         # (fast_rcnn imports ops)
+    return cfg.PIXEL_MEANS
+
+
+def image_blob(pixels, frames=None, canvas=None, means=None, flip=None, out=None):
+    """uint8 BGR frames of their own sizes -> the (B, H, W, 3) f32 image blob on the device in ONE launch (csrc/image_blob.hip, DESIGN.md
+    section 3.23): out[b, y, x, c] = float32(float64(frame_b[y, x', c]) - means[c]) at the top-left corner of a canvas of +0.0 (the
+    reference's im_list_to_blob), x' = w_b - 1 - x for a frame whose flip flag is set (the mirror within its own width).
+    pixels   a 1-D uint8 buffer with the frames' pixels back to back, a device tensor or a numpy array (uploaded); or a list of
+             (h, w, 3) uint8 images, packed first (pack_image_frames; frames must then be None)
+    frames   (B, 4) int32 [byte offset, h, w, flip], a device tensor or a host array / sequence (uploaded)
+    canvas   (H, W); None = the frames' maximal height and width, which needs a host table
+    means    three numbers; None = cfg.PIXEL_MEANS
+    flip     a per-frame sequence of flags, folded into a host table's fourth column (a device table carries its own)
+    out      a contiguous f32 device tensor of the result's shape to write into; it may be any slice of frames of a larger batch buffer
+             (4-byte alignment is all it needs).  With device inputs and out= the call allocates nothing and can be captured.
+    Every argument is checked before anything is uploaded or launched: TypeError for a dtype other than uint8 / int32 / f32,
+    ValueError for shapes, devices, a frame larger than the canvas or a table that does not fit `pixels`.  The VALUES of the table are
+    checked only when it comes from the host: reading a device tensor would synchronise.  Under a malformed device table the call stays
+    inside its buffers and the frames it cannot use come out as zeros (include/mv3d_hip.h).  There is no torch path."""
+    fn = "image_blob"
+    if isinstance(pixels, (list, tuple)):
+        if frames is not None:
+            raise ValueError("{}: a list of images brings its own table, frames must be None".format(fn))
+        pixels, frames, _ = pack_image_frames(pixels)
+    if frames is None:
+        raise ValueError("{}: frames, the (B, 4) int32 table [byte offset, h, w, flip], is required".format(fn))
+    if isinstance(pixels, torch.Tensor):
+        if pixels.dtype != torch.uint8:
+            raise TypeError("{}: pixels must be uint8, got {}".format(fn, pixels.dtype))
+        if not pixels.is_cuda:
+            raise ValueError("{}: a pixels tensor must live on the device (pass a numpy array to have it uploaded)".format(fn))
+    else:
+        pixels = np.asarray(pixels)
+        if pixels.dtype != np.uint8:
+            raise TypeError("{}: pixels must be uint8, got {}".format(fn, pixels.dtype))
+    if pixels.ndim != 1 or (isinstance(pixels, torch.Tensor) and not pixels.is_contiguous()):
+        raise ValueError("{}: pixels must be one contiguous run of bytes, got shape {}".format(fn, tuple(pixels.shape)))
+    total = int(pixels.shape[0])
+    if total > 0x7fffffff:
+        raise ValueError("{}: {} bytes of pixels, at most 2^31 - 1 go into one call".format(fn, total))
+    host_table = not isinstance(frames, torch.Tensor)
+    if host_table:
+        frames = np.asarray(frames)
+        if not np.issubdtype(frames.dtype, np.integer):
+            raise TypeError("{}: frames must be integers, got {}".format(fn, frames.dtype))
+    elif frames.dtype != torch.int32:
+        raise TypeError("{}: a frames tensor must be int32, got {}".format(fn, frames.dtype))
+    if frames.ndim != 2 or frames.shape[1] != 4 or not 1 <= frames.shape[0] <= IMAGE_MAX_FRAMES:
+        raise ValueError("{}: frames must be (B, 4) with 1 <= B <= {}, got {}".format(fn, IMAGE_MAX_FRAMES, tuple(frames.shape)))
+    B = int(frames.shape[0])
+    if flip is not None:
+        if not host_table:
+            raise ValueError("{}: flip= is folded into a host table; a device table carries the flags in its fourth column".format(fn))
+        flags = np.asarray(flip).reshape(-1)
+        if flags.shape[0] != B:
+            raise ValueError("{}: flip must have one flag per frame ({}), got {}".format(fn, B, flags.shape[0]))
+        frames = frames.astype(np.int64)
+        frames[:, 3] = flags != 0
+    if canvas is None:
+        if not host_table:
+            raise ValueError("{}: canvas=None (the frames' maximal shape) needs a host table; give canvas=(H, W)".format(fn))
+        canvas = (int(frames[:, 1].max()), int(frames[:, 2].max()))
+    if len(canvas) != 2:
+        raise ValueError("{}: canvas must be (H, W), got {}".format(fn, canvas))
+    Hc, Wc = int(canvas[0]), int(canvas[1])
+    if Hc < 1 or Wc < 1 or Hc * Wc * 3 > 0x7fffffff:
+        raise ValueError("{}: a canvas has sides >= 1 and fewer than 2^31 elements, got {}".format(fn, (Hc, Wc)))
+    if host_table:
+        f = frames.astype(np.int64)
+        if (f[:, 1:3] < 1).any() or (f[:, 0] < 0).any():
+            raise ValueError("{}: a frame needs offset >= 0 and h, w >= 1, got {}".format(fn, f.tolist()))
+        if (f[:, 1] > Hc).any() or (f[:, 2] > Wc).any():
+            b = int(np.argmax((f[:, 1] > Hc) | (f[:, 2] > Wc)))
+            raise ValueError("{}: frame {} is {} x {}, larger than the canvas {} x {}".format(fn, b, f[b, 1], f[b, 2], Hc, Wc))
+        if (f[:, 0] + 3 * f[:, 1] * f[:, 2] > total).any():
+            raise ValueError("{}: the table does not fit pixels: a frame ends behind its {} bytes".format(fn, total))
+        if (np.abs(f) > 0x7fffffff).any():
+            raise ValueError("{}: the table's values must fit int32".format(fn))
+    m = np.asarray(_pixel_means() if means is None else means, np.float64).reshape(-1)
+    if m.shape[0] != 3:
+        raise ValueError("{}: means must be three numbers, got {}".format(fn, m.shape[0]))
+    shape = (B, Hc, Wc, 3)
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32):
+        raise TypeError("{}: out must be a {} tensor".format(fn, torch.float32))
+    tensors = [(n, t) for n, t in (("pixels", pixels), ("frames", frames), ("out", out)) if isinstance(t, torch.Tensor)]
+    for name, t in tensors:
+        if not t.is_cuda or t.device != tensors[0][1].device:
+            raise ValueError("{}: {} on {}: every tensor must live on one HIP device".format(fn, name, t.device))
+        if name != "pixels" and not t.is_contiguous():
+            raise ValueError("{}: {} must be contiguous".format(fn, name))
+    dev = tensors[0][1].device if tensors else "cuda"
+    if out is not None and tuple(out.shape) != shape:
+        raise ValueError("{}: out must be {}, got {}".format(fn, shape, tuple(out.shape)))
+    pix = pixels if isinstance(pixels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pixels)).to(dev)
+    tab = torch.from_numpy(np.ascontiguousarray(frames, np.int32)).to(dev) if host_table else frames
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(out.device):
+        check(lib().mv3d_image_blob(_ptr(pix), total, _ptr(tab), B, (C.c_double * 3)(*m), Hc, Wc, _ptr(out), _stream()), "mv3d_image_blob")
+    return out
+
+
 # ------------------------------------------------------------------ the deep-fusion join (DESIGN.md §3.19)
 _FJ_DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 

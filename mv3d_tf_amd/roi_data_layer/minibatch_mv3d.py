@@ -13,7 +13,8 @@ cfg.FRONT_VIEW_INPUT (not in the reference; default off = the blobs above exactl
 input, as a device tensor: see `front_view_blob`.
 cfg.LIDAR_BV_FROM_SCAN (not in the reference; default off) takes `lidar_bv_data` of an entry without an in-memory 'lidar_bv' from its
 scan ('velodyne' array or 'velodyne_path' file) instead of 'lidar_bv_path': a (1,601,601,9) device tensor rasterised by
-ops.point_cloud_2_top_batch, im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters."""
+ops.point_cloud_2_top_batch, im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters.
+cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`."""
 import numpy as np
 import numpy.random as npr
 
@@ -65,6 +66,19 @@ def front_view_blob(entry, cloud=None):
     return ops.point_cloud_2_front(_entry_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv') if cloud is None else cloud)[None]
 
 
+def image_blob(entry, image):
+    """`image_data` (1,H,W,3) f32 on the device under cfg.IMAGE_BLOB_ON_DEVICE: the frame's uint8 (h,w,3) BGR pixels are uploaded
+    ONCE, as bytes, and ops.image_blob subtracts cfg.PIXEL_MEANS (bit for bit the host expression of the key-off path).  A `flipped`
+    entry sets the call's flip flag, which gives the mirrored frame directly -- no f32 upload, no ops.mirror_columns.
+    cfg.IMAGE_CANVAS = (H, W) pads the frame at the top-left corner of a zero canvas of that shape (im_list_to_blob's rule), so that
+    a step's frames of different sizes stack; a larger frame raises ValueError.  None: (H, W) = (h, w), no padding.  An image that
+    is not a uint8 (h,w,3) array raises TypeError."""
+    if not isinstance(image, np.ndarray) or image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise TypeError("cfg.IMAGE_BLOB_ON_DEVICE needs the frame as a uint8 (h, w, 3) array, got {}".format(
+            "{} {}".format(image.dtype, image.shape) if isinstance(image, np.ndarray) else type(image).__name__))
+    return ops.image_blob([image], canvas=cfg.IMAGE_CANVAS, flip=[bool(entry.get('flipped', False))])
+
+
 def get_minibatch(roidb, num_classes):
     num_images = len(roidb)
     npr.randint(0, high=len(cfg.TRAIN.SCALES), size=num_images)          # RNG-stream parity (:22-23)
@@ -73,19 +87,20 @@ def get_minibatch(roidb, num_classes):
     assert num_images == 1, "Single batch only"
     entry = roidb[0]
     image = entry['image'] if 'image' in entry else _read_image_bgr(entry['image_path'])
-    image = image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS
+    on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)              # then image_data is final here: built, and mirrored, by ops.image_blob
+    image_data = image_blob(entry, image) if on_device else (image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS)[None].astype(np.float32)
     cloud = None
     if cfg.LIDAR_BV_FROM_SCAN and 'lidar_bv' not in entry:
         # no stored map: the scan is uploaded once (a mirrored frame's with y negated, whose raster IS the column-reversed map:
         # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror) and rasterised on the device
         cloud = ops._dev(_entry_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv'))
-        blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': ops.point_cloud_2_top_batch(cloud)[None], 'calib': entry['calib']}
+        blobs = {'image_data': image_data, 'lidar_bv_data': ops.point_cloud_2_top_batch(cloud)[None], 'calib': entry['calib']}
         blobs.update(gt_blobs(entry, ops.BEV_SHAPE))
-        if entry.get('flipped', False):
+        if entry.get('flipped', False) and not on_device:
             blobs['image_data'] = ops.mirror_columns(ops._dev(blobs['image_data']))
     else:
         bev = entry['lidar_bv'] if 'lidar_bv' in entry else np.load(entry['lidar_bv_path'])
-        blobs = {'image_data': image[None].astype(np.float32), 'lidar_bv_data': np.asarray(bev)[None], 'calib': entry['calib']}
+        blobs = {'image_data': image_data, 'lidar_bv_data': np.asarray(bev)[None], 'calib': entry['calib']}
         blobs.update(gt_blobs(entry, np.asarray(bev).shape))
     if cloud is None and entry.get('flipped', False):
         # a mirrored frame (kitti_mv3d.append_flipped_images): the files are the source frame's, the entry's ground truth and
@@ -94,7 +109,7 @@ def get_minibatch(roidb, num_classes):
         if blobs['lidar_bv_data'].shape[2] != 601:
             raise ValueError("a mirrored frame needs the 601 columns wide BEV map of point_cloud_2_top (mirror axis = column "
                              "300), this one is {} wide".format(blobs['lidar_bv_data'].shape[2]))
-        for k in ('image_data', 'lidar_bv_data'):
+        for k in ('lidar_bv_data',) if on_device else ('image_data', 'lidar_bv_data'):
             blobs[k] = ops.mirror_columns(ops._dev(blobs[k]))
     if cfg.FRONT_VIEW_INPUT:
         blobs['lidar_fv_data'] = front_view_blob(entry, cloud)

@@ -5,7 +5,9 @@ rows of rois[0] (BEV) and rois[1] (image) stay on the device until the last forw
 With `with_3d=True` the rows of rois[2] (the x, y, z, l, w, h LIDAR boxes) are kept as well, for
 datasets.proposal_recall_3d.evaluate_recall_3d.
 The frames' scans enter as in detect_batch.test_net: a three-view network gets `lidar_fv_data` rasterised from them, and with
-cfg.LIDAR_BV_FROM_SCAN `lidar_bv_data` is rasterised from them too and no stored BEV map is opened (`detect_batch.scan_feed`)."""
+cfg.LIDAR_BV_FROM_SCAN `lidar_bv_data` is rasterised from them too and no stored BEV map is opened (`detect_batch.scan_feed`).
+With cfg.IMAGE_BLOB_ON_DEVICE frames group by BEV shape only and a group's `image_data` is one uint8 upload and one ops.image_blob call
+that pads the frames to one canvas (`detect_batch.image_feed`)."""
 import os
 import pickle
 
@@ -14,7 +16,7 @@ import torch
 
 from .. import ops
 from ..fast_rcnn.config import cfg, get_output_dir
-from ..fast_rcnn.detect_batch import _load_frame, iter_frame_groups, loop_scan_source, scan_feed
+from ..fast_rcnn.detect_batch import _image_key, _load_frame, host_image_blob, image_feed, iter_frame_groups, loop_scan_source, scan_feed
 
 
 def imdb_proposals(sess, net, imdb, with_3d=False):
@@ -34,13 +36,13 @@ def imdb_proposals(sess, net, imdb, with_3d=False):
     def keys():
         for i in range(num_images):
             pending[i] = _load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
-            yield (np.shape(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
+            yield (_image_key(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
 
     kept = []                                                  # per group: (frames, cap, rois_bv, rois_img, num_rois, status, rois_3d), on the device
     for group in iter_frame_groups(keys(), batch_size):
         ims, bvs, calibs, clouds = zip(*(pending.pop(i) for i in group))
         B = len(group)
-        im_blob = np.stack([(np.asarray(im, np.float64) - cfg.PIXEL_MEANS).astype(np.float32) for im in ims])
+        im_blob = image_feed(ims) if cfg.IMAGE_BLOB_ON_DEVICE else host_image_blob(ims)
         feed = {"image_data": im_blob, "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
         if not from_scan:
             feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
