@@ -14,18 +14,47 @@ raises ValueError where it asks for its output directory (config.get_output_dir)
 fast_rcnn.test_mv keeps the reference's frame-by-frame entry points as they are: they feed two views.  The third view's input enters
 here: `box_detect(sess, net, im, bv, calib, boxes=None, fv=None)` is test_mv.box_detect with the frame's (64,512,3) front-view map fed
 as `lidar_fv_data`, and `test_net` rasterises the frames' Velodyne scans for a three-view network (`front_view_source`), which sends it
-down the device route whatever BATCH_SIZE is."""
-import os
-import pickle
+down the device route whatever BATCH_SIZE is.
+The loops over an imdb (`test_net` here, rpn_msr.generate.imdb_proposals) share their pieces: `loop_scan_source` says whether the
+frames' scans are needed, `iter_loaded_groups` loads and groups the frames, `group_feed` builds a group's feed (`image_feed`,
+`scan_feed`) and `forward_fixed_rois` runs it; `launch_post` and `post_lists` are the tail of `test_net` and of `ServeGraph`."""
 import time
 
 import numpy as np
 import torch
 
 from .. import ops
-from . import test_mv
+from . import loop_parts, test_mv
 from .config import cfg, get_output_dir
 from ..networks.mv3d import n_classes
+
+
+def post_settings(post):
+    """a copy of `post` = dict(max_per_image=...) with `oriented` (default: cfg.TEST.NMS_ORIENTED) and `footprint` (default:
+    cfg.TEST.NMS_ORIENTED_BOXES) filled in: what `launch_post` and `post_lists` read"""
+    post = dict(post)
+    post.setdefault("oriented", bool(cfg.TEST.get("NMS_ORIENTED", False)))
+    post.setdefault("footprint", cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed"))
+    return post
+
+
+def launch_post(post, cls_prob, pred_bv, corners, pred_cnr_r, num_rois, cap, K, plain_cnr_r=False, out=None, workspace=None):
+    """the device tail `post` asks for behind a box tail: ops.detect_post_oriented, or ops.detect_post, which gets the regressed
+    corners (and fills det_cnr_r) only with plain_cnr_r; asynchronous -> the tail's six-tuple"""
+    mpi = int(post.get("max_per_image", 300))
+    if post["oriented"]:
+        return ops.detect_post_oriented(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, cap, K, mpi, cfg.TEST.NMS,
+                                        strict_gt=bool(cfg.USE_GPU_NMS), footprint=post["footprint"], out=out, workspace=workspace)
+    return ops.detect_post(cls_prob, pred_bv, corners, pred_cnr_r if plain_cnr_r else None, num_rois, cap, K, mpi, cfg.TEST.NMS, out=out)
+
+
+def post_lists(post, out):
+    """the ONE read-back behind `launch_post`: per frame (dets, dets_cnr) exactly as class_detections + limit_detections return them
+    (dets[0] == [], class j (N,5) / (N,25) f32).  Oriented NMS on the 'regressed' footprint: dets_cnr holds the regressed corners
+    of the kept rows (the boxes the NMS judged)"""
+    if post["oriented"] and post["footprint"] == "regressed":
+        return [(dets, cnr_r) for dets, _, cnr_r in ops.detect_post_lists(out, with_cnr_r=True)]
+    return ops.detect_post_lists(out)
 
 
 class ServeGraph(test_mv.ServeGraph):
@@ -34,11 +63,8 @@ class ServeGraph(test_mv.ServeGraph):
     cfg.TEST.NMS_ORIENTED) captures ops.detect_post_oriented with `footprint` (default: cfg.TEST.NMS_ORIENTED_BOXES) instead."""
 
     def __init__(self, net, feed, warmup=2, post=None):
-        self.post = None if post is None else dict(post)
+        self.post = None if post is None else post_settings(post)
         self._post_out = self._post_ws = None
-        if self.post is not None:
-            self.post.setdefault("oriented", bool(cfg.TEST.get("NMS_ORIENTED", False)))
-            self.post.setdefault("footprint", cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed"))
         super().__init__(net, feed, warmup)
 
     def _step(self):
@@ -50,29 +76,19 @@ class ServeGraph(test_mv.ServeGraph):
                 self._post_out = ops.detect_post_outputs(B, n_classes, cap, dev)
                 if self.post["oriented"]:
                     self._post_ws = ops.detect_post_oriented_workspace(B, n_classes, cap, dev)
-            if self.post["oriented"]:
-                out["post"] = ops.detect_post_oriented(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"],
-                                                       out["num_rois"], cap, n_classes, int(self.post.get("max_per_image", 300)),
-                                                       cfg.TEST.NMS, strict_gt=bool(cfg.USE_GPU_NMS), footprint=self.post["footprint"],
-                                                       out=self._post_out, workspace=self._post_ws)
-            else:
-                out["post"] = ops.detect_post(out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"], out["num_rois"], cap,
-                                              n_classes, int(self.post.get("max_per_image", 300)), cfg.TEST.NMS, out=self._post_out)
+            out["post"] = launch_post(self.post, out["cls_prob"], out["pred_bv"], out["corners"], out["pred_corners_r"], out["num_rois"],
+                                      cap, n_classes, plain_cnr_r=True, out=self._post_out, workspace=self._post_ws)
         return out
 
     def final_detections(self):
-        """after a replay of a graph built with `post`: per frame (dets, dets_cnr) exactly as class_detections + limit_detections return
-        them (dets[0] == [], class j (N,5) / (N,25) f32) -- the score cut, NMS and cap ran inside the graph; the ONE host round trip is the
-        counts, the status words and the rows in front of the counts.  Oriented NMS on the 'regressed' footprint: dets_cnr holds the
-        regressed corners of the kept rows (the boxes the NMS judged)"""
+        """after a replay of a graph built with `post`: `post_lists` of the tail that ran inside the graph; the ONE host round trip
+        is the counts, the status words and the rows in front of the counts"""
         if self.post is None:
             raise ValueError("final_detections() needs ServeGraph(..., post=dict(max_per_image=...))")
         self.stream.synchronize()
         if int(self.out["status"].max().item()) & 1:
             raise ZeroDivisionError("float division")
-        if self.post["oriented"] and self.post["footprint"] == "regressed":
-            return [(dets, cnr_r) for dets, _, cnr_r in ops.detect_post_lists(self.out["post"], with_cnr_r=True)]
-        return ops.detect_post_lists(self.out["post"])
+        return post_lists(self.post, self.out["post"])
 
 
 def front_view_source(net, imdb):
@@ -165,22 +181,6 @@ def box_detect(sess, net, im, bv, calib, boxes=None, fv=None):
     return test_mv.box_detect(sess, _FeedsFrontView(net, fv), im, bv, calib, boxes)
 
 
-def _load_frame(imdb, i, stored_bv=True):
-    """(image, BEV map, calib) of frame i of a duck-typed imdb (see test_mv.test_net); stored_bv=False (cfg.LIDAR_BV_FROM_SCAN): the
-    map is None and neither imdb.bv_at nor imdb.lidar_path_at is touched"""
-    if hasattr(imdb, "image_at"):
-        im, bv = imdb.image_at(i), (imdb.bv_at(i) if stored_bv else None)
-    else:
-        bv = np.load(imdb.lidar_path_at(i)) if stored_bv else None
-        path = imdb.image_path_at(i)
-        if path.endswith(".npy"):
-            im = np.load(path)
-        else:
-            from PIL import Image                               # (the reference uses cv2.imread: BGR)
-            im = np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
-    return im, bv, imdb.calib_at(i)
-
-
 def iter_frame_groups(keys, batch_size):
     """Groups of CONSECUTIVE frame indices whose keys (the frames' image and BEV shapes) are equal, at most `batch_size` per group:
     frames are never padded or reordered, a change of shape just ends the group.  Lazy: `keys` may load the frames as it goes."""
@@ -199,86 +199,77 @@ def group_frames(keys, batch_size):
     return list(iter_frame_groups(keys, batch_size))
 
 
-def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
-    """test_mv.test_net with cfg.TEST.BATCH_SIZE (not in the reference).  1: test_mv.test_net, untouched.  n > 1: one eager forward
-    with fixed ROI rows per group of equally shaped consecutive frames (`iter_frame_groups`), the box tail and ops.detect_post on the
-    device, ONE read-back of the final detections per group.  A three-view network takes the device route for any BATCH_SIZE and
-    gets `lidar_fv_data` from the frames' scans (`front_view_source`), a group's frames rasterised by ONE batched
-    ops.point_cloud_2_front call.  cfg.LIDAR_BV_FROM_SCAN: the device route for any BATCH_SIZE, no stored BEV map is opened (`_load_frame`
-    touches neither imdb.bv_at nor imdb.lidar_path_at), frames group by image shape and ops.BEV_SHAPE, and a group's `lidar_bv_data` is
-    ONE ops.point_cloud_2_top_batch call on the group's scans (`scan_feed`: one upload for both rasters).  cfg.TEST.NMS_ORIENTED: the device route for any BATCH_SIZE, with
-    ops.detect_post_oriented on cfg.TEST.NMS_ORIENTED_BOXES; 'regressed' stores the regressed corners in all_boxes_cnr.
-    cfg.IMAGE_BLOB_ON_DEVICE: the device route for any BATCH_SIZE; frames group by BEV shape only, and a group's `image_data` is ONE
-    uint8 upload and ONE ops.image_blob call that pads the frames to cfg.IMAGE_CANVAS or the group's maximal image shape (`image_feed`;
-    a frame larger than IMAGE_CANVAS raises ValueError before the forward).  Pickles, the `im_detect: i/n` line (per frame, times averaged over the
-    group) and the evaluate_detections call are test_mv.test_net's."""
-    batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
-    oriented = bool(cfg.TEST.get("NMS_ORIENTED", False))
-    footprint = cfg.TEST.get("NMS_ORIENTED_BOXES", "regressed")
-    points_of, from_scan = loop_scan_source(net, imdb)
-    three_views = getattr(net, "views", 2) == 3
-    on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)
-    if batch_size <= 1 and not oriented and points_of is None and not on_device:
-        return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
-    if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
-        net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
-        net.mfma_trunk = bool(cfg.TEST.get("MFMA_TRUNK", False))
-    num_images = len(imdb.image_index)
-    all_boxes = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
-    all_boxes_cnr = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
-    output_dir = get_output_dir(imdb, weights_filename, oriented_nms=True)
+def iter_loaded_groups(imdb, points_of, from_scan, batch_size):
+    """(group, (ims, bvs, calibs, clouds)) for every group of `iter_frame_groups` over the imdb's frames, whose key is `_image_key`
+    of the image and the BEV shape (ops.BEV_SHAPE under from_scan, where `loop_parts.load_frame` opens no stored map).  Lazy: a frame
+    (and its scan, points_of(i), if a source is given) is loaded when its key is asked for and let go of when its group is handed out"""
     pending = {}
 
     def keys():
-        for i in range(num_images):
-            pending[i] = _load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
+        for i in range(len(imdb.image_index)):
+            pending[i] = loop_parts.load_frame(imdb, i, not from_scan) + ((None if points_of is None else points_of(i)),)
             yield (_image_key(pending[i][0]), ops.BEV_SHAPE if from_scan else np.shape(pending[i][1]))
 
+    for group in iter_frame_groups(keys(), batch_size):
+        yield group, tuple(zip(*(pending.pop(i) for i in group)))
+
+
+def group_feed(net, ims, bvs, calibs, clouds, from_scan):
+    """the feed of one group of frames: `image_data` from `image_feed` (cfg.IMAGE_BLOB_ON_DEVICE) or `host_image_blob`, `lidar_bv_data`
+    stacked from the stored maps or, under from_scan, rasterised with a three-view network's `lidar_fv_data` by `scan_feed` (the
+    group's scans back to back: one upload, one call per view), `calib`, and `im_info` = the BEV size, scale 1, per frame"""
+    feed = {"image_data": image_feed(ims) if cfg.IMAGE_BLOB_ON_DEVICE else host_image_blob(ims),
+            "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
+    if not from_scan:
+        feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
+    feed.update(scan_feed(clouds, from_scan, getattr(net, "views", 2) == 3))
+    feed["im_info"] = np.array([[feed["lidar_bv_data"].shape[1], feed["lidar_bv_data"].shape[2], 1]] * len(ims), dtype=np.float32)
+    return feed
+
+
+def forward_fixed_rois(net, feed):
+    """net.forward(feed) without gradients and with fixed ROI rows per frame (every frame owns `rois_per_frame` rows)"""
+    net.fixed_rois = True
+    try:
+        with torch.no_grad():
+            return net.forward(feed)
+    finally:
+        net.fixed_rois = False
+
+
+def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
+    """test_mv.test_net with cfg.TEST.BATCH_SIZE (not in the reference).  1: test_mv.test_net, untouched.  n > 1: one eager forward
+    with fixed ROI rows per group of equally shaped consecutive frames (`iter_loaded_groups`, `group_feed`), the box tail and
+    `launch_post` on the device, ONE read-back of the final detections per group (`post_lists`).  A three-view network,
+    cfg.LIDAR_BV_FROM_SCAN, cfg.TEST.NMS_ORIENTED and cfg.IMAGE_BLOB_ON_DEVICE each select the device route for any BATCH_SIZE.
+    Pickles, the `im_detect: i/n` line (per frame, times averaged over the group) and the evaluate_detections call are
+    test_mv.test_net's."""
+    batch_size = int(cfg.TEST.get("BATCH_SIZE", 1))
+    post = post_settings(dict(max_per_image=max_per_image))
+    points_of, from_scan = loop_scan_source(net, imdb)
+    if batch_size <= 1 and not post["oriented"] and points_of is None and not cfg.IMAGE_BLOB_ON_DEVICE:
+        return test_mv.test_net(sess, net, imdb, weights_filename, max_per_image=max_per_image, thresh=thresh, vis=vis)
+    loop_parts.apply_test_precision(net)
+    num_images = len(imdb.image_index)
+    all_boxes, all_boxes_cnr = loop_parts.detection_lists(imdb)
+    output_dir = get_output_dir(imdb, weights_filename, oriented_nms=True)
     t_detect = t_misc = 0.0
-    for group in iter_frame_groups(keys(), max(batch_size, 1)):
-        ims, bvs, calibs, clouds = zip(*(pending.pop(i) for i in group))
-        B = len(group)
+    for group, frames in iter_loaded_groups(imdb, points_of, from_scan, max(batch_size, 1)):
         t0 = time.time()
-        im_blob = image_feed(ims) if on_device else host_image_blob(ims)
-        feed = {"image_data": im_blob, "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
-        if not from_scan:
-            feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
-        feed.update(scan_feed(clouds, from_scan, three_views))         # the group's scans back to back: one upload, one call per view
-        feed["im_info"] = np.array([[feed["lidar_bv_data"].shape[1], feed["lidar_bv_data"].shape[2], 1]] * B, dtype=np.float32)
-        net.fixed_rois = True
-        try:
-            with torch.no_grad():
-                L = net.forward(feed)
-                cnr, pr, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
-        finally:
-            net.fixed_rois = False
+        L = forward_fixed_rois(net, group_feed(net, *frames, from_scan))
+        cnr, pr, pred_bv, _ = ops.box_detect_tail(L["rois"][2].contiguous(), L["bbox_pred"].contiguous(), n_classes)
         torch.cuda.synchronize()                                       # (for the timer only: one per group)
         t1 = time.time()
-        if oriented:
-            post = ops.detect_post_oriented(L["cls_prob"], pred_bv, cnr, pr, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
-                                            max_per_image, cfg.TEST.NMS, strict_gt=bool(cfg.USE_GPU_NMS), footprint=footprint)
-        else:
-            post = ops.detect_post(L["cls_prob"], pred_bv, cnr, None, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes,
-                                   max_per_image, cfg.TEST.NMS)
+        out = launch_post(post, L["cls_prob"], pred_bv, cnr, pr, L["num_rois"], int(L["rois_per_frame"]), imdb.num_classes)
         if int(L["rois_status"].max().item()) & 1:
             raise ZeroDivisionError("float division")
-        if oriented and footprint == "regressed":
-            frames = [(dets, cnr_r) for dets, _, cnr_r in ops.detect_post_lists(post, with_cnr_r=True)]
-        else:
-            frames = ops.detect_post_lists(post)
+        lists = post_lists(post, out)
         t2 = time.time()
-        for i, (dets, dets_cnr) in zip(group, frames):
+        for i, (dets, dets_cnr) in zip(group, lists):
             for j in range(1, imdb.num_classes):
                 all_boxes[j][i] = dets[j]
                 all_boxes_cnr[j][i] = dets_cnr[j]
-            t_detect += (t1 - t0) / B
-            t_misc += (t2 - t1) / B
+            t_detect += (t1 - t0) / len(group)
+            t_misc += (t2 - t1) / len(group)
             print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, t_detect / (i + 1), t_misc / (i + 1)))
-    with open(os.path.join(output_dir, 'detections.pkl'), 'wb') as f:
-        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
-    with open(os.path.join(output_dir, 'detections_cnr.pkl'), 'wb') as f:
-        pickle.dump(all_boxes_cnr, f, pickle.HIGHEST_PROTOCOL)
-    print('Evaluating detections')
-    imdb.evaluate_detections(all_boxes, all_boxes_cnr, output_dir)
-    return all_boxes, all_boxes_cnr
-
+    return loop_parts.save_and_evaluate(imdb, all_boxes, all_boxes_cnr, output_dir)

@@ -7,15 +7,14 @@ lib/fast_rcnn/test_mv.py:149-264.  `sess` is an opaque context (ignored: there i
 session).  Returns (scores (R,K), pred_boxes_bv (R,4K) f64, pred_boxes_cnr (R,24K) f32,
 pred_boxes_cnr_r (R,24K) f32) like the reference, K = 2; the geometric tail runs in
 libmv3d_hip.so (mv3d_box_detect_tail)."""
-import os
 import time
-import pickle
 
 import numpy as np
 import torch
 
 from .. import ops
 from .config import cfg, get_output_dir
+from .loop_parts import apply_test_precision, detection_lists, load_frame, save_and_evaluate
 from .nms_wrapper import nms
 from ..networks.mv3d import n_classes
 
@@ -67,31 +66,17 @@ def limit_detections(dets, dets_cnr, max_per_image):
 
 
 def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, vis=False):
-    """lib/fast_rcnn/test_mv.py:321-518 without the drawing: runs `box_detect` on every frame of `imdb`, collects
+    """lib/fast_rcnn/test_mv.py:321-518 without the drawing: runs `box_detect` on every frame of `imdb` (`load_frame`), collects
     all_boxes[cls][image] (N,5) and all_boxes_cnr[cls][image] (N,25), pickles them under get_output_dir() and calls
-    imdb.evaluate_detections.  `imdb` is duck-typed: image_index, num_classes, name, calib_at(i), evaluate_detections,
-    and either image_at(i) / bv_at(i) (arrays) or image_path_at(i) / lidar_path_at(i) (files: .npy for the BEV, an
-    image readable by numpy / PIL).  As in the reference the `thresh` argument is shadowed by 0.05 (:421)."""
-    if hasattr(net, "mfma_trunk") and (cfg.TEST.get("MFMA_TRUNK", False) or cfg.TEST.get("PRECISION", "fp32") != "fp32"):
-        net.amp_dtype = {"fp32": None, "fp16": torch.float16, "bf16": torch.bfloat16}[cfg.TEST.get("PRECISION", "fp32")]
-        net.mfma_trunk = bool(cfg.TEST.get("MFMA_TRUNK", False))
+    imdb.evaluate_detections.  `imdb` is duck-typed: image_index, num_classes, name, evaluate_detections and what `load_frame`
+    asks for.  As in the reference the `thresh` argument is shadowed by 0.05 (:421)."""
+    apply_test_precision(net)
     num_images = len(imdb.image_index)
-    all_boxes = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
-    all_boxes_cnr = [[[] for _ in range(num_images)] for _ in range(imdb.num_classes)]
+    all_boxes, all_boxes_cnr = detection_lists(imdb)
     output_dir = get_output_dir(imdb, weights_filename)
     t_detect = t_misc = 0.0                                            # the reference's _t['im_detect'] / _t['misc'] timers (:355, :433-436, :482-502)
     for i in range(num_images):
-        if hasattr(imdb, "image_at"):
-            im, bv = imdb.image_at(i), imdb.bv_at(i)
-        else:
-            bv = np.load(imdb.lidar_path_at(i))
-            path = imdb.image_path_at(i)
-            if path.endswith(".npy"):
-                im = np.load(path)
-            else:
-                from PIL import Image                               # (the reference uses cv2.imread: BGR)
-                im = np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
-        calib = imdb.calib_at(i)
+        im, bv, calib = load_frame(imdb, i)
         t0 = time.time()
         scores, boxes_bv, boxes_cnr, boxes_cnr_r = box_detect(sess, net, im, bv, calib, None)
         t1 = time.time()
@@ -103,14 +88,7 @@ def test_net(sess, net, imdb, weights_filename, max_per_image=300, thresh=0.05, 
             all_boxes_cnr[j][i] = dets_cnr[j]
         t_misc += time.time() - t1
         print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, t_detect / (i + 1), t_misc / (i + 1)))   # lib/fast_rcnn/test_mv.py:504-506
-    with open(os.path.join(output_dir, 'detections.pkl'), 'wb') as f:
-        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
-    with open(os.path.join(output_dir, 'detections_cnr.pkl'), 'wb') as f:
-        pickle.dump(all_boxes_cnr, f, pickle.HIGHEST_PROTOCOL)
-    print('Evaluating detections')
-    imdb.evaluate_detections(all_boxes, all_boxes_cnr, output_dir)
-    return all_boxes, all_boxes_cnr
-
+    return save_and_evaluate(imdb, all_boxes, all_boxes_cnr, output_dir)
 
 
 class ServeGraph:

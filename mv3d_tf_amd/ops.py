@@ -400,6 +400,39 @@ def detect_post_outputs(B, K, cap, dev, with_cnr_r=True):
             torch.empty((B, K, cap), dtype=torch.int32, device=dev), tail[:B * K].view(B, K), tail[B * K:])
 
 
+def _detect_post_args(name, cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame, num_classes, max_per_image, strict_gt,
+                      score_thresh, nms_thresh):
+    """what detect_post and detect_post_oriented (`name`, the prefix of the messages) do with their arguments: the row and shape
+    checks, the widening to contiguous f32 and the parameter block -> (B, params, (cls_prob, pred_bv, corners, pred_cnr_r))"""
+    K, cap = int(num_classes), int(rows_per_frame)
+    if cap <= 0 or cls_prob.shape[0] % cap:
+        check(_lib.ERR_INVALID_ARG, name + ": rows are not a multiple of rows_per_frame")
+    B = cls_prob.shape[0] // cap
+    cls_prob, pred_bv, corners = cls_prob.float().contiguous(), pred_bv.float().contiguous(), corners.float().contiguous()
+    if pred_cnr_r is not None:
+        pred_cnr_r = pred_cnr_r.float().contiguous()
+    if (cls_prob.shape[1], pred_bv.shape, corners.shape) != (K, (B * cap, 4 * K), (B * cap, 24)) or \
+            (pred_cnr_r is not None and pred_cnr_r.shape != (B * cap, 24 * K)) or \
+            (num_rois is not None and (num_rois.dtype != torch.int32 or num_rois.numel() != B)):
+        check(_lib.ERR_INVALID_ARG, name + ": input shapes")
+    params = _lib.DetectPostParams(K, cap, int(max_per_image), 1 if strict_gt else 0, float(score_thresh), 0, float(nms_thresh))
+    return B, params, (cls_prob, pred_bv, corners, pred_cnr_r)
+
+
+def _detect_post_launch(fn, name, B, params, inputs, num_rois, extra, out, workspace):
+    """the launch behind both: `out` (default: fresh detect_post_outputs) with its status zeroed (the kernels OR into it), then
+    fn(*inputs, num_rois, B, params, *extra, *outputs, workspace, its bytes, stream)"""
+    if out is None:
+        out = detect_post_outputs(B, params.num_classes, params.rows_per_frame, inputs[0].device, inputs[3] is not None)
+    det_bv, det_cnr, det_cnr_r, det_row, det_count, status = out
+    status.zero_()
+    rc = fn(*[_ptr(t) for t in inputs], _ptr(num_rois), B, C.byref(params), *extra, _ptr(det_bv), _ptr(det_cnr),
+            _ptr(det_cnr_r if inputs[3] is not None else None), _ptr(det_row), _ptr(det_count), _ptr(status),
+            _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(), _stream())
+    check(rc, name)
+    return out
+
+
 def detect_post(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame, num_classes, max_per_image, nms_thresh,
                 score_thresh=0.05, use_gpu_nms=None, out=None):
     """The per-frame tail of test_net (score cut, NMS, cap over all classes; lib/fast_rcnn/test_mv.py:420-444, 491-501) for a batch
@@ -410,29 +443,9 @@ def detect_post(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame
     if use_gpu_nms is None:
         from .fast_rcnn.config import cfg
         use_gpu_nms = bool(cfg.USE_GPU_NMS)
-    K, cap = int(num_classes), int(rows_per_frame)
-    if cap <= 0 or cls_prob.shape[0] % cap:
-        check(_lib.ERR_INVALID_ARG, "detect_post: rows are not a multiple of rows_per_frame")
-    B = cls_prob.shape[0] // cap
-    dev = cls_prob.device
-    cls_prob = cls_prob.float().contiguous()
-    pred_bv, corners = pred_bv.float().contiguous(), corners.float().contiguous()
-    if pred_cnr_r is not None:
-        pred_cnr_r = pred_cnr_r.float().contiguous()
-    if (cls_prob.shape[1], pred_bv.shape, corners.shape) != (K, (B * cap, 4 * K), (B * cap, 24)) or \
-            (pred_cnr_r is not None and pred_cnr_r.shape != (B * cap, 24 * K)) or \
-            (num_rois is not None and (num_rois.dtype != torch.int32 or num_rois.numel() != B)):
-        check(_lib.ERR_INVALID_ARG, "detect_post: input shapes")
-    if out is None:
-        out = detect_post_outputs(B, K, cap, dev, pred_cnr_r is not None)
-    det_bv, det_cnr, det_cnr_r, det_row, det_count, status = out
-    status.zero_()
-    params = _lib.DetectPostParams(K, cap, int(max_per_image), 1 if use_gpu_nms else 0, float(score_thresh), 0, float(nms_thresh))
-    rc = lib().mv3d_detect_post(_ptr(cls_prob), _ptr(pred_bv), _ptr(corners), _ptr(pred_cnr_r), _ptr(num_rois), B, C.byref(params),
-                                _ptr(det_bv), _ptr(det_cnr), _ptr(det_cnr_r if pred_cnr_r is not None else None), _ptr(det_row),
-                                _ptr(det_count), _ptr(status), None, 0, _stream())
-    check(rc, "mv3d_detect_post")
-    return out
+    B, params, inputs = _detect_post_args("detect_post", cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame, num_classes,
+                                          max_per_image, use_gpu_nms, score_thresh, nms_thresh)
+    return _detect_post_launch(lib().mv3d_detect_post, "mv3d_detect_post", B, params, inputs, num_rois, (), out, None)
 
 
 _FOOTPRINTS = {"proposal": 0, "regressed": 1}
@@ -454,35 +467,15 @@ def detect_post_oriented(cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_
     nothing).  `workspace`: detect_post_oriented_workspace(...), or the cached one of this stream.  Asynchronous: kernel launches only."""
     if footprint not in _FOOTPRINTS:
         raise ValueError("detect_post_oriented: footprint is 'regressed' or 'proposal', not %r" % (footprint,))
-    K, cap = int(num_classes), int(rows_per_frame)
-    if cap <= 0 or cls_prob.shape[0] % cap:
-        check(_lib.ERR_INVALID_ARG, "detect_post_oriented: rows are not a multiple of rows_per_frame")
-    B = cls_prob.shape[0] // cap
-    dev = cls_prob.device
-    cls_prob = cls_prob.float().contiguous()
-    pred_bv, corners = pred_bv.float().contiguous(), corners.float().contiguous()
-    if pred_cnr_r is not None:
-        pred_cnr_r = pred_cnr_r.float().contiguous()
-    if (cls_prob.shape[1], pred_bv.shape, corners.shape) != (K, (B * cap, 4 * K), (B * cap, 24)) or \
-            (pred_cnr_r is not None and pred_cnr_r.shape != (B * cap, 24 * K)) or \
-            (num_rois is not None and (num_rois.dtype != torch.int32 or num_rois.numel() != B)):
-        check(_lib.ERR_INVALID_ARG, "detect_post_oriented: input shapes")
-    params = _lib.DetectPostParams(K, cap, int(max_per_image), 1 if strict_gt else 0, float(score_thresh), 0, float(nms_thresh))
+    B, params, inputs = _detect_post_args("detect_post_oriented", cls_prob, pred_bv, corners, pred_cnr_r, num_rois, rows_per_frame,
+                                          num_classes, max_per_image, strict_gt, score_thresh, nms_thresh)
     need = lib().mv3d_detect_post_oriented_workspace_bytes(B, C.byref(params))
     if need == 0:
         check(_lib.ERR_INVALID_ARG, "detect_post_oriented: batch, num_classes or rows_per_frame out of range")
     if workspace is None:
-        workspace = _workspace(need, dev, "detect_post_oriented")
-    if out is None:
-        out = detect_post_outputs(B, K, cap, dev, pred_cnr_r is not None)
-    det_bv, det_cnr, det_cnr_r, det_row, det_count, status = out
-    status.zero_()
-    rc = lib().mv3d_detect_post_oriented(_ptr(cls_prob), _ptr(pred_bv), _ptr(corners), _ptr(pred_cnr_r), _ptr(num_rois), B,
-                                         C.byref(params), _FOOTPRINTS[footprint], _ptr(det_bv), _ptr(det_cnr),
-                                         _ptr(det_cnr_r if pred_cnr_r is not None else None), _ptr(det_row), _ptr(det_count),
-                                         _ptr(status), _ptr(workspace), workspace.numel() * workspace.element_size(), _stream())
-    check(rc, "mv3d_detect_post_oriented")
-    return out
+        workspace = _workspace(need, inputs[0].device, "detect_post_oriented")
+    return _detect_post_launch(lib().mv3d_detect_post_oriented, "mv3d_detect_post_oriented", B, params, inputs, num_rois,
+                               (_FOOTPRINTS[footprint],), out, workspace)
 
 
 def nms_oriented(corners, scores, thresh, strict_gt=False):

@@ -5,8 +5,8 @@ Keys and dtypes as the reference feeds them: image_data (
 lidar_bv_data (1,Hbv,Wbv,9), calib (4,12), gt_boxes / gt_boxes_bv (G,5), gt_boxes_3d (G,7), gt_boxes_corners (G,25),
 im_info (1,3) = BEV size.  One numpy draw is kept for RNG-stream parity with the reference (`npr.randint` over
 cfg.TRAIN.SCALES, :22-23, whose result the reference never uses either).  A roidb entry may carry the frame in memory
-('image' (H,W,3) BGR array, 'lidar_bv' array) instead of 'image_path' / 'lidar_bv_path'; image files are read with
-numpy (.npy) or PIL -- cv2 is not a dependency here.  An entry with `flipped` true (cfg.TRAIN.USE_FLIPPED) returns its two maps as
+('image' (H,W,3) BGR array, 'lidar_bv' array) instead of 'image_path' / 'lidar_bv_path'; image files are read by
+utils.read_image.read_image_bgr.  An entry with `flipped` true (cfg.TRAIN.USE_FLIPPED) returns its two maps as
 device tensors, mirrored left/right by ops.mirror_columns; every other entry returns numpy as the reference does.
 
 cfg.FRONT_VIEW_INPUT (not in the reference; default off = the blobs above exactly) adds `lidar_fv_data` (1,64,512,3), the third view's
@@ -21,13 +21,7 @@ import numpy.random as npr
 from .. import ops
 from ..datasets.kitti_mv3d import gt_blobs
 from ..fast_rcnn.config import cfg
-
-
-def _read_image_bgr(path):
-    if path.endswith(".npy"):
-        return np.load(path)
-    from PIL import Image                                    # what cv2.imread returns: uint8 BGR
-    return np.asarray(Image.open(path).convert("RGB"))[:, :, ::-1]
+from ..utils.read_image import read_image_bgr
 
 
 def _entry_cloud(entry, key, own_map):
@@ -86,7 +80,7 @@ def get_minibatch(roidb, num_classes):
         'num_images ({}) must divide BATCH_SIZE ({})'.format(num_images, cfg.TRAIN.BATCH_SIZE)
     assert num_images == 1, "Single batch only"
     entry = roidb[0]
-    image = entry['image'] if 'image' in entry else _read_image_bgr(entry['image_path'])
+    image = entry['image'] if 'image' in entry else read_image_bgr(entry['image_path'])
     on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)              # then image_data is final here: built, and mirrored, by ops.image_blob
     image_data = image_blob(entry, image) if on_device else (image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS)[None].astype(np.float32)
     cloud = None
