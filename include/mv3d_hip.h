@@ -507,6 +507,33 @@ int mv3d_point_cloud_2_top_batch(const float *points_dev, const int32_t *offsets
 int mv3d_point_cloud_2_top_batch_dense(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
                                        const double *ranges8_host, float *top_dev, int32_t *status_dev, void *stream);
 
+/* The MV3D paper's BEV encoding (section 3.1 of the paper; csrc/bev_paper.hip) from the same inputs: a second
+ * scatter / resolve body beside the one above, three launches whatever num_frames is.  PARITY UNPINNED: the reference has no such
+ * raster; tests/bev_paper_restatement.py states the definition.  Kept rows, cells and height slices are those of
+ * mv3d_point_cloud_2_top_batch (one statement, csrc/bev_cell.h): a row passes the two range tests and falls into the slice set
+ * S = { i < M : z in [height_i, height_i + zres) }, M = ceil((height_hi - height_lo) / zres); a row with empty S is dropped; a row
+ * with non-empty S whose cell lies outside the map sets *status_dev and is dropped.  Per frame (H, W, M + 2) -- (601, 601, 10)
+ * without ranges:
+ *   channel i < M   max z of the kept rows with i in S, as z - (float)height_lo
+ *   channel M       reflectance (bit for bit) of the kept row with the largest z (-0.0 == +0.0); among equal z the last row of the frame
+ *   channel M + 1   T[min(N, 63)], N = the cell's kept rows, T = mv3d_bev_density_table: min(1, log(N + 1) / log 64)
+ * and an empty cell is all zeros.  The map does not depend on the order of a frame's rows.
+ * Arguments, alignment, the offsets rule ("no value in it can make the call read or write out of bounds"), capture and refusals are
+ * mv3d_point_cloud_2_top_batch's, plus
+ *   workspace_dev  mv3d_point_cloud_2_top_paper_workspace(num_frames, ranges8_host) bytes on the device, 16-byte aligned, the
+ *                  caller's: 8 bytes per cell and frame (the winner words).  Cleared by the call; nothing is kept in it between calls.
+ * mv3d_point_cloud_2_top_paper_shape: dims[3] = (H, W, M + 2), refusing what mv3d_point_cloud_2_top_shape refuses.
+ * mv3d_point_cloud_2_top_paper_workspace: 0 for num_frames outside [1, MV3D_FV_MAX_FRAMES] or such ranges.
+ * mv3d_bev_density_table (HOST only, no device work): out64[n] = (float)fmin(1.0, log((double)(n + 1)) / log(64.0)), n = 0 .. 63,
+ * computed with libm -- the table the resolve kernel is handed by value; out64[0] == 0, out64[63] == 1. */
+int mv3d_point_cloud_2_top_paper_batch(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
+                                       const double *ranges8_host, float *top_dev, void *workspace_dev, int32_t *status_dev,
+                                       void *stream);
+size_t mv3d_point_cloud_2_top_paper_workspace(int num_frames, const double *ranges8_host);
+int mv3d_point_cloud_2_top_paper_shape(double res, double zres, double side_lo, double side_hi, double fwd_lo, double fwd_hi,
+                                       double height_lo, double height_hi, int *dims);
+int mv3d_bev_density_table(float *out64);
+
 /* ------------------------------------------------------------------ the target layers' random subsamplings (HOST code)
  * The reference subsamples with `npr.choice(inds, size=k, replace=False)` on the numpy GLOBAL legacy RandomState
  * (lib/rpn_msr/anchor_target_layer_tf.py:146-159,178-183; lib/rpn_msr/proposal_target_layer_tf.py:246-269) = 

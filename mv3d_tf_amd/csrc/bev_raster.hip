@@ -30,33 +30,9 @@
 //            16-byte boundary.  Clear and resolve therefore run over the FLAT range of num_frames * H * W * C elements: `head` scalar
 //            elements up to the first 16-byte boundary of top_dev, 16-byte vectors, `tail` scalar elements.  The body needs 4-byte
 //            alignment of top_dev only.  All element indices are 64-bit (1024 frames x 3 250 809 elements > 2^31).
+#include "bev_cell.h"       // BevParams, bev_params, and the cell / slice rule shared with bev_paper.hip
 #include "common.h"
 #include "frame_rows.h"
-
-// The rasteriser's parameters, host arithmetic; the kernels take the struct by value.  The dtypes numpy gives every step (f32 range
-// tests against Python floats, f64 slice tests against np.arange's values, which are h0, h0 + zres, h0 + i * ((h0 + zres) - h0), ...)
-// are spelled out in oracle/mv3d_oracle.c:mv3d_ref_point_cloud_2_top_ranges.
-struct BevParams {
-    float fwd0f, fwd1f, ylo, yhi, resf, h0f;
-    double h0, next, delta, zres;
-    int xoff, yoff, Hd, Wd, Cd, nslice, zmax;
-};
-
-static bool bev_params(double res, double zres, double side0, double side1, double fwd0, double fwd1, double h0, double h1, BevParams &q)
-{
-    if (!(res > 0.0) || !(zres > 0.0) || !(side1 > side0) || !(fwd1 > fwd0) || !(h1 >= h0)) return false;
-    const double nx = (side1 - side0) / res, ny = (fwd1 - fwd0) / res, nz = (h1 - h0) / zres;
-    if (!(nx < 32768.0) || !(ny < 32768.0) || !(nz < 31.0)) return false;       // (the key of the last channel holds 5 bits of slice)
-    const int x_max = (int)nx, y_max = (int)ny, z_max = (int)nz;                 // read_lidar.py:49-51
-    q.Wd = x_max + 1; q.Hd = y_max + 1; q.Cd = z_max + 1; q.zmax = z_max;
-    q.xoff = (int)floor(side0 / res); q.yoff = (int)floor(fwd1 / res);
-    q.nslice = (int)ceil(nz);
-    q.h0 = h0; q.next = h0 + zres; q.delta = q.next - h0; q.zres = zres;
-    q.fwd0f = (float)fwd0; q.fwd1f = (float)fwd1; q.ylo = (float)(-side1); q.yhi = (float)(-side0); q.resf = (float)res; q.h0f = (float)h0;
-    return true;
-}
-
-#define BEVB_MAX_INDEX ((1u << 27) - 2u)       // largest index within a frame: index + 1 stays below 2^27, as mv3d_point_cloud_2_top requires
 
 // zero keys: a workgroup clears 16 KB contiguous, four 16-byte stores per thread; workgroup 0 also clears the head / tail elements
 // (at most 3 each) and the status word
@@ -90,19 +66,13 @@ __global__ __launch_bounds__(256) void bevb_scatter_kernel(const float *__restri
     const unsigned idx = p - (unsigned)s_off[lo];
     if (idx > BEVB_MAX_INDEX) return;
     const float4 v = reinterpret_cast<const float4 *>(pts)[p];
-    if (!(v.x > q.fwd0f && v.x < q.fwd1f)) return;               // f_filt (read_lidar.py:58-59): f32 against the f32-rounded bounds
-    if (!(v.y > q.ylo && v.y < q.yhi)) return;                   // s_filt (:60-61)
-    int xi = (int)(-v.y / q.resf), yi = (int)(-v.x / q.resf);   // f32 divide, astype(int32) truncates (:96-97)
-    xi -= q.xoff;                                                // int(np.floor(side_range[0] / res)) (:102)
-    yi += q.yoff;                                                // int(np.floor(fwd_range[1] / res))  (:103)
-    if (xi < 0) xi += q.Wd;                                      // numpy: a negative index counts from the end ...
-    if (yi < 0) yi += q.Hd;
-    const bool out = xi < 0 || xi >= q.Wd || yi < 0 || yi >= q.Hd;      // ... anything else outside the map is its IndexError
+    long long pixel;
+    bool out;
+    if (!bev_cell_of(v, q, pixel, out)) return;                  // the range tests and the cell: bev_cell.h
     const double z = (double)v.z;
-    unsigned *cell = keys + (long long)lo * n + ((long long)yi * q.Wd + xi) * q.Cd;
-    for (int i = 0; i < q.nslice; ++i) {                         // np.arange(h0, h1, zres) (:80), compared in f64 (:82-83)
-        const double height = i == 0 ? q.h0 : (i == 1 ? q.next : q.h0 + (double)i * q.delta);
-        if (z >= height && z < height + q.zres) {
+    unsigned *cell = keys + (long long)lo * n + pixel * q.Cd;
+    for (int i = 0; i < q.nslice; ++i) {
+        if (bev_in_slice(z, i, q)) {
             if (out) { if (status) atomicOr(status, 1); return; }
             if (i < q.zmax) atomicMax(&cell[i], idx + 1u);
             atomicMax(&cell[q.zmax], ((unsigned)i << 27) | (idx + 1u));
@@ -161,19 +131,18 @@ static int bevb_launch(const float *points_dev, const int32_t *offsets_dev, int 
     if (num_frames == 0) return MV3D_OK;
     BevParams q;
     if (r) {
-        if (!status_dev || !bev_params(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], q)) return MV3D_ERR_INVALID_ARG;
+        if (!status_dev || !bev_params8(r, q)) return MV3D_ERR_INVALID_ARG;
     } else {
-        bev_params(0.1, 0.3, -30.0, 30.0, 0.0, 60.0, -2.0, 0.4, q);      // tools/read_lidar.py:121-133 -> (601, 601, 9); no cell can fall outside
+        bev_params_mv3d(q);                                              // tools/read_lidar.py:121-133 -> (601, 601, 9); no cell can fall outside
         status_dev = nullptr;
     }
     if ((!offsets_dev && num_frames != 1) || !top_dev || (total_points > 0 && !points_dev)) return MV3D_ERR_INVALID_ARG;
     if (((uintptr_t)points_dev & 15) != 0 || ((uintptr_t)top_dev & 3) != 0 || ((uintptr_t)offsets_dev & 3) != 0 || ((uintptr_t)status_dev & 3) != 0)
         return MV3D_ERR_INVALID_ARG;
     const long long n = (long long)q.Hd * q.Wd * q.Cd, total = n * num_frames;
-    const long long to_boundary = (long long)(((16u - (unsigned)((uintptr_t)top_dev & 15u)) & 15u) / 4u);      // 0 .. 3 elements
-    const int head = (int)(to_boundary < total ? to_boundary : total);
-    const long long nvec = (total - head) / 4;
-    const int tail = (int)(total - head - 4 * nvec);
+    int head, tail;
+    long long nvec;
+    bev_flat_split(top_dev, total, head, nvec, tail);
     const long long clear_groups = nvec / 1024 + 1, resolve_groups = nvec / 512 + 1;
     if (resolve_groups > 0x7FFFFFFFll) return MV3D_ERR_INVALID_ARG;
     hipLaunchKernelGGL(bevb_clear_kernel, dim3((unsigned)clear_groups), dim3(256), 0, s, top_dev, head, nvec, tail, status_dev);

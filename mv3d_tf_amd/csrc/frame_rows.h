@@ -1,5 +1,5 @@
 // Which frame owns a row of `num_frames` clouds laid back to back: the one statement of the rule for every scatter kernel that takes
-// (points, offsets) -- fv_scatter_kernel (front_view_raster.hip) and bevb_scatter_kernel (bev_raster.hip).
+// (points, offsets) -- fv_scatter_kernel (front_view_raster.hip), bevb_scatter_kernel (bev_raster.hip) and bevp_scatter_kernel (bev_paper.hip).
 // Frame b owns rows offsets[b] .. offsets[b + 1].  The frame of row p is the LAST b with offsets[b] <= p (a binary search over the
 // offsets staged in LDS; equal neighbours = an empty frame, skipped by that rule).  A row outside [offsets[b], offsets[b + 1]) -- in
 // front of offsets[0], behind offsets[num_frames], or anything under offsets that do not ascend -- belongs to NO frame and is skipped.

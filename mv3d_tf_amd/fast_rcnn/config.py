@@ -94,6 +94,14 @@ cfg.FRONT_VIEW_INPUT = False
 # records no lidar_bv_path, and get_minibatch, detect_batch.test_net and rpn_msr.generate.imdb_proposals never open a stored map.  With
 # FRONT_VIEW_INPUT also on, both rasters read one upload of the scan.  False = the stored maps, every blob and code path as before.
 cfg.LIDAR_BV_FROM_SCAN = False
+# (not in the reference) what the rasterised `lidar_bv_data` holds.  'reference' = point_cloud_2_top's map, (601, 601, 9): per height
+# slice the LAST point written, and the reflectance of the last slice's last point.  'paper' = the MV3D paper's encoding (section 3.1;
+# ops.point_cloud_2_top_paper), (601, 601, 10): per slice the MAXIMAL height, the reflectance of the cell's
+# highest point, and the density min(1, log(N + 1) / log 64); it does not depend on the order of the points, and the network's BEV
+# conv1_1 takes 10 channels (MV3D(bev_channels=None) follows this key).  Parity unpinned, no accuracy claim.  'paper' needs
+# LIDAR_BV_FROM_SCAN, because stored lidar_bv/*.npy maps are reference-encoded: prepare_roidb and the detection loops raise
+# ValueError otherwise, and for any other value (ops.bev_encoding).
+cfg.LIDAR_BV_ENCODING = 'reference'
 # (not in the reference, which subtracts PIXEL_MEANS on the host, frame by frame, and uploads f32) True: `image_data` is built on the
 # device from ONE upload of the frames' uint8 pixels (ops.image_blob) by get_minibatch, detect_batch.test_net
 # and rpn_msr.generate.imdb_proposals; the two loops then group frames by BEV shape only and pad a group's frames to one canvas, the

@@ -113,6 +113,7 @@ def scan_source(imdb, needed_by):
 def loop_scan_source(net, imdb):
     """(i -> scan or None, maps_from_scans) for a detection loop: a three-view network needs the scans for `lidar_fv_data`,
     cfg.LIDAR_BV_FROM_SCAN for `lidar_bv_data` of any network; None when neither asks"""
+    ops.bev_encoding()                                      # 'paper' without LIDAR_BV_FROM_SCAN, or an unknown value: ValueError here
     from_scan = bool(cfg.LIDAR_BV_FROM_SCAN)
     points_of = front_view_source(net, imdb)
     return (scan_source(imdb, "cfg.LIDAR_BV_FROM_SCAN") if points_of is None and from_scan else points_of), from_scan
@@ -120,14 +121,14 @@ def loop_scan_source(net, imdb):
 
 def scan_feed(clouds, bev, fv):
     """the feed entries a group of frames gets from its scans: the clouds are concatenated and uploaded ONCE, and `lidar_bv_data`
-    (bev true: one ops.point_cloud_2_top_batch call) and `lidar_fv_data` (fv true: one ops.point_cloud_2_front call) are rasterised
+    (bev true: one ops.scan_bev call, the raster cfg.LIDAR_BV_ENCODING names) and `lidar_fv_data` (fv true: one ops.point_cloud_2_front call) are rasterised
     from that one device tensor"""
     feed = {}
     if bev or fv:
         pts = ops._dev(np.concatenate(clouds, 0))
         offsets = np.cumsum([0] + [len(c) for c in clouds])
         if bev:
-            feed["lidar_bv_data"] = ops.point_cloud_2_top_batch(pts, offsets=offsets)
+            feed["lidar_bv_data"] = ops.scan_bev(pts, offsets=offsets)
         if fv:
             feed["lidar_fv_data"] = ops.point_cloud_2_front(pts, offsets=offsets)
     return feed

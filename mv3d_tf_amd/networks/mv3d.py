@@ -60,7 +60,7 @@ def draw_drop_path(rng, views):
 class MV3D:
     """One class for both graphs; `phase` is 'TEST' (MV3D_test) or 'TRAIN' (MV3D_train)."""
 
-    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2, fusion=None, roi_upsample=None):
+    def __init__(self, phase="TEST", trainable=True, device=None, seed=0, views=2, fusion=None, roi_upsample=None, bev_channels=None):
         """views = 2: the reference's graphs (BEV + RGB towers).  views = 3 adds the front view the MV3D paper has and the
         reference leaves a TODO (`proposal_transform`, network.py:293-315): a third VGG16 trunk on `lidar_fv_data`
         (1, 64, 512, 3), `rois_fv` = mv3d_rois_3d_to_fv(rois_3d), a third RoiPool `pool_5_3` and tower fc6_3 / fc7_3, the
@@ -68,7 +68,10 @@ class MV3D:
         fusion = 'early' (the reference's head) | 'deep' (the paper's deep fusion: the views are joined by an element-wise mean after
         fc6 and after fc7, cls_score / bbox_pred read the 2048-wide join); None = cfg.FUSION.
         roi_upsample = (BEV, image, front view) factors, each 1, 2 or 4: the paper's bilinear upsampling of conv5_3* in front of RoiPool
-        (section 3.2: (4, 2, 4)); (1, 1, 1) = the reference's graphs; None = cfg.ROI_UPSAMPLE."""
+        (section 3.2: (4, 2, 4)); (1, 1, 1) = the reference's graphs; None = cfg.ROI_UPSAMPLE.
+        bev_channels = the channels of `lidar_bv_data`, i.e. the input width of the BEV trunk's conv1_1, the only variable it changes:
+        9 = the reference's map, 10 = the paper's encoding (ops.point_cloud_2_top_paper); None = what
+        cfg.LIDAR_BV_ENCODING gives (ops.bev_channels).  forward() raises ValueError for a map of another width."""
         self.phase = phase
         self.views = int(views)
         self.fusion = cfg.FUSION if fusion is None else fusion
@@ -78,6 +81,9 @@ class MV3D:
         if not isinstance(up, (tuple, list)) or len(up) != 3 or any(isinstance(s, bool) or s not in (1, 2, 4) for s in up):
             raise ValueError("roi_upsample must be three factors (BEV, image, front view), each 1, 2 or 4, got %r" % (up,))
         self.roi_upsample = tuple(int(s) for s in up)
+        self.bev_channels = ops.bev_channels() if bev_channels is None else bev_channels
+        if isinstance(self.bev_channels, bool) or not isinstance(self.bev_channels, int) or self.bev_channels < 1:
+            raise ValueError("bev_channels must be a positive int, got %r" % (bev_channels,))
         # drop-path draws of the deep head (cfg.TRAIN.DROP_PATH): the network's own generator, never numpy's global one (the
         # target layers' draw stream is the reference's); the same seed on every rank
         self.drop_path_rng = np.random.RandomState(cfg.RNG_SEED)
@@ -110,8 +116,8 @@ class MV3D:
             b = torch.zeros(shape[0], device=self.device, requires_grad=trainable)
             self.params[name] = [w, b]
 
-        trunks = (("", 9), ("_2", 3)) + ((("_3", 3),) if self.views == 3 else ())
-        for suffix, cin in trunks:                                 # BEV trunk (9 ch), RGB trunk (3 ch) [, FV trunk (3 ch)]
+        trunks = (("", self.bev_channels), ("_2", 3)) + ((("_3", 3),) if self.views == 3 else ())
+        for suffix, cin in trunks:                                 # BEV trunk (9 ch; 10 for the paper's map), RGB trunk (3 ch) [, FV trunk (3 ch)]
             c = cin
             for stem, cout, _ in _VGG:
                 var(stem + suffix, (cout, c, 3, 3), 0.01)
@@ -451,6 +457,9 @@ class MV3D:
         dev = self.device
         to_dev = lambda a: a.to(dev) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32)).to(dev)
         self._stage_host_inputs(feed, L, dev, to_dev)
+        if L["lidar_bv_data"].shape[-1] != self.bev_channels:
+            raise ValueError("lidar_bv_data has %d channels, the network's BEV trunk takes %d (bev_channels; cfg.LIDAR_BV_ENCODING)"
+                             % (L["lidar_bv_data"].shape[-1], self.bev_channels))
         keep_prob = float(feed.get("keep_prob", self.keep_prob))
         self._step_half = None
         if self.cast_many and self.amp_dtype is not None and self.phase == "TRAIN" and torch.is_grad_enabled():

@@ -768,6 +768,90 @@ def point_cloud_2_top_batch(points, offsets=None, ranges=None, out=None):
     return out
 
 
+BEV_PAPER_SHAPE = (601, 601, 10)     # the paper's encoding of the same call: rows x columns x (8 slices + top intensity + density)
+
+
+def _ranges8(fn, ranges):
+    """ranges -> the (8) C doubles the BEV entries take, None for None (anything but 8 numbers: ctypes / float raise TypeError or
+    ValueError here)"""
+    return None if ranges is None else (C.c_double * 8)(*[float(v) for v in ranges])
+
+
+def point_cloud_2_top_paper_workspace_bytes(num_frames=1, ranges=None):
+    """bytes of workspace ops.point_cloud_2_top_paper needs for num_frames frames of these ranges: 8 per cell and frame"""
+    return int(lib().mv3d_point_cloud_2_top_paper_workspace(int(num_frames), _ranges8("point_cloud_2_top_paper", ranges)))
+
+
+def bev_density_table():
+    """the 64 f32 density values T[n] = min(1, log(n + 1) / log 64) as the library computes them (mv3d_bev_density_table, host only)"""
+    out = (C.c_float * 64)()
+    check(lib().mv3d_bev_density_table(out), "mv3d_bev_density_table")
+    return np.frombuffer(out, np.float32).copy()
+
+
+def point_cloud_2_top_paper(points, offsets=None, ranges=None, out=None, workspace=None):
+    """The MV3D paper's BEV encoding (csrc/bev_paper.hip; parity unpinned, the definition is
+    tests/bev_paper_restatement.py) of B clouds behind three launches, argument for argument ops.point_cloud_2_top_batch and with its
+    kept rows, cells and slices: the result is (B,601,601,10) f32 on the device -- (601,601,10) without offsets -- or (.., H, W, M + 2)
+    for ranges = (res, zres, side_lo, side_hi, fwd_lo, fwd_hi, height_lo, height_hi), M = ceil((height_hi - height_lo) / zres):
+    channels < M the maximal z - height_lo of each height slice, channel M the reflectance of the cell's highest point (among equal
+    heights the last row), channel M + 1 the density min(1, log(N + 1) / log 64) of the cell's N kept points; an empty cell is 0.
+    With ranges ONE status word is read back (a synchronisation) to raise IndexError where point_cloud_2_top_batch does.
+    out = a contiguous f32 device tensor of the result's shape (any run of frames of a larger buffer: 4-byte alignment is all it
+    needs), workspace = a uint8 device tensor of point_cloud_2_top_paper_workspace_bytes(B, ranges) bytes, 16-byte aligned (default: the
+    reused per-stream buffer); with both given, device inputs and no ranges the call allocates nothing and can be captured.
+    Every argument is checked before anything is launched, as ops.point_cloud_2_top_batch checks it."""
+    fn = "point_cloud_2_top_paper"
+    r = None
+
+    def frame():
+        nonlocal r
+        if ranges is None:
+            return BEV_PAPER_SHAPE
+        r = _ranges8(fn, ranges)
+        dims = (C.c_int * 3)()
+        if lib().mv3d_point_cloud_2_top_paper_shape(*r, dims) != _lib.OK:
+            raise ValueError("{}: ranges {} are empty, inverted or beyond 32767 cells / 31 slices".format(fn, tuple(r)))
+        return tuple(dims)
+
+    need = lambda B: int(lib().mv3d_point_cloud_2_top_paper_workspace(B, r))
+    pts, off, B, P, out, dev = _scan_args(fn, points, offsets, frame, out, workspace, need, frame_rows=BEV_MAX_FRAME_POINTS)
+    if workspace is None:
+        workspace = _workspace(need(B), dev, "bev_paper")
+    elif workspace.data_ptr() % 16:
+        raise ValueError("{}: workspace must be 16-byte aligned".format(fn))
+    status = None if r is None else torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib().mv3d_point_cloud_2_top_paper_batch(_ptr(pts), _ptr(off), B, P, r, _ptr(out), _ptr(workspace), _ptr(status), _stream()),
+          "mv3d_point_cloud_2_top_paper_batch")
+    if status is not None and int(status.item()):
+        raise IndexError("{}: a point's cell lies outside the map (numpy raises IndexError there)".format(fn))
+    return out
+
+
+def bev_encoding():
+    """cfg.LIDAR_BV_ENCODING checked: 'reference' or 'paper'; 'paper' without cfg.LIDAR_BV_FROM_SCAN raises ValueError (stored
+    lidar_bv/*.npy maps are reference-encoded), as does any other value.  prepare_roidb and the detection loops call it before they
+    load a frame."""
+    from .fast_rcnn.config import cfg
+    enc = cfg.LIDAR_BV_ENCODING
+    if enc not in ("reference", "paper"):
+        raise ValueError("cfg.LIDAR_BV_ENCODING must be 'reference' or 'paper', got %r" % (enc,))
+    if enc == "paper" and not cfg.LIDAR_BV_FROM_SCAN:
+        raise ValueError("cfg.LIDAR_BV_ENCODING = 'paper' needs cfg.LIDAR_BV_FROM_SCAN: stored bird's-eye-view maps are reference-encoded")
+    return enc
+
+
+def bev_channels():
+    """channels of the network's `lidar_bv_data` under cfg.LIDAR_BV_ENCODING: 10 for 'paper', else 9"""
+    return BEV_PAPER_SHAPE[2] if bev_encoding() == "paper" else BEV_SHAPE[2]
+
+
+def scan_bev(points, offsets=None):
+    """The network's `lidar_bv_data` from scans on the device, for every feed (get_minibatch, detect_batch.scan_feed): the raster
+    cfg.LIDAR_BV_ENCODING names, on MV3D's ranges -- ops.point_cloud_2_top_batch ('reference') or ops.point_cloud_2_top_paper."""
+    return (point_cloud_2_top_paper if bev_encoding() == "paper" else point_cloud_2_top_batch)(points, offsets=offsets)
+
+
 def gt_encode(box_cam, cos_sin, inv_rot, tr):
     """box_cam (G,6) f32, cos_sin (G,2) f64, inv_rot (9) f32, tr (12) f32 device tensors -> (corners_cam (G,24),
     corners_lidar (G,24), boxes_3d (G,6), boxes_bv (G,4)) f32 in ONE buffer (pack, views): a host caller fetches it with

@@ -13,7 +13,8 @@ cfg.FRONT_VIEW_INPUT (not in the reference; default off = the blobs above exactl
 input, as a device tensor: see `front_view_blob`.
 cfg.LIDAR_BV_FROM_SCAN (not in the reference; default off) takes `lidar_bv_data` of an entry without an in-memory 'lidar_bv' from its
 scan ('velodyne' array or 'velodyne_path' file) instead of 'lidar_bv_path': a (1,601,601,9) device tensor rasterised by
-ops.point_cloud_2_top_batch, im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters.
+ops.scan_bev -- ops.point_cloud_2_top_batch, or under cfg.LIDAR_BV_ENCODING = 'paper' ops.point_cloud_2_top_paper and (1,601,601,10) --,
+im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters.
 cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`."""
 import numpy as np
 import numpy.random as npr
@@ -88,7 +89,7 @@ def get_minibatch(roidb, num_classes):
         # no stored map: the scan is uploaded once (a mirrored frame's with y negated, whose raster IS the column-reversed map:
         # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror) and rasterised on the device
         cloud = ops._dev(_entry_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv'))
-        blobs = {'image_data': image_data, 'lidar_bv_data': ops.point_cloud_2_top_batch(cloud)[None], 'calib': entry['calib']}
+        blobs = {'image_data': image_data, 'lidar_bv_data': ops.scan_bev(cloud)[None], 'calib': entry['calib']}
         blobs.update(gt_blobs(entry, ops.BEV_SHAPE))
         if entry.get('flipped', False) and not on_device:
             blobs['image_data'] = ops.mirror_columns(ops._dev(blobs['image_data']))
