@@ -223,6 +223,21 @@ size_t mv3d_roi_pool_backward_workspace_bytes(int num_views, const mv3d_roi_grad
  * no scratch memory and is slower (one launch, XCD-sliced, geometry recomputed per slice). */
 int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
                                  void *workspace, size_t workspace_bytes, void *stream);
+/* Host only (no device, no environment): the name of the body that runs such a RoiPoolGrad call -- mv3d_roi_pool_backward,
+ * mv3d_roi_pool_backward_views and mv3d_roi_pool_backward_views_pair launch what this very selection returns, and the pair's forward
+ * and decode ask it whether the argmax plane holds compact codes.  have_workspace != 0: a workspace of at least
+ * mv3d_roi_pool_backward_workspace_bytes() bytes is given (a shorter one counts as none); pair != 0: the call goes through the pair's
+ * entries.  Pointers in `views` may be NULL, as for the size queries; the alignment conditions apply where they are given.
+ *   "generic"   any view outside the sliced kernel's shapes (C no multiple of 64 or > 4096, PH * PW > 512, a pooled size > 255,
+ *               2^26 pixels or more): one launch per view, C <= 4096 (16-byte aligned buffers, C % 4 == 0) or <= 1024
+ *   "sliced"    one launch, 64-channel slices, no scratch memory
+ *   "indexed"   index + gather (three launches): have_workspace, same C in {64, 128, 256, 512} for all views, pooled sizes <= 15,
+ *               16-byte aligned buffers
+ *   "tiles"     the pair's LDS map tiles: pair, the indexed conditions, C in {256, 512}, every view with at least one ROI and a map of
+ *               at most 65534 pixels
+ * A static string, or NULL where the entries return MV3D_ERR_INVALID_ARG for the shapes. */
+const char *mv3d_roi_pool_backward_path(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
+                                        int have_workspace, int pair);
 
 /* The PAIR: RoiPool and RoiPoolGrad of a training step with a PRIVATE argmax plane between them (the fast training path).
  * `top_data` and `bottom_diff` are bit-identical to mv3d_roi_pool_forward_views / mv3d_roi_pool_backward_views.

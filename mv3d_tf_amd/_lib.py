@@ -225,6 +225,7 @@ _SIGS = {
     "mv3d_roi_pool_forward_views_half": (C.c_int, [C.c_int, C.POINTER(RoiView), C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "mv3d_roi_pool_backward_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiGradView), C.c_int, C.c_int]),
     "mv3d_roi_pool_backward_views": (C.c_int, [C.c_int, C.POINTER(RoiGradView), C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "mv3d_roi_pool_backward_path": (C.c_char_p, [C.c_int, C.POINTER(RoiGradView), C.c_int, C.c_int, C.c_int, C.c_int]),
     "mv3d_roi_pool_pair_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(RoiGradView), C.c_int, C.c_int]),
     "mv3d_roi_pool_forward_views_pair": (C.c_int, [C.c_int, C.POINTER(RoiView), C.c_int, C.c_int, C.c_int, _P]),
     "mv3d_roi_pool_backward_views_pair": (C.c_int, [C.c_int, C.POINTER(RoiGradView), C.c_int, C.c_int, _P, C.c_size_t, _P]),

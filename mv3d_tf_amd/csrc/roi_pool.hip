@@ -1205,20 +1205,29 @@ extern "C" int mv3d_roi_pool_forward(const float *bottom_data, float spatial_sca
     return mv3d_launch_status();
 }
 
-static int roi_pool_backward_generic(const float *top_diff, float spatial_scale, int batch_size, int num_rois,
-                                     int height, int width, int channels, int pooled_height, int pooled_width,
-                                     const float *bottom_rois, float *bottom_diff, const int32_t *argmax_data,
-                                     void *stream)
+// The generic kernel's vector width (float4 loads when C % 4 == 0 and the buffers, where given, are 16-byte aligned) and its limits:
+// C <= 4096 (vectorised) / 1024 (scalar), batch * height * width inside an int
+static bool bwd_generic_vec4(const mv3d_roi_grad_view &w)
 {
-    if (batch_size <= 0 || num_rois < 0 || height <= 0 || width <= 0 || channels <= 0 || pooled_height <= 0 ||
-        pooled_width <= 0 || !bottom_diff || (num_rois > 0 && (!bottom_rois || !top_diff || !argmax_data)))
-        return MV3D_ERR_INVALID_ARG;
-    if ((long long)height * width * channels > 0x7fffffffLL) return MV3D_ERR_INVALID_ARG;
+    return w.channels % 4 == 0 && (!w.top_diff || aligned16(w.top_diff)) && (!w.bottom_diff || aligned16(w.bottom_diff)) &&
+           (!w.argmax_data || aligned16(w.argmax_data));
+}
+static bool bwd_generic_ok(const mv3d_roi_grad_view &w)
+{
+    return (long long)w.batch_size * w.height * w.width <= 0x7fffffffLL && w.channels / (bwd_generic_vec4(w) ? 4 : 1) <= 64 * 16;
+}
+
+static int roi_pool_backward_generic(const mv3d_roi_grad_view &w, int pooled_height, int pooled_width, void *stream)
+{
+    if (!bwd_generic_ok(w)) return MV3D_ERR_INVALID_ARG;
+    const float *top_diff = w.top_diff, *bottom_rois = w.bottom_rois;
+    float *bottom_diff = w.bottom_diff;
+    const int32_t *argmax_data = w.argmax_data;
+    const float spatial_scale = w.spatial_scale;
+    const int batch_size = w.batch_size, num_rois = w.num_rois, height = w.height, width = w.width, channels = w.channels;
     const long long pixels = (long long)batch_size * height * width;
-    if (pixels > 0x7fffffffLL) return MV3D_ERR_INVALID_ARG;
-    const bool v4 = (channels % 4 == 0) && aligned16(top_diff) && aligned16(bottom_diff) && aligned16(argmax_data);
+    const bool v4 = bwd_generic_vec4(w);
     const int cv = channels / (v4 ? 4 : 1);
-    if (cv > 64 * 16) return MV3D_ERR_INVALID_ARG;       // C <= 4096 (vectorised) / 1024 (scalar)
     const int nacc = cv <= 64 ? 1 : (cv <= 128 ? 2 : (cv <= 256 ? 4 : (cv <= 512 ? 8 : 16)));
     const unsigned blocks = (unsigned)((pixels + BWD_PIX - 1) / BWD_PIX);
     hipStream_t s = (hipStream_t)stream;
@@ -1428,46 +1437,86 @@ static int bwd_gather_groups()
 #endif
 }
 
-static int grad_views_check(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width)
+// the shape half of the backward entries' argument check (the query below answers from it alone, pointers may be NULL there)
+static bool grad_views_shapes_ok(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width)
 {
-    if (num_views <= 0 || num_views > MV3D_MAX_ROI_VIEWS || !views || pooled_height <= 0 || pooled_width <= 0)
-        return MV3D_ERR_INVALID_ARG;
+    if (num_views <= 0 || num_views > MV3D_MAX_ROI_VIEWS || !views || pooled_height <= 0 || pooled_width <= 0) return false;
     for (int k = 0; k < num_views; ++k) {
         const mv3d_roi_grad_view &w = views[k];
-        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 || !w.bottom_diff ||
-            (w.num_rois > 0 && (!w.bottom_rois || !w.top_diff || !w.argmax_data)) ||
+        if (w.batch_size <= 0 || w.num_rois < 0 || w.height <= 0 || w.width <= 0 || w.channels <= 0 ||
             (long long)w.height * w.width * w.channels > 0x7fffffffLL ||
             (long long)w.num_rois * pooled_height * pooled_width > 0x7fffffffLL)
-            return MV3D_ERR_INVALID_ARG;
+            return false;
+    }
+    return true;
+}
+
+static int grad_views_check(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width)
+{
+    if (!grad_views_shapes_ok(num_views, views, pooled_height, pooled_width)) return MV3D_ERR_INVALID_ARG;
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_grad_view &w = views[k];
+        if (!w.bottom_diff || (w.num_rois > 0 && (!w.bottom_rois || !w.top_diff || !w.argmax_data))) return MV3D_ERR_INVALID_ARG;
     }
     return MV3D_OK;
 }
 
-extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
-                                            void *workspace, size_t workspace_bytes, void *stream)
+// ---------------------------------------------------------------------------------------------------------------
+// Which body runs a RoiPoolGrad call: THE decision of the three backward entries (they launch what this returns) and of the pair's
+// forward and decode ("tiles" or not).  Shapes and, where given, pointer alignment only.
+static const char ROI_GRAD_GENERIC[] = "generic", ROI_GRAD_SLICED[] = "sliced", ROI_GRAD_INDEXED[] = "indexed", ROI_GRAD_TILES[] = "tiles";
+static bool roi_pair_shapes(int num_views, const mv3d_roi_grad_view *g, int PH, int PW);
+
+extern "C" const char *mv3d_roi_pool_backward_path(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
+                                                   int have_workspace, int pair)
 {
-    const int rc0 = grad_views_check(num_views, views, pooled_height, pooled_width);
-    if (rc0 != MV3D_OK) return rc0;
+    if (!grad_views_shapes_ok(num_views, views, pooled_height, pooled_width)) return nullptr;
+    if (pair && roi_pair_shapes(num_views, views, pooled_height, pooled_width)) return ROI_GRAD_TILES;
     bool fast = true;
     for (int k = 0; k < num_views; ++k)
         fast = fast && bwd_fast_ok(views[k].channels, pooled_height, pooled_width, views[k].height, views[k].width, views[k].batch_size);
-    if (workspace && ((uintptr_t)workspace % MV3D_ALIGN)) return MV3D_ERR_WORKSPACE;
     if (!fast) {                                          // generic shapes: one launch of the generic kernel per view
+        for (int k = 0; k < num_views; ++k)
+            if (!bwd_generic_ok(views[k])) return nullptr;
+        return ROI_GRAD_GENERIC;
+    }
+    if (have_workspace && bwd_index_eligible(num_views, views, pooled_height, pooled_width)) {
+        size_t pool_entries = 0;                          // pool offsets are 31-bit
+        for (int k = 0; k < num_views; ++k) pool_entries += bwd_pool_entries(views[k], pooled_height, pooled_width);
+        return pool_entries > 0x7fffffffull ? nullptr : ROI_GRAD_INDEXED;
+    }
+    return ROI_GRAD_SLICED;
+}
+
+static int roi_pool_backward_run(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
+                                 void *workspace, size_t workspace_bytes, bool pair, void *stream)
+{
+    const int rc0 = grad_views_check(num_views, views, pooled_height, pooled_width);
+    if (rc0 != MV3D_OK) return rc0;
+    if (workspace && ((uintptr_t)workspace % MV3D_ALIGN)) return MV3D_ERR_WORKSPACE;
+    // a workspace shorter than the index needs counts as none
+    const bool have_ws = workspace &&
+                         workspace_bytes >= mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);
+    const char *path = mv3d_roi_pool_backward_path(num_views, views, pooled_height, pooled_width, have_ws, pair);
+    if (!path) return MV3D_ERR_INVALID_ARG;
+    if (path == ROI_GRAD_TILES) {
+        // the decision mv3d_roi_pool_forward_views_pair took from the same shapes: compact codes in argmax_data
+        for (int k = 0; k < num_views; ++k)
+            if (!aligned16(views[k].bottom_diff) || !aligned16(views[k].top_diff) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
+        // ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip): the round-5 structure it replaced (index +
+        // zero fill, gather: three launches) was level alone and 3 - 7 % slower in the path (profiles/r06_g)
+        return mv3d_launch_roi_pair_tiles(num_views, views, pooled_height, pooled_width, (hipStream_t)stream);
+    }
+    if (path == ROI_GRAD_GENERIC) {
         for (int k = 0; k < num_views; ++k) {
-            const mv3d_roi_grad_view &w = views[k];
-            const int rc = roi_pool_backward_generic(w.top_diff, w.spatial_scale, w.batch_size, w.num_rois, w.height, w.width,
-                                                     w.channels, pooled_height, pooled_width, w.bottom_rois, w.bottom_diff,
-                                                     w.argmax_data, stream);
+            const int rc = roi_pool_backward_generic(views[k], pooled_height, pooled_width, stream);
             if (rc != MV3D_OK) return rc;
         }
         return MV3D_OK;
     }
-    const bool indexed = workspace && bwd_index_eligible(num_views, views, pooled_height, pooled_width) &&
-                         workspace_bytes >= mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);
-    if (indexed) {
+    if (path == ROI_GRAD_INDEXED) {
         // the gather's 64-channel slices, one per XCD or XCD group: the slice count divides 8 (C = 64, 128, 256 or 512)
         const int nsl = views[0].channels / 64;
-        if (nsl > 8 || 8 % nsl != 0) return MV3D_ERR_INVALID_ARG;
         BwdIndexPlan pl;
         const int rc = bwd_index_plan(num_views, views, pooled_height, pooled_width, workspace, pl);
         if (rc != MV3D_OK) return rc;
@@ -1501,6 +1550,12 @@ extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_v
     for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
     hipLaunchKernelGGL(roi_pool_bwd_sliced_kernel, dim3(blocks), dim3(BW_THREADS), carry, (hipStream_t)stream, p);
     return mv3d_launch_status();
+}
+
+extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
+                                            void *workspace, size_t workspace_bytes, void *stream)
+{
+    return roi_pool_backward_run(num_views, views, pooled_height, pooled_width, workspace, workspace_bytes, false, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1542,7 +1597,7 @@ extern "C" int mv3d_roi_pool_forward_views_pair(int num_views, const mv3d_roi_vi
     if (rc0 != MV3D_OK) return rc0;
     mv3d_roi_grad_view g[MV3D_MAX_ROI_VIEWS];
     grad_views_of(num_views, views, g);
-    if (!roi_pair_shapes(num_views, g, pooled_height, pooled_width))
+    if (mv3d_roi_pool_backward_path(num_views, g, pooled_height, pooled_width, 0, 1) != ROI_GRAD_TILES)
         // shapes outside the pair's kernels: the plain forward (int32 argmax plane); mv3d_roi_pool_backward_views_pair takes the same
         // decision from the same shapes
         return roi_pool_forward_views_impl(num_views, views, pooled_height, pooled_width, cold_maps != 0, stream);
@@ -1564,17 +1619,7 @@ extern "C" int mv3d_roi_pool_forward_views_pair(int num_views, const mv3d_roi_vi
 extern "C" int mv3d_roi_pool_backward_views_pair(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
                                                  void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int rc0 = grad_views_check(num_views, views, pooled_height, pooled_width);
-    if (rc0 != MV3D_OK) return rc0;
-    if (workspace && ((uintptr_t)workspace % MV3D_ALIGN)) return MV3D_ERR_WORKSPACE;
-    // the decision mv3d_roi_pool_forward_views_pair took from the same shapes: compact codes in argmax_data?
-    if (!roi_pair_shapes(num_views, views, pooled_height, pooled_width))
-        return mv3d_roi_pool_backward_views(num_views, views, pooled_height, pooled_width, workspace, workspace_bytes, stream);
-    for (int k = 0; k < num_views; ++k)
-        if (!aligned16(views[k].bottom_diff) || !aligned16(views[k].top_diff) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
-    // ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip): the round-5 structure it replaced (index +
-    // zero fill, gather: three launches) was level alone and 3 - 7 % slower in the path (profiles/r06_g)
-    return mv3d_launch_roi_pair_tiles(num_views, views, pooled_height, pooled_width, (hipStream_t)stream);
+    return roi_pool_backward_run(num_views, views, pooled_height, pooled_width, workspace, workspace_bytes, true, stream);
 }
 
 // The argmax plane a forward of the pair left in `argmax_data` -> the reference's int32 plane (num_rois, PH, PW, C) in `argmax_out`
@@ -1590,7 +1635,7 @@ extern "C" int mv3d_roi_pool_argmax_decode(int num_views, const mv3d_roi_view *v
         if (views[k].num_rois > 0 && !argmax_out[k]) return MV3D_ERR_INVALID_ARG;
     mv3d_roi_grad_view g[MV3D_MAX_ROI_VIEWS];
     grad_views_of(num_views, views, g);
-    const bool pair = roi_pair_shapes(num_views, g, pooled_height, pooled_width);
+    const bool pair = mv3d_roi_pool_backward_path(num_views, g, pooled_height, pooled_width, 0, 1) == ROI_GRAD_TILES;
     for (int k = 0; k < num_views; ++k) {
         const mv3d_roi_view &w = views[k];
         const long long total = (long long)w.num_rois * pooled_height * pooled_width * w.channels;

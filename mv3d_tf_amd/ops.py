@@ -564,13 +564,17 @@ def roi_pool_forward_views(views, pooled_height, pooled_width, outs=None, cold_m
     return res
 
 
-def roi_pool_backward_views(views, pooled_height, pooled_width, outs=None):
+def roi_pool_backward_views(views, pooled_height, pooled_width, outs=None, workspace=None):
     """views: list of (top_diff (R,PH,PW,C), rois (R,5), argmax (R,PH,PW,C) i32, data_shape (B,H,W,C), spatial_scale);
-    RoiPoolGrad of all of them behind one call.  Returns [bottom_diff, ...]; pass `outs` to reuse output tensors."""
+    RoiPoolGrad of all of them behind one call.  Returns [bottom_diff, ...]; pass `outs` to reuse output tensors.
+    workspace = None: the cached buffer of mv3d_roi_pool_backward_workspace_bytes bytes (index + gather for the shapes that take it);
+    False: none (the sliced kernel for those shapes); a uint8 tensor: handed to the entry as is (same results every way)."""
     arr, res = _roi_grad_views(views, outs)
-    nbytes = lib().mv3d_roi_pool_backward_workspace_bytes(len(views), arr, pooled_height, pooled_width)
-    ws = _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
-    check(lib().mv3d_roi_pool_backward_views(len(views), arr, pooled_height, pooled_width, _ptr(ws), ws.numel(), _stream()),
+    if workspace is None:
+        nbytes = lib().mv3d_roi_pool_backward_workspace_bytes(len(views), arr, pooled_height, pooled_width)
+        workspace = _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
+    wp, wn = (None, 0) if workspace is False else (_ptr(workspace), workspace.numel())
+    check(lib().mv3d_roi_pool_backward_views(len(views), arr, pooled_height, pooled_width, wp, wn, _stream()),
           "mv3d_roi_pool_backward_views")
     return res
 

@@ -52,6 +52,21 @@ def test_workspace_queries_and_argument_validation(hiplib):
                               None) == hiplib.ERR_INVALID_ARG
     assert L.mv3d_roi_pool_forward(None, 0.125, 1, 4, 8, 8, 16, 7, 7, None, None, None, None) == hiplib.ERR_INVALID_ARG
     assert L.mv3d_nms_device(None, 10, 0.7, 0, None, None, None, None, 0, None) == hiplib.ERR_INVALID_ARG
+    # RoiPoolGrad's body query: NULL where the entries refuse the shapes (and the entries do refuse them, before any HIP call)
+    gv = lambda Cc, R=4, H=8, W=8: hiplib.RoiGradView(None, None, None, None, 0.125, 1, R, H, W, Cc)      # noqa: E731
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(64)), 7, 7, 0, 0) == b"sliced"
+    assert L.mv3d_roi_pool_backward_path(1, None, 7, 7, 0, 0) is None
+    assert L.mv3d_roi_pool_backward_path(0, C.byref(gv(64)), 7, 7, 0, 0) is None
+    assert L.mv3d_roi_pool_backward_path(5, (hiplib.RoiGradView * 5)(*[gv(64)] * 5), 7, 7, 0, 0) is None
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(64)), 0, 7, 0, 0) is None
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(0)), 7, 7, 1, 1) is None
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(64, R=-1)), 7, 7, 0, 0) is None
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(1025)), 7, 7, 0, 0) is None                       # generic, scalar loads: C <= 1024
+    assert L.mv3d_roi_pool_backward_path(1, C.byref(gv(64, H=40000, W=40000)), 7, 7, 0, 0) is None       # H * W * C beyond an int
+    bad = hiplib.RoiGradView(4096, 4096, 4096, 4096, 0.125, 1, 4, 8, 8, 1025)     # (non-NULL "pointers", never dereferenced)
+    assert L.mv3d_roi_pool_backward_views(1, C.byref(bad), 7, 7, None, 0, None) == hiplib.ERR_INVALID_ARG
+    assert L.mv3d_roi_pool_backward_views_pair(1, C.byref(bad), 7, 7, None, 0, None) == hiplib.ERR_INVALID_ARG
+    assert L.mv3d_roi_pool_backward(4096, 0.125, 1, 4, 8, 8, 1025, 7, 7, 4096, 4096, 4096, None) == hiplib.ERR_INVALID_ARG
     # the MFMA convolution: NULL / misaligned pointers, channel counts the tiles do not cover, buffers beyond 32-bit offsets
     A = 4096                                                             # a non-NULL, 16-byte aligned "pointer" (never dereferenced)
     assert L.mv3d_conv3x3_f16(None, A, A, A, 1, 8, 8, 64, 64, 1, 0, 1, None) == hiplib.ERR_INVALID_ARG

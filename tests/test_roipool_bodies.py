@@ -1,0 +1,556 @@
+"""Every RoiPoolGrad body at every pooled size it promises, on the forward's own argmax plane and on foreign planes.
+
+RoiPoolGrad has four device bodies behind three entries; mv3d_roi_pool_backward_path names the one a call takes:
+
+    generic   roi_pool_bwd_kernel<VEC, NACC>                    any shape; one launch per view
+    sliced    roi_pool_bwd_sliced_kernel                        C % 64 == 0, PH * PW <= 512
+    indexed   roi_bwd_index_kernel x 2 + roi_bwd_gather_kernel  a workspace, C in {64, 128, 256, 512}, pooled sizes <= 15
+    tiles     roi_pair_tiles_kernel (csrc/roi_grad_tiles.hip)   the pair's entries, C in {256, 512}, pooled sizes <= 15
+
+THE TABLE (CASES below, built from these rules; test_table_covers_every_body_and_pooled_size checks it):
+
+    maps         view A (2, 10, 19, C): one 16-pixel segment + a tail of 3;  B (1, 6, 33, C): two segments + a tail of 1;
+                 C (3, 1, 5, C);  the plain entries also get a view with R = 0 and NULL ROI / top_diff / argmax pointers
+    populations  edges  the rows of edge_rois (tests/golden/make_roipool_golden.py) + 40 random boxes that partly leave the map
+                 stack  300 copies of a one-pixel ROI on an interior pixel + 300 on the map's last pixel
+                 cover  70 ROIs that each contain the whole map
+                 many   700 random boxes
+    pooled       all bodies: POOLED_ALL; sliced and generic: + (16, 16), (22, 23); generic: + (23, 23) at C = 64
+    rows         every (body, pooled size) runs `edges`; stack and cover run at (1,1), (7,7), (8,8), (15,15); many at (7,7), (15,15)
+    scale        SCALES, rotating with the pooled size and the population (every body sees every scale)
+    channels     rotating with the pooled size, per body: BODY_WIDTHS (the big populations take each body's narrowest width)
+
+Inputs come from seeds and depend on (population, pooled size, scale, C) only, so bodies that can take the same call get the same
+inputs.  Expected values come from oracle.roi_pool / roi_pool_grad at test time; the CPU half checks that
+roipool_restatement (written from the CUDA kernels) agrees with the oracle (written from the CPU op) bit for bit on every case, on
+the own plane and on the foreign one.  Every comparison is on bits (int32 views); there is no tolerance anywhere."""
+import ctypes as C
+import functools
+import os
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+import roipool_restatement as rs
+from conftest import GOLDEN, ROOT
+
+sys.path.insert(0, GOLDEN)
+from make_roipool_golden import edge_rois  # noqa: E402
+
+VIEWS = [(2, 10, 19), (1, 6, 33), (3, 1, 5)]                # (B, H, W) of views A, B, C
+EMPTY_VIEW = (1, 3, 4)                                     # the R = 0 view of the plain entries
+SCALES = [0.125, 0.0625, 1.0 / 3.0, 0.5]
+POOLED_ALL = [(1, 1), (1, 15), (15, 1), (2, 2), (3, 5), (7, 7), (8, 8), (9, 7), (5, 13), (15, 15)]
+POOLED_BIG = [(16, 16), (22, 23)]                          # sliced and generic only; 22 x 23 = 506 bins
+POOLED_OVER = (23, 23)                                     # 529 > BW_CAND bins: generic even at C = 64
+POOLED_HEAVY = [(1, 1), (7, 7), (8, 8), (15, 15)]          # stack and cover
+POOLED_MANY = [(7, 7), (15, 15)]
+# (C, workspace given) per body, rotating with the pooled size on the `edges` rows; the first entry serves the big populations
+BODY_WIDTHS = {
+    # vector loads / scalar loads / two accumulators (324 = 81 float4 lanes; 320 is 5 x 64 and takes the sliced body at <= 512 bins,
+    # so it runs as a generic case at POOLED_OVER only)
+    "generic": [(20, False), (6, False), (324, False)],
+    "sliced": [(64, False), (1024, False), (192, True)],   # 192 is not in the index's set: sliced even with a workspace
+    "indexed": [(64, True), (128, True), (256, True), (512, True)],
+    "tiles": [(256, False), (512, False)],
+}
+BODIES = list(BODY_WIDTHS)
+
+
+class Case:
+    def __init__(self, body, C_, pooled, pop, scale, ws):
+        self.body, self.C, self.pooled, self.pop, self.scale, self.ws = body, C_, pooled, pop, scale, ws
+        self.key = (pop, pooled[0], pooled[1], scale, C_)
+        self.id = "%s-C%d-%dx%d-%s-s%.4f%s" % (body, C_, pooled[0], pooled[1], pop, scale, "-ws" if ws else "")
+
+
+def _scale_of(pooled, pop):
+    order = POOLED_ALL + POOLED_BIG + [POOLED_OVER]
+    return SCALES[(order.index(pooled) + ["edges", "stack", "cover", "many"].index(pop)) % 4]
+
+
+def _build_cases():
+    cases = []
+    for body in BODIES:
+        widths = BODY_WIDTHS[body]
+        for i, pooled in enumerate(POOLED_ALL):
+            cases.append(Case(body, widths[i % len(widths)][0], pooled, "edges", _scale_of(pooled, "edges"), widths[i % len(widths)][1]))
+        for pop, sizes in (("stack", POOLED_HEAVY), ("cover", POOLED_HEAVY), ("many", POOLED_MANY)):
+            for pooled in sizes:
+                cases.append(Case(body, widths[0][0], pooled, pop, _scale_of(pooled, pop), widths[0][1]))
+    for i, pooled in enumerate(POOLED_BIG):
+        cases.append(Case("generic", BODY_WIDTHS["generic"][i][0], pooled, "edges", _scale_of(pooled, "edges"), False))
+    cases.append(Case("sliced", 64, (16, 16), "edges", _scale_of((16, 16), "edges"), True))      # too large for the index: sliced
+    cases.append(Case("sliced", 64, (22, 23), "edges", _scale_of((22, 23), "edges"), False))
+    cases.append(Case("sliced", 192, (22, 23), "cover", _scale_of((22, 23), "cover"), True))
+    cases.append(Case("generic", 64, POOLED_OVER, "edges", _scale_of(POOLED_OVER, "edges"), False))
+    cases.append(Case("generic", 320, POOLED_OVER, "edges", _scale_of(POOLED_OVER, "edges"), False))
+    return sorted(cases, key=lambda c: (c.key, c.body))      # cases that share inputs are neighbours
+
+
+CASES = _build_cases()
+PLAIN = [c for c in CASES if c.body != "tiles"]
+KEYS = sorted({c.key for c in CASES})
+FOREIGN_KEYS = sorted({c.key for c in PLAIN})
+
+
+# ------------------------------------------------------------------------------------------------------------------ inputs
+def _seed(key, salt):
+    return zlib.crc32(repr((key, salt)).encode()) & 0x7fffffff
+
+
+def population(pop, rng, B, H, W, scale):
+    """ROIs (R, 5) f32 in input coordinates (map pixels divided by the scale)"""
+    if pop == "edges":
+        r = edge_rois(H, W, B)
+        r[:, 1:] *= 0.125 / scale                            # (edge_rois is written for scale 1 / 8)
+        n = 40
+        x1, y1 = rng.uniform(-W / 2.0, W - 1, n), rng.uniform(-H / 2.0, H - 1, n)
+        x2, y2 = x1 + rng.uniform(0, W, n), y1 + rng.uniform(0, H, n)
+        more = np.stack([rng.randint(0, B, n), x1 / scale, y1 / scale, x2 / scale, y2 / scale], 1)
+        return np.concatenate([r, more.astype(np.float32)])
+    if pop == "stack":
+        a = [0, (W // 2) / scale, (H // 2) / scale, (W // 2) / scale, (H // 2) / scale]
+        b = [B - 1, (W - 1) / scale, (H - 1) / scale, (W - 1) / scale, (H - 1) / scale]
+        return np.array([a] * 300 + [b] * 300, np.float32)
+    if pop == "cover":
+        return np.array([[j % B, -(j % 5) / scale, -(j % 3) / scale, (W - 1 + j % 7) / scale, (H - 1 + j % 4) / scale]
+                         for j in range(70)], np.float32)
+    assert pop == "many"
+    n = 700
+    x1, y1 = rng.uniform(-2, W - 1, n), rng.uniform(-2, H - 1, n)
+    x2, y2 = x1 + rng.uniform(0, W / 2.0, n), y1 + rng.uniform(0, H / 2.0, n)
+    return np.stack([rng.randint(0, B, n), x1 / scale, y1 / scale, x2 / scale, y2 / scale], 1).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=2)
+def inputs(key):
+    """[(data (B,H,W,C), rois (R,5), top_diff (R,PH,PW,C))] of views A, B, C"""
+    pop, PH, PW, scale, Cc = key
+    out = []
+    for v, (B, H, W) in enumerate(VIEWS):
+        rng = np.random.RandomState(_seed(key, v))
+        data = rng.uniform(-1, 1, (B, H, W, Cc)).astype(np.float32)
+        rois = population(pop, rng, B, H, W, scale)
+        top_diff = rng.uniform(-1, 1, (rois.shape[0], PH, PW, Cc)).astype(np.float32)
+        out.append((data, rois, top_diff))
+    return out
+
+
+def _oracle():
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    import oracle
+    oracle.build()
+    return oracle
+
+
+@functools.lru_cache(maxsize=2)
+def own_reference(key):
+    """[(top, argmax, bottom_diff)] per view from the oracle"""
+    o = _oracle()
+    _, PH, PW, scale, _ = key
+    out = []
+    for data, rois, top_diff in inputs(key):
+        top, am = o.roi_pool(data, rois, PH, PW, scale)
+        out.append((top, am, o.roi_pool_grad(data, rois, am, top_diff, PH, PW, scale)))
+    return out
+
+
+@functools.lru_cache(maxsize=2)
+def foreign_reference(key):
+    """[(foreign plane, contributing mask, bottom_diff)] per view: the plane from the mixture, the rest from the reference alone"""
+    o = _oracle()
+    _, PH, PW, scale, Cc = key
+    out = []
+    for v, ((data, rois, top_diff), (_, am, _)) in enumerate(zip(inputs(key), own_reference(key))):
+        B, H, W, _ = data.shape
+        plane = rs.foreign_argmax(np.random.RandomState(_seed(key, 100 + v)), am, rois, H, W, Cc, PH, PW, scale)
+        mask = rs.contributing(plane, rois, B, H, W, PH, PW, scale)
+        out.append((plane, mask, o.roi_pool_grad(data, rois, plane, top_diff, PH, PW, scale)))
+    return out
+
+
+def shares(key):
+    """(records with a value in [0, H*W*C), those of them that contribute) over the case's three views"""
+    legal = hit = 0
+    for (data, _, _), (plane, mask, _) in zip(inputs(key), foreign_reference(key)):
+        ok = (plane >= 0) & (plane < data.shape[1] * data.shape[2] * data.shape[3])
+        assert not (mask & ~ok).any()                       # a record outside the frame never contributes
+        legal += int(ok.sum())
+        hit += int(mask.sum())
+    return legal, hit
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+
+
+def _forward_restated(data, rois, PH, PW, scale):
+    """roipool_restatement.forward; a ROI's bins depend on its row alone, so repeated rows (stack) are pooled once"""
+    uniq, inv = np.unique(rois, axis=0, return_inverse=True)
+    top, am = rs.forward(data, uniq, PH, PW, scale)
+    return top[inv.reshape(-1)], am[inv.reshape(-1)]
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU half
+def test_table_covers_every_body_and_pooled_size():
+    have = {(c.body, c.pooled, c.pop) for c in CASES}
+    for body in BODIES:
+        sizes = POOLED_ALL + (POOLED_BIG if body in ("sliced", "generic") else [])
+        for pooled in sizes:
+            assert (body, pooled, "edges") in have, (body, pooled)
+        for pooled in POOLED_HEAVY:
+            assert (body, pooled, "stack") in have and (body, pooled, "cover") in have, (body, pooled)
+        for pooled in POOLED_MANY:
+            assert (body, pooled, "many") in have, (body, pooled)
+        assert {c.scale for c in CASES if c.body == body} == set(SCALES), body
+    assert ("generic", POOLED_OVER, "edges") in have
+    want = {"generic": {(6, False), (20, False), (324, False), (320, False), (64, False)},
+            "sliced": {(64, False), (1024, False), (192, True), (64, True)},
+            "indexed": {(64, True), (128, True), (256, True), (512, True)},
+            "tiles": {(256, False), (512, False)}}
+    for body in BODIES:
+        assert {(c.C, c.ws) for c in CASES if c.body == body} == want[body], body
+    assert any(c.body == "generic" and c.C == 64 and c.pooled == POOLED_OVER for c in CASES)
+    assert any(c.body == "sliced" and c.C == 64 and c.ws and c.pooled == (16, 16) for c in CASES)
+    assert len({c.id for c in CASES}) == len(CASES)
+    assert population("stack", None, 2, 10, 19, 0.125).shape[0] > 512 and population("many", np.random.RandomState(0), 2, 10, 19, 0.5).shape[0] == 700
+
+
+@pytest.fixture(scope="module")
+def hiplib():
+    from mv3d_tf_amd import build
+    build.build()
+    from mv3d_tf_amd import _lib
+    return _lib
+
+
+def grad_view_array(hiplib, views, ptrs=None):
+    """RoiGradView array of [(B, H, W, C, R, scale)]; ptrs[k] = (bottom_diff, rois, top_diff, argmax) or NULL everywhere"""
+    arr = (hiplib.RoiGradView * len(views))()
+    for k, (B, H, W, Cc, R, scale) in enumerate(views):
+        p = ptrs[k] if ptrs else (None, None, None, None)
+        arr[k] = hiplib.RoiGradView(p[0], p[1], p[2], p[3], float(scale), B, R, H, W, Cc)
+    return arr
+
+
+@functools.lru_cache(maxsize=None)
+def rows_of(pop):
+    return population(pop, np.random.RandomState(0), 2, 10, 19, 0.125).shape[0]       # (the same for every view)
+
+
+def case_shapes(case):
+    v = [(B, H, W, case.C, rows_of(case.pop), case.scale) for B, H, W in VIEWS]
+    if case.body != "tiles":
+        v.append(EMPTY_VIEW + (case.C, 0, case.scale))
+    return v
+
+
+def path_of(hiplib, views, pooled, ws, pair, ptrs=None):
+    r = hiplib.lib().mv3d_roi_pool_backward_path(len(views), grad_view_array(hiplib, views, ptrs), pooled[0], pooled[1], int(ws), int(pair))
+    return r.decode() if r is not None else None
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.id)
+def test_path_names_the_intended_body(hiplib, case):
+    views = case_shapes(case)
+    assert path_of(hiplib, views, case.pooled, case.ws, case.body == "tiles") == case.body
+    for k, v in enumerate(views[:3]):                        # each view alone takes the same body
+        assert path_of(hiplib, [v], case.pooled, case.ws, case.body == "tiles") == case.body, k
+
+
+def test_path_around_each_boundary(hiplib):
+    one = lambda Cc, pooled, ws=False, pair=False, B=1, H=10, W=19, R=5: path_of(hiplib, [(B, H, W, Cc, R, 0.125)], pooled, ws, pair)  # noqa: E731
+    assert one(64, (7, 7)) == "sliced" and one(65, (7, 7)) == "generic" and one(128, (7, 7)) == "sliced"
+    assert one(64, (7, 7), ws=True) == "indexed" and one(192, (7, 7), ws=True) == "sliced" and one(1024, (7, 7), ws=True) == "sliced"
+    assert one(64, (15, 15), ws=True) == "indexed" and one(64, (16, 16), ws=True) == "sliced"
+    assert one(64, (15, 16), ws=True) == "sliced" and one(64, (16, 15), ws=True) == "sliced"
+    assert one(256, (15, 15), pair=True) == "tiles" and one(256, (16, 16), pair=True) == "sliced"
+    assert one(256, (16, 16), ws=True, pair=True) == "sliced"
+    assert one(64, (22, 23)) == "sliced" and one(64, (23, 23)) == "generic" and one(64, (23, 22)) == "sliced"
+    assert one(64, (7, 7), pair=True) == "sliced" and one(128, (7, 7), ws=True, pair=True) == "indexed"
+    assert one(512, (7, 7), pair=True) == "tiles" and one(1024, (7, 7), pair=True) == "sliced"
+    # an empty view in a pair call: the plain bodies
+    two = [(2, 10, 19, 256, 5, 0.125), (1, 6, 33, 256, 0, 0.125)]
+    assert path_of(hiplib, two, (7, 7), False, True) == "sliced" and path_of(hiplib, two, (7, 7), True, True) == "indexed"
+    assert path_of(hiplib, two[:1], (7, 7), False, True) == "tiles"
+    assert one(256, (7, 7), pair=True, R=0) == "sliced" and one(256, (7, 7), ws=True, R=0) == "indexed"
+    # the pair's maps: 65534 pixels at the most
+    assert one(256, (7, 7), pair=True, H=2, W=32767) == "tiles" and one(256, (7, 7), pair=True, H=3, W=21845) == "sliced"
+    assert one(256, (7, 7), ws=True, pair=True, H=3, W=21845) == "indexed"
+    # views of different widths: never the index; one generic view makes the call generic
+    mixed = [(2, 10, 19, 256, 5, 0.125), (1, 6, 33, 512, 5, 0.125)]
+    assert path_of(hiplib, mixed, (7, 7), True, True) == "sliced"
+    assert path_of(hiplib, mixed + [(1, 6, 33, 20, 5, 0.125)], (7, 7), True, True) == "generic"
+    # pointer alignment where given: 16 bytes for the index and the tiles
+    A = 4096
+    for ptrs in ((A + 4, A, A, A), (A, A, A + 4, A), (A, A, A, A + 8)):
+        assert path_of(hiplib, [(1, 10, 19, 256, 5, 0.125)], (7, 7), True, True, [ptrs]) == "sliced"
+    assert path_of(hiplib, [(1, 10, 19, 256, 5, 0.125)], (7, 7), True, True, [(A, A + 4, A, A)]) == "tiles"      # (ROI rows are 20 bytes)
+    # refused shapes
+    assert one(0, (7, 7)) is None and one(64, (0, 7)) is None and one(64, (7, 7), B=0) is None and one(64, (7, 7), R=-1) is None
+    assert path_of(hiplib, [], (7, 7), False, False) is None and path_of(hiplib, [(1, 4, 4, 64, 1, 0.125)] * 5, (7, 7), False, False) is None
+    assert one(1023, (7, 7)) == "generic" and one(1025, (7, 7)) is None          # scalar loads: C <= 1024
+    assert one(4092, (7, 7)) == "generic" and one(4100, (7, 7)) is None          # vector loads: C <= 4096
+    assert path_of(hiplib, [(1, 10, 19, 4092, 5, 0.125)], (7, 7), False, False, [(A, A, A + 4, A)]) is None      # (unaligned: scalar loads)
+    assert one(64, (7, 7), H=40000, W=40000) is None                               # H * W * C beyond an int
+    assert one(64, (15, 15), R=10 ** 7) is None                                     # R * PH * PW beyond an int
+
+
+@pytest.mark.parametrize("key", KEYS, ids=lambda k: "%s-%dx%d-s%.4f-C%d" % k)
+def test_restatements_agree_on_every_case(key):
+    """oracle (from the CPU op) == roipool_restatement (from the CUDA kernels), bit for bit: top, argmax, and bottom_diff on the
+    forward's own plane and -- for the keys of the plain bodies -- on the foreign plane, whose shares must hold: of the records
+    with a value in [0, H*W*C) at least 10 % contribute and at least 10 % do not.  Measured contributing shares (run with -s):
+    edges 65 % at 1 x 1, 36 % at 2 x 2, 37 - 40 % at 15 x 1, 30 % at 1 x 15, 22 - 27 % from 3 x 5 to 23 x 23; stack 76 % at every
+    size; cover 88 % at 1 x 1, 22 % at 7 x 7, 20 % at 8 x 8, 17 - 18 % from 15 x 15 to 23 x 23; many 25 % at 7 x 7, 23 % at 15 x 15"""
+    _, PH, PW, scale, _ = key
+    for v, ((data, rois, top_diff), (top, am, bd)) in enumerate(zip(inputs(key), own_reference(key))):
+        B, H, W, _ = data.shape
+        r_top, r_am = _forward_restated(data, rois, PH, PW, scale)
+        assert same_bits(top, r_top) and np.array_equal(am, r_am), v
+        assert same_bits(bd, rs.backward(top_diff, am, rois, B, H, W, PH, PW, scale)), v
+        if key in FOREIGN_KEYS:
+            plane, _, f_bd = foreign_reference(key)[v]
+            assert same_bits(f_bd, rs.backward(top_diff, plane, rois, B, H, W, PH, PW, scale)), v
+    if key in FOREIGN_KEYS:
+        legal, hit = shares(key)
+        print("foreign shares %s: %d records in [0, HWC), %.1f %% contribute" % (key, legal, 100.0 * hit / legal))
+        assert hit >= 0.10 * legal and legal - hit >= 0.10 * legal, (legal, hit)
+
+
+def test_widened_candidate_set_is_invisible_on_the_own_plane_only():
+    """the reason for foreign planes: a backward whose candidate ranges are one bin too wide on each side equals the reference on
+    the plane its forward wrote, and differs from it on a foreign one (view A of the 7 x 7 `edges` case)"""
+    case = next(c for c in CASES if c.pooled == (7, 7) and c.pop == "edges" and c.body == "generic")
+    data, rois, top_diff = inputs(case.key)[0]
+    _, am, bd = own_reference(case.key)[0]
+    plane, _, f_bd = foreign_reference(case.key)[0]
+    B, H, W, _ = data.shape
+    assert same_bits(bd, rs.backward(top_diff, am, rois, B, H, W, 7, 7, case.scale, widen=1))
+    wide = rs.backward(top_diff, plane, rois, B, H, W, 7, 7, case.scale, widen=1)
+    assert int((bits(wide) != bits(f_bd)).sum()) > 0.05 * f_bd.size
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU half
+NAN_BITS = 0x7fc00000
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    from mv3d_tf_amd import build, ops
+    build.build()
+    return torch, ops
+
+
+def dev(torch, a):
+    return torch.as_tensor(np.ascontiguousarray(a)).cuda()
+
+
+def nan_like(torch, shape, dtype=None):
+    """an output buffer no launch has written: f32 NaN (int32: the same bits)"""
+    if dtype == torch.int32:
+        return torch.full(tuple(shape), NAN_BITS, dtype=torch.int32, device="cuda")
+    return torch.full(tuple(shape), float("nan"), dtype=torch.float32, device="cuda")
+
+
+def host_bits(t):
+    return t.cpu().numpy().view(np.int32)
+
+
+class Device:
+    """a case's inputs on the device: the three views, plus the R = 0 view for the plain bodies"""
+
+    def __init__(self, torch, hiplib, case):
+        self.case = case
+        self.host = inputs(case.key)
+        self.data = [dev(torch, d) for d, _, _ in self.host]
+        self.rois = [dev(torch, r) for _, r, _ in self.host]
+        self.top_diff = [dev(torch, t) for _, _, t in self.host]
+        self.shapes = [d.shape for d, _, _ in self.host]
+        self.empty = None
+        if case.body != "tiles":
+            self.empty_shape = EMPTY_VIEW + (case.C,)
+            self.empty = (torch.empty((0, case.pooled[0], case.pooled[1], case.C), device="cuda"), torch.empty((0, 5), device="cuda"),
+                          torch.empty((0, case.pooled[0], case.pooled[1], case.C), dtype=torch.int32, device="cuda"))
+        self.ws = False
+        if case.ws:                                          # the workspace needs no initialisation: random bytes
+            n = hiplib.lib().mv3d_roi_pool_backward_workspace_bytes(len(case_shapes(case)), grad_view_array(hiplib, case_shapes(case)),
+                                                                     case.pooled[0], case.pooled[1])
+            self.ws = torch.randint(0, 256, (n,), dtype=torch.uint8, device="cuda")
+
+    def backward(self, torch, ops, top_diffs, planes, which=(0, 1, 2), with_empty=True):
+        """RoiPoolGrad of the views `which` behind ONE call of the case's body, into NaN-filled buffers; returns their bottom_diffs"""
+        PH, PW = self.case.pooled
+        views = [(top_diffs[k], self.rois[k], planes[k], self.shapes[k], self.case.scale) for k in which]
+        outs = [nan_like(torch, self.shapes[k]) for k in which]
+        if self.case.body == "tiles":
+            return ops.roi_pool_backward_views_pair(views, PH, PW, outs=outs)
+        ws = self.ws                                         # (sized for all four views: serves fewer as well)
+        if with_empty:
+            views.append((self.empty[0], self.empty[1], self.empty[2], self.empty_shape, self.case.scale))
+            outs.append(nan_like(torch, self.empty_shape))
+        got = ops.roi_pool_backward_views(views, PH, PW, outs=outs, workspace=ws)
+        if with_empty:
+            assert not host_bits(got[-1]).any(), "the R = 0 view must come back all +0.0"
+            got = got[:-1]
+        return got
+
+
+@pytest.fixture(scope="module", params=CASES, ids=lambda c: c.id)
+def state(request, gpu, hiplib):
+    torch, _ = gpu
+    return Device(torch, hiplib, request.param)
+
+
+@pytest.fixture(scope="module", params=PLAIN, ids=lambda c: c.id)
+def plain_state(request, gpu, hiplib):
+    """the cases of the bodies that read an int32 plane (the pair reads its own forward's codes only)"""
+    torch, _ = gpu
+    return Device(torch, hiplib, request.param)
+
+
+def _forward_single(torch, hiplib, data, rois, PH, PW, scale):
+    """mv3d_roi_pool_forward into NaN-filled buffers"""
+    B, H, W, Cc = data.shape
+    R = rois.shape[0]
+    top, am = nan_like(torch, (R, PH, PW, Cc)), nan_like(torch, (R, PH, PW, Cc), torch.int32)
+    rc = hiplib.lib().mv3d_roi_pool_forward(data.data_ptr(), C.c_float(scale), B, R, H, W, Cc, PH, PW, rois.data_ptr(), top.data_ptr(),
+                                            am.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    assert rc == 0
+    return top, am
+
+
+@pytest.mark.gpu
+def test_forward(gpu, hiplib, state):
+    """top and argmax of every view equal the oracle's bits: all views in one call and the single-view entry (plain bodies'
+    cases), the pair's forward + decode (tiles cases)"""
+    torch, ops = gpu
+    case = state.case
+    PH, PW = case.pooled
+    want = own_reference(case.key)
+    fv = [(state.data[k], state.rois[k], case.scale) for k in range(3)]
+    outs = [(nan_like(torch, w[0].shape), nan_like(torch, w[0].shape, torch.int32)) for w in want]
+    if case.body == "tiles":
+        res = ops.roi_pool_forward_views_pair(fv, PH, PW, outs=outs)
+        dec = ops.roi_pool_argmax_decode(fv, res, PH, PW)
+        got = [(top, am) for (top, _), am in zip(res, dec)]
+    else:
+        empty = (nan_like(torch, state.empty_shape), state.empty[1], case.scale)
+        e_out = (torch.empty((0, PH, PW, case.C), device="cuda"), torch.empty((0, PH, PW, case.C), dtype=torch.int32, device="cuda"))
+        got = ops.roi_pool_forward_views(fv + [empty], PH, PW, outs=outs + [e_out])[:3]
+    for k, ((top, am), (o_top, o_am, _)) in enumerate(zip(got, want)):
+        assert np.array_equal(host_bits(top), bits(o_top)) and np.array_equal(am.cpu().numpy(), o_am), k
+    if case.body != "tiles":
+        for k, (o_top, o_am, _) in enumerate(want):
+            top, am = _forward_single(torch, hiplib, state.data[k], state.rois[k], PH, PW, case.scale)
+            assert np.array_equal(host_bits(top), bits(o_top)) and np.array_equal(am.cpu().numpy(), o_am), k
+
+
+def _own_planes(torch, ops, state):
+    """the argmax planes the case's backward reads: the oracle's int32 planes, or for the pair what its forward wrote"""
+    case = state.case
+    if case.body != "tiles":
+        return [dev(torch, am) for _, am, _ in own_reference(case.key)]
+    fv = [(state.data[k], state.rois[k], case.scale) for k in range(3)]
+    return [am for _, am in ops.roi_pool_forward_views_pair(fv, case.pooled[0], case.pooled[1])]
+
+
+@pytest.mark.gpu
+def test_backward_own_plane(gpu, state):
+    """bottom_diff equals oracle.roi_pool_grad bit for bit, all views behind one call and each view alone; at the widths the
+    sliced, indexed and tiles bodies share, the other bodies give the same bits"""
+    torch, ops = gpu
+    case = state.case
+    PH, PW = case.pooled
+    want = own_reference(case.key)
+    planes = _own_planes(torch, ops, state)
+    got = state.backward(torch, ops, state.top_diff, planes)
+    for k in range(3):
+        assert np.array_equal(host_bits(got[k]), bits(want[k][2])), k
+    for k in range(3):                                       # each view alone
+        if case.body == "tiles":
+            fv = [(state.data[k], state.rois[k], case.scale)]
+            (_, am), = ops.roi_pool_forward_views_pair(fv, PH, PW)
+            alone, = ops.roi_pool_backward_views_pair([(state.top_diff[k], state.rois[k], am, state.shapes[k], case.scale)], PH, PW,
+                                                      outs=[nan_like(torch, state.shapes[k])])
+        else:
+            alone, = state.backward(torch, ops, state.top_diff, planes, which=(k,), with_empty=False)
+        assert torch.equal(alone.view(torch.int32), got[k].view(torch.int32)), k
+        if case.body in ("generic", "sliced"):               # the single-view entry (no workspace)
+            one = ops.roi_pool_backward(state.top_diff[k], state.rois[k], planes[k], state.shapes[k], PH, PW, case.scale)
+            if not case.ws:
+                assert torch.equal(one.view(torch.int32), got[k].view(torch.int32)), k
+    if case.body == "tiles":                                 # the same call through the sliced and the indexed body
+        plain = [(state.top_diff[k], state.rois[k], dev(torch, want[k][1]), state.shapes[k], case.scale) for k in range(3)]
+        sliced = ops.roi_pool_backward_views(plain, PH, PW, outs=[nan_like(torch, s) for s in state.shapes], workspace=False)
+        indexed = ops.roi_pool_backward_views(plain, PH, PW, outs=[nan_like(torch, s) for s in state.shapes])
+        for k in range(3):
+            assert torch.equal(sliced[k].view(torch.int32), got[k].view(torch.int32)), k
+            assert torch.equal(indexed[k].view(torch.int32), got[k].view(torch.int32)), k
+
+
+@pytest.mark.gpu
+def test_backward_foreign_plane_and_poisoned_top_diff(gpu, plain_state):
+    """generic, sliced and indexed on a plane no forward wrote: bottom_diff equals the oracle's bits; and with every record that
+    does not contribute set to NaN, +Inf, -Inf in turn, bottom_diff keeps those bits (a select, never a multiply)"""
+    torch, ops = gpu
+    state = plain_state
+    case = state.case
+    ref = foreign_reference(case.key)
+    planes = [dev(torch, plane) for plane, _, _ in ref]
+    got = state.backward(torch, ops, state.top_diff, planes)
+    for k in range(3):
+        assert np.array_equal(host_bits(got[k]), bits(ref[k][2])), k
+    masks = [dev(torch, mask) for _, mask, _ in ref]
+    for poison in (float("nan"), float("inf"), float("-inf")):
+        bad = [torch.where(m, t, torch.full_like(t, poison)) for m, t in zip(masks, state.top_diff)]
+        again = state.backward(torch, ops, bad, planes)
+        for k in range(3):
+            assert torch.equal(again[k].view(torch.int32), got[k].view(torch.int32)), (poison, k)
+
+
+ORDER_CASES = [("sliced", 64, False), ("indexed", 128, True), ("tiles", 256, False)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("body,Cc,ws", ORDER_CASES, ids=[b for b, _, _ in ORDER_CASES])
+def test_view_order_and_density(gpu, hiplib, oracle, body, Cc, ws):
+    """views of very different ROI density (bwd_order and mv3d_rgt_layout sort by it) behind one call, in both orders: every view
+    gets the bits of that view alone, which are the oracle's"""
+    torch, ops = gpu
+    PH, PW, scale = 7, 7, 0.125
+    pops = ["edges", "stack", "cover"]                       # ~0.15, ~3 and ~4.7 ROIs per pixel in views A, B, C
+    host, want = [], []
+    for v, ((B, H, W), pop) in enumerate(zip(VIEWS, pops)):
+        rng = np.random.RandomState(4000 + 10 * Cc + v)
+        data = rng.uniform(-1, 1, (B, H, W, Cc)).astype(np.float32)
+        rois = population(pop, rng, B, H, W, scale)
+        top_diff = rng.uniform(-1, 1, (rois.shape[0], PH, PW, Cc)).astype(np.float32)
+        _, am = oracle.roi_pool(data, rois, PH, PW, scale)
+        host.append((data, rois, top_diff, am))
+        want.append(oracle.roi_pool_grad(data, rois, am, top_diff, PH, PW, scale))
+    d = [tuple(dev(torch, a) for a in h) for h in host]
+    shapes = [(B, H, W, Cc, h[1].shape[0], scale) for (B, H, W), h in zip(VIEWS, host)]
+    assert path_of(hiplib, shapes, (PH, PW), ws, body == "tiles") == body
+
+    def run(order):
+        outs = [nan_like(torch, d[k][0].shape) for k in order]
+        if body == "tiles":
+            res = ops.roi_pool_forward_views_pair([(d[k][0], d[k][1], scale) for k in order], PH, PW)
+            return ops.roi_pool_backward_views_pair([(d[k][2], d[k][1], am, d[k][0].shape, scale) for k, (_, am) in zip(order, res)],
+                                                    PH, PW, outs=outs)
+        return ops.roi_pool_backward_views([(d[k][2], d[k][1], d[k][3], d[k][0].shape, scale) for k in order], PH, PW, outs=outs,
+                                           workspace=None if ws else False)
+    for order in ((0, 1, 2), (2, 1, 0), (1,), (0,), (2,)):
+        for k, got in zip(order, run(order)):
+            assert np.array_equal(host_bits(got), bits(want[k])), (order, k)
