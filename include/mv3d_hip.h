@@ -549,6 +549,43 @@ int mv3d_point_cloud_2_top_paper_shape(double res, double zres, double side_lo, 
                                        double height_lo, double height_hi, int *dims);
 int mv3d_bev_density_table(float *out64);
 
+/* ------------------------------------------------------------------ crop to the camera image (csrc/scan_crop.hip)
+ * "We also remove points that are out of the image boundaries when projected to the image plane" (the MV3D paper, section 3.4), in
+ * front of the rasterisers above: a stable compaction of `num_frames` clouds back to back into another such batch.  PARITY UNPINNED:
+ * the reference has no such code; tests/scan_crop_restatement.py states the rule.
+ *   points_dev      (total_points, 4) f32 [x, y, z, reflectance], the frames' clouds concatenated, 16-byte aligned; never written
+ *   offsets_dev     (num_frames + 1) int32 ON THE DEVICE, mv3d_point_cloud_2_front's rule: frame b owns rows offsets[b] .. offsets[b + 1];
+ *                   rows no frame owns -- in front of offsets[0], behind offsets[num_frames], anything under offsets that do not
+ *                   ascend -- are dropped.  NULL with num_frames == 1: the one frame owns every row.
+ *   calib_dev       (num_frames, 48) f32: per frame the (4, 12) calibration table of the feeds (P2, P3, R0_rect, Tr_velo_to_cam)
+ *   image_hw_dev    (num_frames, 2) int32: per frame the height and the width of its image
+ *   points_out_dev  (total_points, 4) f32, 16-byte aligned, no byte in common with points_dev: the kept rows of frame 0 from row 0 on
+ *                   and the frames behind it back to back, each frame's rows in their order, every row copied as 16 bytes bit for bit
+ *                   (a NaN reflectance keeps its payload); the rows at and behind offsets_out[num_frames] are not written
+ *   offsets_out_dev (num_frames + 1) int32: offsets_out[b] = the kept rows of the frames < b, so offsets_out[0] = 0 --
+ *                   (points_out_dev, offsets_out_dev) is a batch like (points_dev, offsets_dev)
+ *   workspace_dev   workspace_bytes >= mv3d_scan_crop_workspace(total_points) bytes, 16-byte aligned, the caller's; it needs no
+ *                   initialisation and holds nothing between calls
+ * Kept: a row of frame b whose x, y, z are finite and for which, with M = (P2 . R0) . Tr of the frame's table in f32 (the matrix
+ * mv3d_proposal_3d projects with, tests/golden/proj_matrix.npz) and v[r] = fma(M[r][3], 1, fma(M[r][2], z, fma(M[r][1], y,
+ * fma(M[r][0], x, 0)))) in f64 (homogeneous w = 1, a position): v[2] > 0 and, u = v[0] / v[2], w = v[1] / v[2] in f64,
+ * 0 <= u < width and 0 <= w < height.  No margin, no minimum depth; a frame whose height or width is <= 0 keeps nothing; the
+ * reflectance is never examined.
+ * No value in offsets_dev, calib_dev or image_hw_dev can make the call read or write out of bounds.  Three launches on `stream`
+ * whatever the batch (flags, scan, copy; the scan alone with total_points == 0, which writes offsets_out = 0), none of whose workgroups
+ * waits for another; no allocation, no host synchronisation; capturable, and a replay may find other clouds and other device
+ * offsets in the same buffers (total_points, the capacity, fixes the grid).  num_frames == 0 returns MV3D_OK without a launch.
+ * MV3D_ERR_INVALID_ARG before any launch: num_frames outside [0, MV3D_FV_MAX_FRAMES], negative total_points, NULL or misaligned
+ * pointers (points, output and workspace may be NULL with total_points == 0), offsets_dev == NULL with num_frames != 1, a workspace
+ * that is too small, points_out_dev overlapping points_dev.
+ * mv3d_scan_crop_workspace: bytes for total_points rows (one bit per row and 4 bytes per tile, each part rounded up to 256); 0 for
+ * a count <= 0.  mv3d_scan_crop_tile_rows (HOST only): the consecutive rows one workgroup compacts, for the tests' sizes. */
+size_t mv3d_scan_crop_workspace(int total_points);
+int mv3d_scan_crop_tile_rows(void);
+int mv3d_scan_crop_to_image(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
+                            const float *calib_dev, const int32_t *image_hw_dev, float *points_out_dev, int32_t *offsets_out_dev,
+                            void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------ the target layers' random subsamplings (HOST code)
  * The reference subsamples with `npr.choice(inds, size=k, replace=False)` on the numpy GLOBAL legacy RandomState
  * (lib/rpn_msr/anchor_target_layer_tf.py:146-159,178-183; lib/rpn_msr/proposal_target_layer_tf.py:246-269) = 

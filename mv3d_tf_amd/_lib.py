@@ -210,6 +210,9 @@ _SIGS = {
     "mv3d_point_cloud_2_top_paper_workspace": (C.c_size_t, [C.c_int, _P]),
     "mv3d_point_cloud_2_top_paper_shape": (C.c_int, [C.c_double] * 8 + [_P]),
     "mv3d_bev_density_table": (C.c_int, [_P]),
+    "mv3d_scan_crop_workspace": (C.c_size_t, [C.c_int]),
+    "mv3d_scan_crop_tile_rows": (C.c_int, []),
+    "mv3d_scan_crop_to_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_box_detect_tail": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "mv3d_detect_post_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(DetectPostParams)]),
     "mv3d_detect_post": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(DetectPostParams), _P, _P, _P, _P, _P, _P, _P, C.c_size_t,

@@ -219,6 +219,23 @@ __device__ __forceinline__ void image_point(const float M[12], float x, float y,
     px = v[0] / v[2]; py = v[1] / v[2];
 }
 
+// A Velodyne POINT on the image plane: v = M . [x, y, z, 1] in f64, image_point's accumulation order with homogeneous w = 1 (a
+// position, where image_point keeps the reference's w = 0).  The pixel is (v[0] / v[2], v[1] / v[2]) where v[2] > 0: the caller's
+// test (scan_crop.hip).
+__device__ __forceinline__ void scan_image_point(const float *M, float x, float y, float z, double v[3])
+{
+    const double cx = (double)x, cy = (double)y, cz = (double)z;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double acc = 0.0;
+        acc = fma((double)M[r * 4 + 0], cx, acc);
+        acc = fma((double)M[r * 4 + 1], cy, acc);
+        acc = fma((double)M[r * 4 + 2], cz, acc);
+        acc = fma((double)M[r * 4 + 3], 1.0, acc);
+        v[r] = acc;
+    }
+}
+
 __device__ __forceinline__ void group8_minmax(double v, int lane_base, double &mn, double &mx, bool &any_nan)
 {
     any_nan = false;

@@ -102,6 +102,14 @@ cfg.LIDAR_BV_FROM_SCAN = False
 # LIDAR_BV_FROM_SCAN, because stored lidar_bv/*.npy maps are reference-encoded: prepare_roidb and the detection loops raise
 # ValueError otherwise, and for any other value (ops.bev_encoding).
 cfg.LIDAR_BV_ENCODING = 'reference'
+# (not in the reference, whose maps hold every return inside [0, 60] x [-30, 30] m) True: the paper's "we also remove points that are out
+# of the image boundaries when projected to the image plane" (section 3.4): a frame's uploaded scan is compacted on the device to the
+# points the frame's calibration table puts inside its own image (ops.scan_crop_to_image), in front of the
+# bird's-eye-view and front-view rasters of get_minibatch, detect_batch.test_net and rpn_msr.generate.imdb_proposals.  KITTI labels
+# only what the left colour image shows; with the crop the map is empty elsewhere, and RPN_SKIP_EMPTY_ANCHORS then drops those
+# anchors.  Parity unpinned, no accuracy claim.  Needs LIDAR_BV_FROM_SCAN, because stored lidar_bv/*.npy maps hold every point:
+# prepare_roidb and the detection loops raise ValueError otherwise (ops.scan_crop).  False = every blob and code path as before.
+cfg.LIDAR_CROP_TO_IMAGE = False
 # (not in the reference, which subtracts PIXEL_MEANS on the host, frame by frame, and uploads f32) True: `image_data` is built on the
 # device from ONE upload of the frames' uint8 pixels (ops.image_blob) by get_minibatch, detect_batch.test_net
 # and rpn_msr.generate.imdb_proposals; the two loops then group frames by BEV shape only and pad a group's frames to one canvas, the

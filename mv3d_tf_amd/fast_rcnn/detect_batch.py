@@ -114,19 +114,23 @@ def loop_scan_source(net, imdb):
     """(i -> scan or None, maps_from_scans) for a detection loop: a three-view network needs the scans for `lidar_fv_data`,
     cfg.LIDAR_BV_FROM_SCAN for `lidar_bv_data` of any network; None when neither asks"""
     ops.bev_encoding()                                      # 'paper' without LIDAR_BV_FROM_SCAN, or an unknown value: ValueError here
+    ops.scan_crop()                                         # cfg.LIDAR_CROP_TO_IMAGE without LIDAR_BV_FROM_SCAN: ValueError here
     from_scan = bool(cfg.LIDAR_BV_FROM_SCAN)
     points_of = front_view_source(net, imdb)
     return (scan_source(imdb, "cfg.LIDAR_BV_FROM_SCAN") if points_of is None and from_scan else points_of), from_scan
 
 
-def scan_feed(clouds, bev, fv):
+def scan_feed(clouds, bev, fv, calibs=None, image_shapes=None):
     """the feed entries a group of frames gets from its scans: the clouds are concatenated and uploaded ONCE, and `lidar_bv_data`
     (bev true: one ops.scan_bev call, the raster cfg.LIDAR_BV_ENCODING names) and `lidar_fv_data` (fv true: one ops.point_cloud_2_front call) are rasterised
-    from that one device tensor"""
+    from that one device tensor.  Under cfg.LIDAR_CROP_TO_IMAGE that tensor is first cropped ONCE (ops.scan_crop_to_image) to the points
+    each frame's table of `calibs` puts inside its own image, `image_shapes` = the frames' (h, w, ...), and both rasters read the crop."""
     feed = {}
     if bev or fv:
         pts = ops._dev(np.concatenate(clouds, 0))
         offsets = np.cumsum([0] + [len(c) for c in clouds])
+        if ops.scan_crop():
+            pts, offsets = ops.scan_crop_to_image(pts, offsets, calibs, image_shapes)
         if bev:
             feed["lidar_bv_data"] = ops.scan_bev(pts, offsets=offsets)
         if fv:
@@ -218,12 +222,13 @@ def iter_loaded_groups(imdb, points_of, from_scan, batch_size):
 def group_feed(net, ims, bvs, calibs, clouds, from_scan):
     """the feed of one group of frames: `image_data` from `image_feed` (cfg.IMAGE_BLOB_ON_DEVICE) or `host_image_blob`, `lidar_bv_data`
     stacked from the stored maps or, under from_scan, rasterised with a three-view network's `lidar_fv_data` by `scan_feed` (the
-    group's scans back to back: one upload, one call per view), `calib`, and `im_info` = the BEV size, scale 1, per frame"""
+    group's scans back to back: one upload, one call per view; under cfg.LIDAR_CROP_TO_IMAGE cropped with the group's tables and the
+    frames' OWN image shapes, not the padded canvas), `calib`, and `im_info` = the BEV size, scale 1, per frame"""
     feed = {"image_data": image_feed(ims) if cfg.IMAGE_BLOB_ON_DEVICE else host_image_blob(ims),
             "calib": np.stack([np.asarray(c, np.float32).reshape(4, 12) for c in calibs]), "keep_prob": 1.0}
     if not from_scan:
         feed["lidar_bv_data"] = np.stack([np.asarray(bv, np.float32) for bv in bvs])
-    feed.update(scan_feed(clouds, from_scan, getattr(net, "views", 2) == 3))
+    feed.update(scan_feed(clouds, from_scan, getattr(net, "views", 2) == 3, calibs, [np.shape(im) for im in ims]))
     feed["im_info"] = np.array([[feed["lidar_bv_data"].shape[1], feed["lidar_bv_data"].shape[2], 1]] * len(ims), dtype=np.float32)
     return feed
 

@@ -649,15 +649,17 @@ def point_cloud_2_front_workspace_bytes(num_frames=1):
     return int(lib().mv3d_point_cloud_2_front_workspace(int(num_frames)))
 
 
-def _scan_args(fn, points, offsets, frame, out, workspace=None, workspace_bytes=None, frame_rows=None):
+def _scan_args(fn, points, offsets, frame, out, workspace=None, workspace_bytes=None, frame_rows=None, more=None):
     """The argument checks and uploads that the rasterisers of B clouds back to back share (point_cloud_2_front,
     point_cloud_2_top_batch; `fn` is the name the messages carry): points (P,4) f32, a device tensor or a numpy array; offsets None
     (one frame) or (B + 1) int32, whose VALUES are checked only when they come from the host (ascending within [0, P], at most
     `frame_rows` rows a frame where that is given); every tensor on one HIP device; out (optional) a contiguous f32 tensor of the
     result's shape; workspace (optional) contiguous uint8 of at least workspace_bytes(B) bytes.  `frame` is the shape of one frame
     of the result, or a function that gives it, called once the points have passed (the caller's own checks keep their place among
-    these).  TypeError for a wrong dtype, ValueError for a wrong shape, value or device, all before anything is uploaded or
-    allocated.  -> (points on the device, offsets on the device or None, B, P, out, device)"""
+    these); None = the call has no such `out` (scan_crop_to_image, whose result is a batch of clouds).  more (optional) = the caller's
+    checks of its further arguments, called as more(B, P, device) once all of these have passed.  TypeError for a wrong dtype,
+    ValueError for a wrong shape, value or device, all before anything is uploaded or allocated.
+    -> (points on the device, offsets on the device or None, B, P, out, device)"""
     if isinstance(points, torch.Tensor):
         if points.dtype != torch.float32:
             raise TypeError("{}: points must be float32, got {}".format(fn, points.dtype))
@@ -687,10 +689,10 @@ def _scan_args(fn, points, offsets, frame, out, workspace=None, workspace_bytes=
                 raise ValueError("{}: a frame holds at most {} rows".format(fn, frame_rows))
         if offsets.ndim != 1 or not 2 <= offsets.shape[0] <= FV_MAX_FRAMES + 1:
             raise ValueError("{}: offsets must be (B + 1,) with 1 <= B <= {}, got {}".format(fn, FV_MAX_FRAMES, tuple(offsets.shape)))
-        shape = (int(offsets.shape[0]) - 1,) + frame
+        shape = None if frame is None else (int(offsets.shape[0]) - 1,) + frame
     elif frame_rows is not None and P > frame_rows:
         raise ValueError("{}: a frame holds at most {} rows".format(fn, frame_rows))
-    B = 1 if offsets is None else shape[0]
+    B = 1 if offsets is None else int(offsets.shape[0]) - 1
     for name, t, dtype in (("out", out, torch.float32), ("workspace", workspace, torch.uint8)):
         if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dtype):
             raise TypeError("{}: {} must be a {} tensor".format(fn, name, dtype))
@@ -706,11 +708,13 @@ def _scan_args(fn, points, offsets, frame, out, workspace=None, workspace_bytes=
         raise ValueError("{}: out must be {}, got {}".format(fn, shape, tuple(out.shape)))
     if workspace is not None and workspace.numel() < workspace_bytes(B):
         raise ValueError("{}: workspace of {} bytes, {} needed".format(fn, workspace.numel(), workspace_bytes(B)))
+    if more is not None:
+        more(B, P, dev)
     pts = points.contiguous() if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points)).to(dev)
     off = None                                                # (one frame: the entries take NULL offsets, nothing to upload)
     if offsets is not None:
         off = offsets.contiguous() if isinstance(offsets, torch.Tensor) else torch.from_numpy(offsets.astype(np.int32)).to(dev)
-    if out is None:
+    if out is None and shape is not None:
         out = torch.empty(shape, dtype=torch.float32, device=dev)
     return pts, off, B, P, out, dev
 
@@ -854,6 +858,114 @@ def scan_bev(points, offsets=None):
     """The network's `lidar_bv_data` from scans on the device, for every feed (get_minibatch, detect_batch.scan_feed): the raster
     cfg.LIDAR_BV_ENCODING names, on MV3D's ranges -- ops.point_cloud_2_top_batch ('reference') or ops.point_cloud_2_top_paper."""
     return (point_cloud_2_top_paper if bev_encoding() == "paper" else point_cloud_2_top_batch)(points, offsets=offsets)
+
+
+def scan_crop():
+    """cfg.LIDAR_CROP_TO_IMAGE checked: True where the feeds crop their scans to the image (scan_crop_to_image); on without
+    cfg.LIDAR_BV_FROM_SCAN raises ValueError (stored lidar_bv/*.npy maps hold every point and cannot be cropped).  prepare_roidb and
+    the detection loops call it before they load a frame."""
+    from .fast_rcnn.config import cfg
+    on = bool(cfg.LIDAR_CROP_TO_IMAGE)
+    if on and not cfg.LIDAR_BV_FROM_SCAN:
+        raise ValueError("cfg.LIDAR_CROP_TO_IMAGE needs cfg.LIDAR_BV_FROM_SCAN: stored bird's-eye-view maps hold every point and cannot be cropped")
+    return on
+
+
+def scan_crop_workspace_bytes(total_points):
+    """bytes of workspace ops.scan_crop_to_image needs for a batch of total_points rows: one bit per row and 4 bytes per tile"""
+    return int(lib().mv3d_scan_crop_workspace(int(total_points)))
+
+
+def scan_crop_tile_rows():
+    """the consecutive rows one workgroup of the crop compacts (mv3d_scan_crop_tile_rows, host only): the sizes its tests are built on"""
+    return int(lib().mv3d_scan_crop_tile_rows())
+
+
+def _crop_tables(fn, calib, image_hw, B):
+    """calib -> (B,48) f32, image_hw -> (B,2) int32, each a device tensor that passed or a host array to upload; raises as
+    scan_crop_to_image says"""
+    if isinstance(calib, torch.Tensor):
+        if calib.dtype != torch.float32:
+            raise TypeError("{}: a calib tensor must be float32, got {}".format(fn, calib.dtype))
+    else:
+        calib = np.asarray(calib)
+        if calib.dtype.kind != "f":
+            raise TypeError("{}: calib must be floating point, got {}".format(fn, calib.dtype))
+        calib = np.ascontiguousarray(calib, np.float32)          # (the feeds' cast of a frame's table)
+    if tuple(calib.shape) not in ((B, 4, 12), (B, 48)):
+        raise ValueError("{}: calib must be ({}, 4, 12) or ({}, 48), one table per frame, got {}".format(fn, B, B, tuple(calib.shape)))
+    if isinstance(image_hw, torch.Tensor):
+        if image_hw.dtype != torch.int32:
+            raise TypeError("{}: an image_hw tensor must be int32, got {}".format(fn, image_hw.dtype))
+        if tuple(image_hw.shape) != (B, 2):
+            raise ValueError("{}: image_hw must be ({}, 2) [height, width], got {}".format(fn, B, tuple(image_hw.shape)))
+    else:
+        image_hw = np.asarray(image_hw)
+        if not np.issubdtype(image_hw.dtype, np.integer):
+            raise TypeError("{}: image_hw must be integers, got {}".format(fn, image_hw.dtype))
+        if image_hw.ndim != 2 or image_hw.shape[0] != B or image_hw.shape[1] not in (2, 3):
+            raise ValueError("{}: image_hw must be ({}, 2) [height, width] or the frames' image shapes, got {}".format(fn, B, image_hw.shape))
+        if image_hw.size and (image_hw.min() < -2 ** 31 or image_hw.max() >= 2 ** 31):
+            raise ValueError("{}: image_hw does not fit int32".format(fn))
+        image_hw = np.ascontiguousarray(image_hw[:, :2], np.int32)
+    return calib.reshape(B, 48), image_hw
+
+
+def scan_crop_to_image(points, offsets, calib, image_hw, out=None, offsets_out=None, workspace=None):
+    """The paper's crop to the camera image (csrc/scan_crop.hip; parity unpinned, the definition is
+    tests/scan_crop_restatement.py): B clouds back to back -> (points_out, offsets_out), the batch of the rows whose projection by
+    their frame's calibration table falls inside their frame's image, frames and rows in their order, every kept row bit for bit.
+    Both results are device tensors and nothing is read back: points_out is (P,4) f32 of which rows offsets_out[0] = 0 ..
+    offsets_out[B] are written, offsets_out (B + 1) int32 -- what ops.point_cloud_2_top_batch, ops.point_cloud_2_top_paper and
+    ops.point_cloud_2_front take as (points, offsets); the rows behind offsets_out[B] belong to no frame.
+    points, offsets as ops.point_cloud_2_front takes them (offsets None: one frame of every row).  calib = (B,4,12) or (B,48) f32, or
+    a list of the frames' (4,12) tables (host values of any float type are cast to f32, as the feeds cast `calib`); image_hw = (B,2)
+    integers [height, width], or a list of the frames' image shapes (h, w) / (h, w, 3); a frame whose height or width is <= 0 keeps
+    nothing.  Numpy inputs are uploaded; tensors (calib f32, image_hw int32) must live on the points' device.
+    out = a contiguous (P,4) f32 device tensor, 16-byte aligned and apart from `points`, offsets_out = a contiguous (B + 1) int32 device
+    tensor, workspace = a uint8 device tensor of scan_crop_workspace_bytes(P) bytes, 16-byte aligned (default: the reused per-stream
+    buffer); with all three and device inputs the call allocates nothing and can be captured, and a replay may find other clouds and
+    other offsets in the same buffers.  Every argument is checked before anything is uploaded, allocated or launched: TypeError for
+    a wrong dtype, ValueError for a wrong shape, value or device.  Under malformed device offsets the call stays inside its buffers
+    and drops the rows no frame owns (include/mv3d_hip.h)."""
+    fn = "scan_crop_to_image"
+    tables = None
+
+    def more(B, P, dev):
+        nonlocal tables
+        tables = _crop_tables(fn, calib, image_hw, B)
+        for name, t, dtype, shape in (("out", out, torch.float32, (P, 4)), ("offsets_out", offsets_out, torch.int32, (B + 1,))):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+                raise TypeError("{}: {} must be a {} tensor".format(fn, name, dtype))
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("{}: {} must be contiguous {}, got {}".format(fn, name, shape, tuple(t.shape)))
+        mine = [(n, t) for n, t in (("calib", tables[0]), ("image_hw", tables[1]), ("out", out), ("offsets_out", offsets_out))
+                if isinstance(t, torch.Tensor)]
+        for name, t in mine:                                     # (a numpy cloud with no tensor beside it goes to the current device)
+            if not t.is_cuda or t.device != (dev if isinstance(dev, torch.device) else torch.device("cuda", torch.cuda.current_device())):
+                raise ValueError("{}: {} on {}: every tensor must live on one HIP device".format(fn, name, t.device))
+        if out is not None:
+            if out.data_ptr() % 16:
+                raise ValueError("{}: out must be 16-byte aligned".format(fn))
+            if isinstance(points, torch.Tensor) and P and out.data_ptr() < points.data_ptr() + 16 * P and points.data_ptr() < out.data_ptr() + 16 * P:
+                raise ValueError("{}: out must not overlap points".format(fn))
+        if workspace is not None and workspace.data_ptr() % 16:
+            raise ValueError("{}: workspace must be 16-byte aligned".format(fn))
+
+    need = lambda B: scan_crop_workspace_bytes(points.shape[0])
+    pts, off, B, P, _, dev = _scan_args(fn, points, offsets, None, None, workspace, need, more=more)
+    cal, hw = ((t if isinstance(t, torch.Tensor) else torch.from_numpy(t).to(pts.device)).contiguous() for t in tables)
+    if out is None:
+        out = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
+    if offsets_out is None:
+        offsets_out = torch.empty((B + 1,), dtype=torch.int32, device=pts.device)
+    if workspace is None:
+        workspace = _workspace(need(B), pts.device, "scan_crop")
+    check(lib().mv3d_scan_crop_to_image(_ptr(pts), _ptr(off), B, P, _ptr(cal), _ptr(hw), _ptr(out), _ptr(offsets_out), _ptr(workspace),
+                                        workspace.numel(), _stream()), "mv3d_scan_crop_to_image")
+    return out, offsets_out
 
 
 def gt_encode(box_cam, cos_sin, inv_rot, tr):

@@ -15,6 +15,9 @@ cfg.LIDAR_BV_FROM_SCAN (not in the reference; default off) takes `lidar_bv_data`
 scan ('velodyne' array or 'velodyne_path' file) instead of 'lidar_bv_path': a (1,601,601,9) device tensor rasterised by
 ops.scan_bev -- ops.point_cloud_2_top_batch, or under cfg.LIDAR_BV_ENCODING = 'paper' ops.point_cloud_2_top_paper and (1,601,601,10) --,
 im_info = (601, 601, 1); with both keys on the scan is read and uploaded once for both rasters.
+cfg.LIDAR_CROP_TO_IMAGE (not in the reference; default off; needs LIDAR_BV_FROM_SCAN) crops every scan uploaded here to the points
+inside the frame's own image before either raster reads it: see `_device_cloud`.  In-memory 'lidar_bv' / 'lidar_fv' maps are the
+caller's and stay as they are.
 cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`."""
 import numpy as np
 import numpy.random as npr
@@ -42,7 +45,19 @@ def _entry_cloud(entry, key, own_map):
     return pts
 
 
-def front_view_blob(entry, cloud=None):
+def _device_cloud(entry, key, own_map, image):
+    """(points, offsets) of a roidb entry's scan on the device, what the rasterisers take: `_entry_cloud` uploaded once, offsets None
+    = one frame of every row.  Under cfg.LIDAR_CROP_TO_IMAGE the upload is cropped (ops.scan_crop_to_image) to the points the entry's
+    calibration table puts inside `image`, the frame's own (h, w, 3) pixels: offsets is then the crop's (2,) device tensor, and the
+    rows of `points` behind offsets[1] belong to no frame.  A `flipped` entry's cloud, y negated, is cropped with the entry's own,
+    mirrored table; at the image border that need not be the mirror of the source frame's crop."""
+    cloud = ops._dev(_entry_cloud(entry, key, own_map))
+    if ops.scan_crop():
+        return ops.scan_crop_to_image(cloud, None, [entry['calib']], [np.shape(image)])
+    return cloud, None
+
+
+def front_view_blob(entry, cloud=None, offsets=None):
     """`lidar_fv_data` (1,64,512,3) f32 on the device for one roidb entry, from the first of: entry['lidar_fv'], a (64,512,3) map in
     memory, used as is; entry['velodyne'], a (P,4) [x,y,z,reflectance] array; entry['velodyne_path'], a KITTI `.bin` scan or a `.npy`
     (utils.read_lidar.load_velodyne) -- a cloud is rasterised by ops.point_cloud_2_front.
@@ -52,13 +67,15 @@ def front_view_blob(entry, cloud=None):
     +45 deg is column 0 while -45 deg is column 512, outside the map -- so reversing the columns is not the mirrored scene's raster.
     An in-memory 'lidar_fv' is the caller's map for that entry and is not touched.
     cloud = the entry's scan already on the device, (P,4) f32 with y negated if the entry is `flipped` (what get_minibatch uploaded
-    for the bird's-eye view under cfg.LIDAR_BV_FROM_SCAN): rasterised in place of a second read and upload of the scan."""
+    for the bird's-eye view under cfg.LIDAR_BV_FROM_SCAN): rasterised in place of a second read and upload of the scan.  offsets =
+    that cloud's (2,) device offsets where it was cropped (`_device_cloud`): the one frame owns rows offsets[0]:offsets[1]."""
     if 'lidar_fv' in entry:
         fv = ops._dev(entry['lidar_fv'])
         if tuple(fv.shape) != ops.FV_SHAPE:
             raise ValueError("entry['lidar_fv'] must be {}, got {}".format(ops.FV_SHAPE, tuple(fv.shape)))
         return fv[None]
-    return ops.point_cloud_2_front(_entry_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv') if cloud is None else cloud)[None]
+    cloud = _entry_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv') if cloud is None else cloud
+    return ops.point_cloud_2_front(cloud, offsets=offsets).reshape((1,) + ops.FV_SHAPE)
 
 
 def image_blob(entry, image):
@@ -84,12 +101,14 @@ def get_minibatch(roidb, num_classes):
     image = entry['image'] if 'image' in entry else read_image_bgr(entry['image_path'])
     on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)              # then image_data is final here: built, and mirrored, by ops.image_blob
     image_data = image_blob(entry, image) if on_device else (image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS)[None].astype(np.float32)
-    cloud = None
+    cloud = offsets = None
     if cfg.LIDAR_BV_FROM_SCAN and 'lidar_bv' not in entry:
         # no stored map: the scan is uploaded once (a mirrored frame's with y negated, whose raster IS the column-reversed map:
-        # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror) and rasterised on the device
-        cloud = ops._dev(_entry_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv'))
-        blobs = {'image_data': image_data, 'lidar_bv_data': ops.scan_bev(cloud)[None], 'calib': entry['calib']}
+        # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror), cropped to the image under cfg.LIDAR_CROP_TO_IMAGE, and
+        # rasterised on the device
+        cloud, offsets = _device_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv', image)
+        bev = ops.scan_bev(cloud, offsets)
+        blobs = {'image_data': image_data, 'lidar_bv_data': bev.reshape((1,) + tuple(bev.shape[-3:])), 'calib': entry['calib']}
         blobs.update(gt_blobs(entry, ops.BEV_SHAPE))
         if entry.get('flipped', False) and not on_device:
             blobs['image_data'] = ops.mirror_columns(ops._dev(blobs['image_data']))
@@ -107,5 +126,7 @@ def get_minibatch(roidb, num_classes):
         for k in ('lidar_bv_data',) if on_device else ('image_data', 'lidar_bv_data'):
             blobs[k] = ops.mirror_columns(ops._dev(blobs[k]))
     if cfg.FRONT_VIEW_INPUT:
-        blobs['lidar_fv_data'] = front_view_blob(entry, cloud)
+        if cloud is None and 'lidar_fv' not in entry and ops.scan_crop():      # (an in-memory 'lidar_bv': the scan was not uploaded above)
+            cloud, offsets = _device_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv', image)
+        blobs['lidar_fv_data'] = front_view_blob(entry, cloud, offsets)
     return blobs
