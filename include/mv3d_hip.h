@@ -781,6 +781,42 @@ int mv3d_rcnn_loss(const float *cls_score_dev, const int32_t *labels_dev, const 
                    const float *bbox_targets_dev, int num_rois, int num_classes, int box_dim, float sigma,
                    float *losses_dev, float *d_cls_score_dev, float *d_bbox_pred_dev, void *workspace,
                    size_t workspace_bytes, void *stream);
+/* (not in the reference) mv3d_rcnn_loss with the row selection label != -1 for BOTH terms: the means run over the selected rows, the
+ * mean over no rows is NaN (the RPN's rule), the gradient rows of skipped rows are exactly 0.  Same kernels, same arguments, same
+ * workspace; with no label at -1 every output is bit-equal to mv3d_rcnn_loss.  In mv3d_rcnn_loss itself a label of -1 stays out of
+ * range (a NaN loss). */
+int mv3d_rcnn_loss_ignore(const float *cls_score_dev, const int32_t *labels_dev, const float *bbox_pred_dev,
+                          const float *bbox_targets_dev, int num_rois, int num_classes, int box_dim, float sigma,
+                          float *losses_dev, float *d_cls_score_dev, float *d_bbox_pred_dev, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
+/* (not in the reference) Ignore regions in training: sampled background anchors and sampled background ROIs that lie on an ignore
+ * region of their frame get label -1.  Out of place: the inputs are not written, every output label is.
+ *   IoA(c, q)  intersection over the CANDIDATE's area, all f64, +1 pixel convention: iw = min(c2, q2) - max(c0, q0) + 1, ih likewise,
+ *              both > 0 or the result is 0; iw * ih / ((c2 - c0 + 1) (c3 - c1 + 1)); 0 when that area is not > 0 or any of the eight
+ *              numbers is NaN.
+ *   relabel    a label that is exactly 0 becomes -1 iff max_k IoA(c_bv, ignore_bv[b][k]) >= overlap or
+ *              max_m IoA(c_img, ignore_img[b][m]) >= overlap (f64 compare; a NaN overlap relabels nothing); every other label passes
+ *              through bit for bit.
+ *   anchors    rpn_labels (batch, N = 4 H W) f32: c_bv = anchor n of the W-wide grid at feat_stride as integers, not clipped; c_img =
+ *              the image box of that anchor's 3D prior under calib[b] (batch, 4, 12), as mv3d_proposal_3d decodes it (four int32).
+ *   ROIs       roi_labels (num_rois) i32; c_bv = rois_bv[r, 1:5], c_img = rois_img[r, 1:5] (both (num_rois, 5) f32), frame =
+ *              rois_bv[r, 0]; a row whose frame column is no integer in [0, batch) passes through.
+ *   lists      ignore_*_dev (rows, 4) f32 [x1, y1, x2, y2] packed frame after frame, ignore_*_off_dev (batch + 1) i32 ON THE DEVICE:
+ *              frame b owns rows off[b] .. off[b + 1].  Empty frames and empty lists (rows = 0, data pointer NULL) are ordinary.
+ *   counts_dev (batch, 2) i32 or NULL: relabelled anchors and ROIs per frame.
+ *   status_dev (batch) i32 or NULL: MV3D_OK, or MV3D_ERR_INVALID_ARG for a frame whose offsets (either list) are negative, decrease,
+ *              run past the given row count or span more than 1024 boxes; such a frame's labels are written through unchanged and
+ *              its counts are 0.  Nothing in the offsets can take a read out of bounds.
+ * ONE launch, grid (batch, 2) of 1024 threads; no allocation, no read-back, no synchronisation (capturable).  MV3D_ERR_INVALID_ARG
+ * before the launch: a NULL required pointer (the four ROI arrays are required only for num_rois > 0), batch outside [1, 65535],
+ * H, W or feat_stride < 1, negative counts, 4 H W or the last anchor beyond int32. */
+int mv3d_ignore_relabel(const float *rpn_labels_dev, const int32_t *roi_labels_dev, const float *rois_bv_dev,
+                        const float *rois_img_dev, int num_rois, const float *calib_dev, int batch, int H, int W,
+                        int feat_stride, const float *ignore_bv_dev, const int32_t *ignore_bv_off_dev, int ignore_bv_rows,
+                        const float *ignore_img_dev, const int32_t *ignore_img_off_dev, int ignore_img_rows, double overlap,
+                        float *rpn_labels_out_dev, int32_t *roi_labels_out_dev, int32_t *counts_dev, int32_t *status_dev,
+                        void *stream);
 
 /* ------------------------------------------------------------------ the VGG16 trunk's contraction (north_star "MFMA only for the
  * VGG16 conv backbone"): Network.conv(3, 3, c_o, 1, 1) [3x3, stride 1, SAME, + bias, optional ReLU] and

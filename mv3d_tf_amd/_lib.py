@@ -223,6 +223,9 @@ _SIGS = {
     "mv3d_loss_workspace_bytes": (C.c_size_t, [C.c_int]),
     "mv3d_rpn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
     "mv3d_rcnn_loss": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv3d_rcnn_loss_ignore": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv3d_ignore_relabel": (C.c_int, [_P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int,
+                                      C.c_double, _P, _P, _P, _P, _P]),
     "mv3d_roi_pool_forward_views": (C.c_int, [C.c_int, C.POINTER(RoiView), C.c_int, C.c_int, _P]),
     "mv3d_roi_pool_forward_views_cold": (C.c_int, [C.c_int, C.POINTER(RoiView), C.c_int, C.c_int, _P]),
     "mv3d_roi_pool_forward_views_half": (C.c_int, [C.c_int, C.POINTER(RoiView), C.c_int, C.c_int, C.c_int, C.c_int, _P]),

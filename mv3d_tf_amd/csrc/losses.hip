@@ -6,7 +6,8 @@
 //                   smoothL1(x) = 0.5 (sigma x)^2 if |x| < 1/sigma^2, |x| - 0.5/sigma^2 otherwise
 //
 // Row selection: RPN (labels f32 in {-1, 0, 1}): cross-entropy over label != -1, box loss over label == 1 (:95-97);
-// RCNN (labels i32): every row.  A mean over no rows is NaN, as tf.reduce_mean of an empty tensor.
+// RCNN (labels i32): every row; mv3d_rcnn_loss_ignore (not in the reference): both terms over label != -1.
+// A mean over no rows is NaN, as tf.reduce_mean of an empty tensor.
 //
 // Two launches, no atomics, deterministic: (1) every workgroup writes the losses' partial sums of its 256 rows and the
 // UNSCALED gradients; (2) every workgroup adds the partials up in the same fixed order, scales its rows' gradients
@@ -21,6 +22,7 @@ struct LossDev {
     const int32_t *labels_i;     // (R) i32 labels (RCNN) or NULL
     const float *pred, *tgt;     // (R, D)
     int R, K, D;
+    int skip_ignored;            // RCNN only: rows with label -1 take no part (mv3d_rcnn_loss_ignore)
     float sigma2;
     double *partial;             // (blocks, 4): n_ce, n_box, sum_ce, sum_box
     float *losses;               // [2]
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(256) void loss_partial_kernel(LossDev d)
         int label;
         bool use_ce, use_box;
         if (d.labels_f) { const float lf = d.labels_f[r]; label = (int)lf; use_ce = (lf != -1.0f); use_box = (lf == 1.0f); }
-        else { label = d.labels_i[r]; use_ce = use_box = true; }
+        else { label = d.labels_i[r]; use_ce = use_box = !(d.skip_ignored && label == -1); }
         const float *z = d.cls + (long long)r * d.K;
         float *dz = d.d_cls ? d.d_cls + (long long)r * d.K : nullptr;
         if (use_ce) {
@@ -141,6 +143,19 @@ extern "C" int mv3d_rcnn_loss(const float *cls_score_dev, const int32_t *labels_
     d.cls = cls_score_dev; d.labels_i = labels_dev; d.pred = bbox_pred_dev; d.tgt = bbox_targets_dev;
     d.R = num_rois; d.K = num_classes; d.D = box_dim; d.sigma2 = sigma * sigma; d.losses = losses_dev;
     d.d_cls = d_cls_score_dev; d.d_pred = d_bbox_pred_dev;
+    return launch_loss(d, workspace, workspace_bytes, stream);
+}
+
+// mv3d_rcnn_loss with the row selection label != -1 for both terms (ignore regions); the gradient rows of skipped rows are exactly 0
+extern "C" int mv3d_rcnn_loss_ignore(const float *cls_score_dev, const int32_t *labels_dev, const float *bbox_pred_dev,
+                                     const float *bbox_targets_dev, int num_rois, int num_classes, int box_dim, float sigma,
+                                     float *losses_dev, float *d_cls_score_dev, float *d_bbox_pred_dev, void *workspace,
+                                     size_t workspace_bytes, void *stream)
+{
+    LossDev d = {};
+    d.cls = cls_score_dev; d.labels_i = labels_dev; d.pred = bbox_pred_dev; d.tgt = bbox_targets_dev;
+    d.R = num_rois; d.K = num_classes; d.D = box_dim; d.sigma2 = sigma * sigma; d.losses = losses_dev;
+    d.d_cls = d_cls_score_dev; d.d_pred = d_bbox_pred_dev; d.skip_ignored = 1;
     return launch_loss(d, workspace, workspace_bytes, stream);
 }
 

@@ -24,7 +24,7 @@ import scipy.sparse
 import torch
 
 from .. import ops
-from ..fast_rcnn.config import cfg
+from ..fast_rcnn.config import cfg, check_ignore_types
 from .mirror import mirror_annotation, mirror_calib
 
 # calibration file: the reference reads lines 2..5 by position (:158-168); KITTI writes them in this order
@@ -52,26 +52,34 @@ def _device():
     return torch.device("cuda", cfg.GPU_ID)
 
 
-def parse_kitti_labels(lines, Tr, class_to_ind, num_classes):
+def parse_kitti_labels(lines, Tr, class_to_ind, num_classes, ignore_types=None):
     """Annotation dict of one frame (roidb entry) from its label lines.  Objects whose type is not a key of `class_to_ind`
-    are dropped.  Geometry on the device: `mv3d_gt_encode`."""
-    table = [ln.split() for ln in lines if ln.strip()]
-    table = [t for t in table if t[0] in class_to_ind]
+    are dropped.  Geometry on the device: `mv3d_gt_encode`.
+    ignore_types (not in the reference; cfg.TRAIN.IGNORE_TYPES): a non-empty sequence of KITTI types adds the
+    frame's ignore regions -- `ignore_boxes_bv` (K, 4) f32, the `boxes_bv` of the listed types' rows that have a 3D box (h, w, l all
+    > 0, which DontCare rows have not), encoded by the same `mv3d_gt_encode` call as the objects; `ignore_boxes_3D` (K, 6), their
+    LIDAR boxes (what the mirror needs); `ignore_boxes_img` (M, 4) f32, the image boxes of the listed 'DontCare' rows,
+    float32(float64(text)).  None or empty: exactly the keys above."""
+    every = [ln.split() for ln in lines if ln.strip()]
+    table = [t for t in every if t[0] in class_to_ind]
     G = len(table)
-    cls = np.array([class_to_ind[t[0]] for t in table], dtype=np.int32).reshape(G)
+    ign = check_ignore_types(ignore_types, trained=tuple(class_to_ind))
+    ign3d = [t for t in every if t[0] in ign and all(float(v) > 0 for v in t[8:11])] if ign else []
+    table = table + ign3d                                                             # (one encode call for both; split below)
+    cls = np.array([class_to_ind[t[0]] for t in table[:G]], dtype=np.int32).reshape(G)
     # label columns 3..14 (KITTI devkit order: alpha | x1 y1 x2 y2 | h w l | tx ty tz | rotation_y) as the text's floats
-    num = np.array([t[3:15] for t in table], dtype=np.float64).reshape(G, 12)
+    num = np.array([t[3:15] for t in table], dtype=np.float64).reshape(len(table), 12)
     alpha, box2d, hwl, xyz, ry = num[:, 0], num[:, 1:5], num[:, 5:8], num[:, 8:11], num[:, 11]
     lwh = hwl[:, ::-1]
     box_cam = np.ascontiguousarray(np.hstack([xyz, lwh]), dtype=np.float32)          # (tx, ty, tz, l, w, h) f32
-    ann = {'ry': ry.astype(np.float32), 'lwh': lwh.astype(np.float32), 'boxes': box2d.astype(np.float32),
-           'boxes_3D_cam': box_cam, 'gt_classes': cls, 'xyz': xyz.astype(np.float32), 'alphas': alpha.astype(np.float32),
+    ann = {'ry': ry[:G].astype(np.float32), 'lwh': lwh[:G].astype(np.float32), 'boxes': box2d[:G].astype(np.float32),
+           'boxes_3D_cam': box_cam[:G], 'gt_classes': cls, 'xyz': xyz[:G].astype(np.float32), 'alphas': alpha[:G].astype(np.float32),
            'flipped': False}
     onehot = np.zeros((G, num_classes), dtype=np.float32)
     onehot[np.arange(G), cls] = 1.0
     ann['gt_overlaps'] = scipy.sparse.csr_matrix(onehot)
     tr = np.ascontiguousarray(Tr, dtype=np.float32).reshape(3, 4)
-    if G:
+    if len(table):
         dev = _device()
         cos_sin = np.stack([np.cos(ry), np.sin(ry)], axis=1)                          # f64, from the text's floats
         inv_rot = np.linalg.inv(tr[:, :3])                                            # f32 (LAPACK), once per frame
@@ -82,8 +90,19 @@ def parse_kitti_labels(lines, Tr, class_to_ind, num_classes):
     else:
         cam, lid = np.zeros((0, 24), np.float32), np.zeros((0, 24), np.float32)
         box3d, bv = np.zeros((0, 6), np.float32), np.zeros((0, 4), np.float32)
-    ann.update({'boxes3D_cam_corners': cam, 'boxes_corners': lid, 'boxes_3D': box3d, 'boxes_bv': bv})
+    ann.update({'boxes3D_cam_corners': cam[:G], 'boxes_corners': lid[:G], 'boxes_3D': box3d[:G], 'boxes_bv': bv[:G]})
+    if ign:
+        dc = [t[4:8] for t in every if t[0] == 'DontCare'] if 'DontCare' in ign else []
+        ann.update({'ignore_boxes_bv': bv[G:].copy(), 'ignore_boxes_3D': box3d[G:].copy(),
+                    'ignore_boxes_img': np.array(dc, dtype=np.float64).reshape(len(dc), 4).astype(np.float32)})
     return ann
+
+
+def ignore_blobs(entry):
+    """(cfg.TRAIN.IGNORE_TYPES) the ignore regions of one roidb entry as blobs: `ignore_boxes_bv` (K, 4) and `ignore_boxes_img` (M, 4)
+    f32, what MV3D.forward hands to ops.ignore_relabel.  An entry parsed without ignore_types raises KeyError."""
+    return {'ignore_boxes_bv': np.ascontiguousarray(entry['ignore_boxes_bv'], np.float32).reshape(-1, 4),
+            'ignore_boxes_img': np.ascontiguousarray(entry['ignore_boxes_img'], np.float32).reshape(-1, 4)}
 
 
 def gt_blobs(entry, lidar_bv_shape):
@@ -157,7 +176,8 @@ class kitti_mv3d(object):
     def _load_kitti_annotation(self, index):
         with open(os.path.join(self._data_path, 'training', 'label_2', index + '.txt')) as f:
             lines = f.readlines()
-        return parse_kitti_labels(lines, self._load_kitti_calib(index)['Tr_velo2cam'], self._class_to_ind, self.num_classes)
+        return parse_kitti_labels(lines, self._load_kitti_calib(index)['Tr_velo2cam'], self._class_to_ind, self.num_classes,
+                                  ignore_types=cfg.TRAIN.get('IGNORE_TYPES', ()) or None)
 
     def gt_roidb(self):
         return [self._load_kitti_annotation(index) for index in self._image_index]

@@ -44,7 +44,8 @@ def mirror_annotation(entry, width):
     """The roidb entry (parse_kitti_labels) of the mirrored frame; `width` = the image's width in pixels.  Every field is a
     copy, `entry` is not modified.  Fields this module does not know (what prepare_roidb adds) are copied as they are, so
     mirror before prepare_roidb.  One field is added: `boxes_residual` (G, 4) f32, what the f32 rounding of the mirrored
-    `boxes` dropped (see below); nothing else reads it.  Mirroring twice with one width restores every array field bit for
+    `boxes` dropped (see below); nothing else reads it.  An entry parsed with ignore_types has its `ignore_boxes_bv` / `ignore_boxes_3D`
+    mirrored like `boxes_bv` / `boxes_3D` and its `ignore_boxes_img` like `boxes` (with `ignore_boxes_img_residual`).  Mirroring twice with one width restores every array field bit for
     bit, except ry / alphas, which take two f32 roundings (and +-pi may come back as the other sign)."""
     W = int(width)
     if W < 1:
@@ -74,6 +75,19 @@ def mirror_annotation(entry, width):
         out[k] = a
     for k in ('ry', 'alphas'):
         out[k] = _mirror_angle(entry[k])
+    if 'ignore_boxes_bv' in entry:
+        # the frame's ignore regions (cfg.TRAIN.IGNORE_TYPES): the BEV boxes as boxes_bv above, from their mirrored LIDAR boxes; the
+        # DontCare image boxes as `boxes` above, with their own residual
+        i3 = np.array(entry['ignore_boxes_3D'], copy=True)
+        i3[:, 1] = -i3[:, 1]
+        out['ignore_boxes_3D'] = i3
+        out['ignore_boxes_bv'] = lidar_box_to_bv(i3).astype(np.asarray(entry['ignore_boxes_bv']).dtype)
+        ibox = np.asarray(entry['ignore_boxes_img'])
+        i64 = ibox.astype(np.float64) + (np.asarray(entry['ignore_boxes_img_residual'], np.float64)
+                                         if 'ignore_boxes_img_residual' in entry else 0.0)
+        n64 = np.stack([(W - 1) - i64[:, 2], i64[:, 1], (W - 1) - i64[:, 0], i64[:, 3]], axis=1)
+        out['ignore_boxes_img'] = n64.astype(ibox.dtype)
+        out['ignore_boxes_img_residual'] = (n64 - out['ignore_boxes_img'].astype(np.float64)).astype(np.float32)
     out['flipped'] = True
     return out
 

@@ -51,7 +51,15 @@ cfg.TRAIN = _section(
     # DROP_PATH draws global or local drop-path for the two joins of every training forward from the network's own generator
     # (net.drop_path_rng, seeded with RNG_SEED); AUX_LOSSES adds one weight-sharing auxiliary path per view with its own
     # classification and box loss (weight 1), removed at inference.
-    DROP_PATH=False, AUX_LOSSES=False)
+    DROP_PATH=False, AUX_LOSSES=False,
+    # (not in the reference, which drops every label row that is not a trained class, so a Van or the far traffic KITTI marks DontCare
+    # is trained as background while the evaluator forgives detections there) IGNORE_TYPES: KITTI label types whose regions take no part
+    # in training -- a SAMPLED background anchor or ROI whose intersection with such a region, over its OWN area, reaches IGNORE_OVERLAP
+    # (in BEV for the types' 3D boxes, in the image for DontCare boxes) gets label -1 on the device after the target layers have drawn
+    # (ops.ignore_relabel) and both stages' losses skip it.  The sample slot is spent, not redrawn; the numpy
+    # RNG stream of the draws is the key-off stream.  () = the reference.  The documented KITTI setting is ('Van', 'DontCare').  A type
+    # outside KITTI's vocabulary or a trained class raises ValueError (check_ignore_types below).  No accuracy claim.
+    IGNORE_TYPES=(), IGNORE_OVERLAP=0.5)
 cfg.TEST = _section(
     NMS=0.5, HAS_RPN=True, RPN_NMS_THRESH=0.7, RPN_PRE_NMS_TOP_N=12000, RPN_POST_NMS_TOP_N=2000, RPN_MIN_SIZE=5,
     DEBUG_TIMELINE=False,
@@ -131,6 +139,24 @@ cfg.USE_GPU_NMS = False
 cfg.GPU_ID = 0
 
 
+# KITTI's label vocabulary (devkit_object/readme.txt): what cfg.TRAIN.IGNORE_TYPES may list
+KITTI_TYPES = ('Car', 'Van', 'Truck', 'Pedestrian', 'Person_sitting', 'Cyclist', 'Tram', 'Misc', 'DontCare')
+
+
+def check_ignore_types(ignore_types, trained=('Car',)):
+    """cfg.TRAIN.IGNORE_TYPES -> tuple of str; ValueError for a type outside KITTI's vocabulary or a trained class (`trained`: the
+    dataset's class names; kitti_mv3d trains Car)"""
+    if isinstance(ignore_types, str):
+        raise ValueError("IGNORE_TYPES must be a sequence of KITTI label types, got the string %r" % (ignore_types,))
+    types = tuple(ignore_types or ())
+    for t in types:
+        if t not in KITTI_TYPES:
+            raise ValueError("IGNORE_TYPES: %r is not a KITTI label type %s" % (t, KITTI_TYPES))
+        if t in trained:
+            raise ValueError("IGNORE_TYPES: %r is a trained class" % (t,))
+    return types
+
+
 def _merge(a, b, path=""):
     for k, v in a.items():
         if k not in b:
@@ -145,6 +171,8 @@ def _merge(a, b, path=""):
             v = np.array(v, dtype=old.dtype)
         elif path + k == "ROI_UPSAMPLE" and isinstance(v, list):  # (YAML has no tuples: its sequence for this one key)
             v = tuple(v)
+        elif path + k == "TRAIN.IGNORE_TYPES" and isinstance(v, (list, tuple)):   # a YAML sequence, as ROI_UPSAMPLE
+            v = check_ignore_types(v)
         elif path + k == "IMAGE_CANVAS":                          # None or (H, W), a YAML sequence
             v = None if v is None else tuple(int(s) for s in v)
         elif type(old) is not type(v) and not (isinstance(old, float) and isinstance(v, int)):
@@ -175,7 +203,7 @@ def cfg_from_list(cfg_list):
             value = v
         assert type(value) == type(d[keys[-1]]) or k == 'IMAGE_CANVAS', 'type {} does not match original type {}'.format(
             type(value), type(d[keys[-1]]))
-        d[keys[-1]] = value
+        d[keys[-1]] = check_ignore_types(value) if k == 'TRAIN.IGNORE_TYPES' else value
 
 
 def apply_end2end_yml():

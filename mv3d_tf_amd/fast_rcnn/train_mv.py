@@ -38,16 +38,16 @@ class _RpnLoss(torch.autograd.Function):
 
 class _RcnnLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cls_score, labels, bbox_pred, bbox_targets, sigma):
+    def forward(ctx, cls_score, labels, bbox_pred, bbox_targets, sigma, ignore_label=None):
         losses, d_cls, d_pred = ops.rcnn_loss(cls_score.contiguous(), labels.contiguous(), bbox_pred.contiguous(),
-                                              bbox_targets.contiguous(), sigma)
+                                              bbox_targets.contiguous(), sigma, ignore_label=ignore_label)
         ctx.save_for_backward(d_cls, d_pred)
         return losses[0], losses[1]
 
     @staticmethod
     def backward(ctx, g_ce, g_box):
         d_cls, d_pred = ctx.saved_tensors
-        return d_cls * g_ce, None, d_pred * g_box, None, None
+        return d_cls * g_ce, None, d_pred * g_box, None, None, None
 
 
 def modified_smooth_l1(sigma, bbox_pred, bbox_targets):
@@ -68,12 +68,13 @@ def rpn_losses(rpn_cls_score_reshape, rpn_data, rpn_bbox_pred, sigma=3.0):
     return _RpnLoss.apply(cls, labels, rpn_bbox_pred.reshape(-1, 6), targets, float(sigma))
 
 
-def rcnn_losses(cls_score, roi_data_3d, bbox_pred, sigma=3.0):
+def rcnn_losses(cls_score, roi_data_3d, bbox_pred, sigma=3.0, ignore_label=None):
     """train_mv.py:115-127: (cross_entropy, loss_box) from `cls_score`, the `roi_data_3d` tuple (.., labels, targets, ..)
-    of proposal_target_layer_3d and `bbox_pred`."""
+    of proposal_target_layer_3d and `bbox_pred`.  ignore_label=-1 (not in the reference; cfg.TRAIN.IGNORE_TYPES): rows with that label
+    take no part in either term (ops.rcnn_loss)."""
     labels = torch.as_tensor(roi_data_3d[2], device=cls_score.device).reshape(-1).to(torch.int32)
     targets = torch.as_tensor(roi_data_3d[3], dtype=torch.float32, device=cls_score.device)
-    return _RcnnLoss.apply(cls_score, labels, bbox_pred, targets, float(sigma))
+    return _RcnnLoss.apply(cls_score, labels, bbox_pred, targets, float(sigma), ignore_label)
 
 
 def total_loss(net_layers, sigma=3.0):
@@ -81,8 +82,11 @@ def total_loss(net_layers, sigma=3.0):
     of B frames every loss is the mean over the frames of the reference's per-frame loss (what B single-frame steps with
     averaged gradients give, and what the data-parallel all-reduce averages across ranks).  Under deep fusion with
     cfg.TRAIN.AUX_LOSSES the layers hold one auxiliary path per view (`cls_score_aux`, `bbox_pred_aux`): the total gains every path's
-    two ROI losses with weight 1, the returned 4-tuple stays the main terms, and net_layers['loss_aux'] (V, 2) holds the auxiliary ones."""
+    two ROI losses with weight 1, the returned 4-tuple stays the main terms, and net_layers['loss_aux'] (V, 2) holds the auxiliary ones.
+    Under cfg.TRAIN.IGNORE_TYPES the ROI losses, main and auxiliary, skip the rows labelled -1 (the RPN losses always do); a frame
+    whose every sampled ROI was relabelled has a NaN ROI loss, the mean over no rows."""
     L = net_layers
+    ign = -1 if cfg.TRAIN.get('IGNORE_TYPES', ()) else None
     rpn_data = L['rpn_data']
     data = L['roi_data_3d']
     aux = L.get('cls_score_aux')                                # deep fusion with cfg.TRAIN.AUX_LOSSES: (V, R, 2) / (V, R, 48)
@@ -91,13 +95,13 @@ def total_loss(net_layers, sigma=3.0):
         """every auxiliary path's (cross_entropy, loss_box), weight 1 each, through the same loss kernel: the mean over the frames,
         kept as net_layers['loss_aux'] (V, 2); returns their sum"""
         vals = [t for sl in slices for v in range(aux.shape[0])
-                for t in rcnn_losses(aux[v][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred_aux'][v][sl], sigma)]
+                for t in rcnn_losses(aux[v][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred_aux'][v][sl], sigma, ign)]
         L['loss_aux'] = torch.stack(vals).view(len(slices), aux.shape[0], 2).mean(0)
         return L['loss_aux'].sum()
 
     if rpn_data[0].dim() == 1:                                  # one frame: the reference's shapes
         rpn_ce, rpn_box = rpn_losses(L['rpn_cls_score_reshape'], rpn_data, L['rpn_bbox_pred'], sigma)
-        ce, box = rcnn_losses(L['cls_score'], data, L['bbox_pred'], sigma)
+        ce, box = rcnn_losses(L['cls_score'], data, L['bbox_pred'], sigma, ign)
         total = ce + box + rpn_ce + rpn_box
         return (total if aux is None else total + aux_terms([slice(None)])), (ce, box, rpn_ce, rpn_box)
     B = rpn_data[0].shape[0]
@@ -109,7 +113,7 @@ def total_loss(net_layers, sigma=3.0):
         sl = slice(o, o + rows[b])
         slices.append(sl)
         o += rows[b]
-        ce, box = rcnn_losses(L['cls_score'][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred'][sl], sigma)
+        ce, box = rcnn_losses(L['cls_score'][sl], (None, None, data[2][sl], data[3][sl]), L['bbox_pred'][sl], sigma, ign)
         vals += [ce, box, r_ce, r_box]
     # the frames' means with ONE stack + ONE reduction (4 B scalars added and divided one by one were 4 B + 4 B launches each way)
     parts = torch.stack(vals).view(B, 4).mean(0)
@@ -118,7 +122,7 @@ def total_loss(net_layers, sigma=3.0):
 
 def stack_blobs(frames):
     """blobs of several frames (RoIDataLayer.forward() each) -> the feed of one batched pass: images / BEV maps stacked on
-    axis 0 (same size per batch, as KITTI crops are), im_info (B,3), calib (B,4,12), ground truth as per-frame lists.  A map may be
+    axis 0 (same size per batch, as KITTI crops are), im_info (B,3), calib (B,4,12), ground truth and ignore regions as per-frame lists.  A map may be
     a device tensor (the mirrored frames of cfg.TRAIN.USE_FLIPPED): a stack that holds one is made on the device, its numpy
     members uploaded first."""
     if len(frames) == 1:
@@ -137,6 +141,9 @@ def stack_blobs(frames):
     for k in ("gt_boxes", "gt_boxes_bv", "gt_boxes_3d", "gt_boxes_corners"):
         if k in frames[0]:
             feed[k] = [np.asarray(f[k], np.float32) for f in frames]
+    for k in ("ignore_boxes_bv", "ignore_boxes_img"):            # (cfg.TRAIN.IGNORE_TYPES) per frame, packed by the forward pass
+        if k in frames[0]:
+            feed[k] = [np.asarray(f[k], np.float32).reshape(-1, 4) for f in frames]
     return feed
 
 
@@ -272,6 +279,7 @@ class SolverWrapper(object):
             # over its frames either way; the all-reduce starts with the LAST sub-batch's backward pass.
             groups = group_frames_by_shape([data_layer.forward() for _ in range(frames_per_step)])   # get one batch (:162), x frames
             vals = np.zeros(4)
+            ignored = np.zeros(2, np.int64)                                               # relabelled (anchors, ROIs) of this step
             for gi, grp in enumerate(groups):
                 feed = stack_blobs(grp)
                 feed["keep_prob"] = 0.5                                                   # feed_dict (:165-173)
@@ -282,6 +290,8 @@ class SolverWrapper(object):
                 bucketer.dist_enabled = (gi == len(groups) - 1)  # the bucketed all-reduce overlaps the last backward pass
                 (loss if len(groups) == 1 else loss * share).backward()
                 vals += share * np.array([float(v.detach()) for v in parts])              # (ce, box, rpn_ce, rpn_box)
+                if "ignored" in layers and (it + 1) % cfg.TRAIN.DISPLAY == 0:             # (cfg.TRAIN.IGNORE_TYPES; read on display steps only)
+                    ignored = ignored + layers["ignored"].sum(0).cpu().numpy()
             bucketer.finish()
             self.optimizer.step()
             if torch.cuda.is_available():
@@ -297,6 +307,8 @@ class SolverWrapper(object):
             if (it + 1) % cfg.TRAIN.DISPLAY == 0 and rank == 0:
                 self.log('iter: %d / %d, total loss: %.4f, rpn_loss_cls: %.4f, rpn_loss_box: %.4f, loss_cls: %.4f, loss_box: %.4f, lr: %f'
                          % (it + 1, max_iters, history[-1][0], rpn_loss_cls, rpn_loss_box, loss_cls, loss_box, lr))
+                if cfg.TRAIN.get('IGNORE_TYPES', ()):
+                    self.log('ignored: %d anchors, %d rois' % (ignored[0], ignored[1]))
                 self.log('speed: {:.3f}s / iter'.format(spent / (it + 1 - start_iter)))
             if (it + 1) % cfg.TRAIN.SNAPSHOT_ITERS == 0:
                 last_snapshot_iter = it

@@ -456,6 +456,11 @@ class MV3D:
         self._bev_interior = None
         dev = self.device
         to_dev = lambda a: a.to(dev) if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, np.float32)).to(dev)
+        # (not in the reference) cfg.TRAIN.IGNORE_TYPES: the frames' ignore regions must come with the feed, checked before any work
+        ign_on = self.phase == "TRAIN" and bool(cfg.TRAIN.get("IGNORE_TYPES", ()))
+        if ign_on and any(feed.get(k) is None for k in ("ignore_boxes_bv", "ignore_boxes_img")):
+            raise ValueError("cfg.TRAIN.IGNORE_TYPES is set and the feed has no ignore_boxes_bv / ignore_boxes_img "
+                             "(roi_data_layer.minibatch_mv3d.get_minibatch adds them under the key)")
         self._stage_host_inputs(feed, L, dev, to_dev)
         if L["lidar_bv_data"].shape[-1] != self.bev_channels:
             raise ValueError("lidar_bv_data has %d channels, the network's BEV trunk takes %d (bev_channels; cfg.LIDAR_BV_ENCODING)"
@@ -552,13 +557,21 @@ class MV3D:
             rois = (cat(bvb), cat(imgb), cat(b3b))
             rois = rois + (rois[2],)                                                  # network.py:234
             L["rpn_rois"] = rois
+            rpn_labels, roi_labels = out["rpn_labels"], out["labels"]
+            if ign_on:
+                # sampled background anchors / ROIs on an ignore region -> label -1, one launch behind the target layers (DESIGN.md
+                # section 3.26); the path's own buffers stay as drawn.  One frame's lists come as arrays, several frames' as lists.
+                lists = [list(feed[k]) if isinstance(feed[k], (list, tuple)) else [feed[k]] for k in ("ignore_boxes_bv", "ignore_boxes_img")]
+                rpn_labels, roi_labels, L["ignored"], L["ignore_status"] = ops.ignore_relabel(
+                    rpn_labels, roi_labels, out["rois"]["bev"], out["rois"]["rgb"], cal, h, w, lists[0], lists[1],
+                    float(cfg.TRAIN.IGNORE_OVERLAP), feat_stride=stride, want_counts=True)
             if B == 1:
                 m = int(out["n_anchors"][0].item())
-                L["rpn_data"] = (out["rpn_labels"][0], out["rpn_targets"][0], out["anchors"][0, :m], out["anchors_3d"][0, :m])
+                L["rpn_data"] = (rpn_labels[0], out["rpn_targets"][0], out["anchors"][0, :m], out["anchors_3d"][0, :m])
             else:
-                L["rpn_data"] = (out["rpn_labels"], out["rpn_targets"], out["anchors"], out["anchors_3d"], out["n_anchors"])
+                L["rpn_data"] = (rpn_labels, out["rpn_targets"], out["anchors"], out["anchors_3d"], out["n_anchors"])
             L["rpn-data"] = L["rpn_data"]                                             # (the Faster-RCNN spelling)
-            data = (out["rois"]["bev"], out["rois"]["rgb"], out["labels"], out["bbox_targets"], out["rois_3d"])
+            data = (out["rois"]["bev"], out["rois"]["rgb"], roi_labels, out["bbox_targets"], out["rois_3d"])
             L["roi_data_3d"] = data                                                   # (rois_bv, rois_img, labels, targets, rois_3d)
             L["roi_data_bv"], L["roi_data_img"] = data[0], data[1]                    # proposal_transform (network.py:292-315)
             r3, rois_fv = data[4], out["rois"]["fv"]

@@ -1335,10 +1335,107 @@ def rpn_loss(rpn_cls_score, rpn_labels, rpn_bbox_pred, rpn_bbox_targets, sigma=3
                       sigma, want_grad)
 
 
-def rcnn_loss(cls_score, labels, bbox_pred, bbox_targets, sigma=3.0, want_grad=True):
-    """(S,K) logits, (S) i32 labels, (S,D) pred / targets -> (losses[2], d_cls, d_pred)."""
-    return _loss_call(lib().mv3d_rcnn_loss, "mv3d_rcnn_loss", cls_score, labels, bbox_pred, bbox_targets,
-                      (cls_score.shape[1], bbox_pred.shape[1]), sigma, want_grad)
+def rcnn_loss(cls_score, labels, bbox_pred, bbox_targets, sigma=3.0, want_grad=True, ignore_label=None):
+    """(S,K) logits, (S) i32 labels, (S,D) pred / targets -> (losses[2], d_cls, d_pred).  ignore_label=-1 (not in the reference,
+    DESIGN.md section 3.26): rows with that label take no part in either term (mv3d_rcnn_loss_ignore: means over the other rows, NaN
+    over none, zero gradient rows); None = the reference's every row, where a label of -1 poisons the loss."""
+    if ignore_label is None:
+        fn, name = lib().mv3d_rcnn_loss, "mv3d_rcnn_loss"
+    elif int(ignore_label) == -1:
+        fn, name = lib().mv3d_rcnn_loss_ignore, "mv3d_rcnn_loss_ignore"
+    else:
+        raise ValueError("rcnn_loss: ignore_label must be None or -1, got %r" % (ignore_label,))
+    return _loss_call(fn, name, cls_score, labels, bbox_pred, bbox_targets, (cls_score.shape[1], bbox_pred.shape[1]), sigma, want_grad)
+
+
+# ------------------------------------------------------------------ ignore regions in training (DESIGN.md section 3.26)
+IGNORE_MAX_BOXES = 1024               # TARGET_MAX_GT: ignore boxes per frame and list
+
+
+def pack_box_lists(frames):
+    """per-frame (K_b, 4) host arrays -> (rows (sum K_b, 4) f32, offsets (B + 1) int32): the packed form ignore_relabel takes"""
+    arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in frames]
+    off = np.zeros((len(arrs) + 1,), np.int32)
+    off[1:] = np.cumsum([a.shape[0] for a in arrs])
+    return (np.concatenate(arrs, 0) if arrs else np.zeros((0, 4), np.float32)), off
+
+
+def _is_packed(v):
+    if not (isinstance(v, tuple) and len(v) == 2):
+        return False
+    if isinstance(v[1], torch.Tensor):
+        return v[1].dim() == 1 and v[1].dtype == torch.int32
+    return np.ndim(v[1]) == 1 and np.issubdtype(np.asarray(v[1]).dtype, np.integer)
+
+
+def ignore_relabel(rpn_labels, roi_labels, rois_bv, rois_img, calib, H, W, ignore_bv, ignore_img, overlap, feat_stride=8,
+                   want_counts=False, out=None):
+    """Sampled background anchors and ROIs on an ignore region get label -1 (mv3d_ignore_relabel, one launch, out of place).
+    rpn_labels (B, 4 H W) f32 and roi_labels (S) or (S, 1) int32 device tensors, rois_bv / rois_img (S, 5) f32 with the frame in column
+    0, calib (B, 4, 12) f32.  ignore_bv / ignore_img: a sequence of B per-frame (K_b, 4) arrays, or an already packed (rows, offsets)
+    tuple -- rows (R, 4) f32, offsets (B + 1) int32; host lists cross in ONE copy, packed device tensors are used where they lie (no
+    allocation beyond the outputs, capturable with out=).  overlap: the f64 threshold on the intersection over the candidate's area.
+    Returns (rpn_labels_out, roi_labels_out, counts, status): the labels in the inputs' shapes, counts (B, 2) int32 [anchors, ROIs]
+    relabelled per frame (None unless want_counts), status (B) int32 = _lib.ERR_INVALID_ARG for a frame whose offsets are out of
+    order, out of the rows or span more than IGNORE_MAX_BOXES (its labels are written through); all on the device, nothing is read
+    back.  out = that tuple from an earlier call (counts may be None) to write into."""
+    name = "ignore_relabel"
+    for nm, t, dt in (("rpn_labels", rpn_labels, torch.float32), ("roi_labels", roi_labels, torch.int32), ("rois_bv", rois_bv, torch.float32),
+                      ("rois_img", rois_img, torch.float32), ("calib", calib, torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError("%s: %s must be a device tensor" % (name, nm))
+        if t.dtype != dt:
+            raise TypeError("%s: %s must be %s, got %s" % (name, nm, dt, t.dtype))
+    dev = rpn_labels.device
+    H, W = int(H), int(W)
+    if rpn_labels.dim() != 2 or rpn_labels.shape[1] != 4 * H * W:
+        raise ValueError("%s: rpn_labels must be (B, %d), got %s" % (name, 4 * H * W, tuple(rpn_labels.shape)))
+    B, S = int(rpn_labels.shape[0]), int(roi_labels.numel())
+    if tuple(calib.shape) != (B, 4, 12):
+        raise ValueError("%s: calib must be (%d, 4, 12), got %s" % (name, B, tuple(calib.shape)))
+    if tuple(rois_bv.shape) != (S, 5) or tuple(rois_img.shape) != (S, 5):
+        raise ValueError("%s: rois_bv and rois_img must be (%d, 5), got %s and %s" % (name, S, tuple(rois_bv.shape), tuple(rois_img.shape)))
+    lists, host = [], []
+    for nm, v in (("ignore_bv", ignore_bv), ("ignore_img", ignore_img)):
+        if not _is_packed(v):
+            if len(v) != B:
+                raise ValueError("%s: %s holds %d frames, rpn_labels %d" % (name, nm, len(v), B))
+            if any(isinstance(a, torch.Tensor) for a in v):
+                v = [a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a for a in v]
+            v = pack_box_lists(v)
+        rows, off = v
+        if isinstance(rows, torch.Tensor) != isinstance(off, torch.Tensor):
+            raise ValueError("%s: %s rows and offsets must both be host arrays or both device tensors" % (name, nm))
+        if isinstance(rows, torch.Tensor):
+            if not (rows.is_cuda and off.is_cuda and rows.dtype == torch.float32 and off.dtype == torch.int32):
+                raise TypeError("%s: packed %s must be f32 rows and int32 offsets on the device" % (name, nm))
+            rows, off = rows.contiguous(), off.contiguous()
+        else:
+            rows, off = np.ascontiguousarray(rows, np.float32), np.ascontiguousarray(off, np.int32)
+            host += [len(lists)]
+        if rows.ndim != 2 or rows.shape[1] != 4 or off.shape[0] != B + 1:
+            raise ValueError("%s: %s must be (R, 4) rows and %d offsets, got %s and %s" % (name, nm, B + 1, tuple(rows.shape), tuple(off.shape)))
+        lists.append([rows, off])
+    if host:
+        up = iter(upload_packed([a for k in host for a in lists[k]], dev))
+        for k in host:
+            lists[k] = [next(up), next(up)]
+    rl, qb, qi, cal = rpn_labels.contiguous(), rois_bv.contiguous(), rois_img.contiguous(), calib.contiguous()
+    ql = roi_labels.contiguous()
+    if out is None:
+        out = (torch.empty_like(rl), torch.empty_like(ql), torch.empty((B, 2), dtype=torch.int32, device=dev) if want_counts else None,
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    o_rpn, o_roi, counts, status = out
+    if o_rpn.shape != rl.shape or o_roi.shape != ql.shape or o_rpn.dtype != rl.dtype or o_roi.dtype != ql.dtype or \
+            not (o_rpn.is_contiguous() and o_roi.is_contiguous()):
+        raise ValueError("%s: out does not fit the labels" % name)
+    (rb, ob), (ri, oi) = lists
+    with torch.cuda.device(dev):
+        check(lib().mv3d_ignore_relabel(_ptr(rl), _ptr(ql), _ptr(qb), _ptr(qi), S, _ptr(cal), B, H, W, int(feat_stride),
+                                        _ptr(rb) if rb.shape[0] else None, _ptr(ob), int(rb.shape[0]),
+                                        _ptr(ri) if ri.shape[0] else None, _ptr(oi), int(ri.shape[0]), C.c_double(float(overlap)),
+                                        _ptr(o_rpn), _ptr(o_roi), _ptr(counts), _ptr(status), _stream()), "mv3d_ignore_relabel")
+    return o_rpn, o_roi, counts, status
 
 
 

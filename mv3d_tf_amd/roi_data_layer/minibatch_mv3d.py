@@ -18,12 +18,14 @@ im_info = (601, 601, 1); with both keys on the scan is read and uploaded once fo
 cfg.LIDAR_CROP_TO_IMAGE (not in the reference; default off; needs LIDAR_BV_FROM_SCAN) crops every scan uploaded here to the points
 inside the frame's own image before either raster reads it: see `_device_cloud`.  In-memory 'lidar_bv' / 'lidar_fv' maps are the
 caller's and stay as they are.
-cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`."""
+cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`.
+cfg.TRAIN.IGNORE_TYPES (not in the reference; default () = the blobs above exactly) adds the frame's ignore regions, `ignore_boxes_bv`
+(K,4) and `ignore_boxes_img` (M,4) f32 host arrays (datasets.kitti_mv3d.ignore_blobs); the roidb must have been parsed under the key."""
 import numpy as np
 import numpy.random as npr
 
 from .. import ops
-from ..datasets.kitti_mv3d import gt_blobs
+from ..datasets.kitti_mv3d import gt_blobs, ignore_blobs
 from ..fast_rcnn.config import cfg
 from ..utils.read_image import read_image_bgr
 
@@ -129,4 +131,6 @@ def get_minibatch(roidb, num_classes):
         if cloud is None and 'lidar_fv' not in entry and ops.scan_crop():      # (an in-memory 'lidar_bv': the scan was not uploaded above)
             cloud, offsets = _device_cloud(entry, 'FRONT_VIEW_INPUT', 'lidar_fv', image)
         blobs['lidar_fv_data'] = front_view_blob(entry, cloud, offsets)
+    if cfg.TRAIN.get('IGNORE_TYPES', ()):
+        blobs.update(ignore_blobs(entry))
     return blobs
