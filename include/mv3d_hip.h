@@ -586,6 +586,31 @@ int mv3d_scan_crop_to_image(const float *points_dev, const int32_t *offsets_dev,
                             const float *calib_dev, const int32_t *image_hw_dev, float *points_out_dev, int32_t *offsets_out_dev,
                             void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------ scan augmentation (csrc/scan_transform.hip)
+ * A similarity transform of the LIDAR frame per cloud -- a rotation about the vertical axis, a uniform scale, a shift, A = [s R | t]
+ * -- on `num_frames` clouds back to back, in front of the crop and the rasterisers above (cfg.TRAIN.SCAN_AUGMENT; the annotation and
+ * the calibration follow on the host, mv3d_tf_amd/datasets/augment.py).  PARITY UNPINNED: the reference trains from stored maps and
+ * has no such code; tests/scan_augment_restatement.py states the rule.
+ *   points_dev      (total_points, 4) f32 [x, y, z, reflectance], the frames' clouds concatenated, 16-byte aligned
+ *   offsets_dev     (num_frames + 1) int32 ON THE DEVICE, mv3d_point_cloud_2_front's rule: frame b owns rows offsets[b] .. offsets[b + 1];
+ *                   rows no frame owns -- in front of offsets[0], behind offsets[num_frames], anything under offsets that do not
+ *                   ascend -- are copied as they are.  NULL with num_frames == 1: the one frame owns every row.
+ *   xform_dev       (num_frames, 12) f64 ON THE DEVICE, 8-byte aligned: per frame the 3x4 matrix A, row-major.  Any twelve numbers
+ *                   are taken as they are; the entry does not ask for a similarity.
+ *   points_out_dev  (total_points, 4) f32, 16-byte aligned: points_dev itself (in place) or a buffer with no byte in common with it
+ * A row [x, y, z, r] of frame b with finite x, y, z becomes c'_i = (float)fma(A[i][3], 1, fma(A[i][2], z, fma(A[i][1], y,
+ * fma(A[i][0], x, 0)))) in f64, i = 0, 1, 2, and r bit for bit (a NaN reflectance keeps its payload).  A row with a non-finite
+ * coordinate is copied, all 16 bytes bit for bit: the rasterisers and the crop drop it as they drop it untransformed.  Every row of
+ * [0, total_points) is written.
+ * No value in offsets_dev or xform_dev can make the call read or write out of bounds.  One launch on `stream`, one thread per row; no
+ * allocation, no host synchronisation, nothing read back; capturable, and a replay may find other clouds, other device offsets and
+ * other matrices in the same buffers (total_points, the capacity, fixes the grid).  num_frames == 0 and total_points == 0 return
+ * MV3D_OK without a launch.  MV3D_ERR_INVALID_ARG before any launch: num_frames outside [0, MV3D_FV_MAX_FRAMES], negative
+ * total_points, NULL or misaligned pointers (points and output may be NULL with total_points == 0), offsets_dev == NULL with
+ * num_frames != 1, points_out_dev overlapping points_dev without being equal to it. */
+int mv3d_scan_transform(const float *points_dev, const int32_t *offsets_dev, int num_frames, int total_points,
+                        const double *xform_dev, float *points_out_dev, void *stream);
+
 /* ------------------------------------------------------------------ the target layers' random subsamplings (HOST code)
  * The reference subsamples with `npr.choice(inds, size=k, replace=False)` on the numpy GLOBAL legacy RandomState
  * (lib/rpn_msr/anchor_target_layer_tf.py:146-159,178-183; lib/rpn_msr/proposal_target_layer_tf.py:246-269) = 

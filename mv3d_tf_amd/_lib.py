@@ -213,6 +213,7 @@ _SIGS = {
     "mv3d_scan_crop_workspace": (C.c_size_t, [C.c_int]),
     "mv3d_scan_crop_tile_rows": (C.c_int, []),
     "mv3d_scan_crop_to_image": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "mv3d_scan_transform": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "mv3d_box_detect_tail": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "mv3d_detect_post_workspace_bytes": (C.c_size_t, [C.c_int, C.POINTER(DetectPostParams)]),
     "mv3d_detect_post": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.POINTER(DetectPostParams), _P, _P, _P, _P, _P, _P, _P, C.c_size_t,

@@ -59,7 +59,20 @@ cfg.TRAIN = _section(
     # (ops.ignore_relabel) and both stages' losses skip it.  The sample slot is spent, not redrawn; the numpy
     # RNG stream of the draws is the key-off stream.  () = the reference.  The documented KITTI setting is ('Van', 'DontCare').  A type
     # outside KITTI's vocabulary or a trained class raises ValueError (check_ignore_types below).  No accuracy claim.
-    IGNORE_TYPES=(), IGNORE_OVERLAP=0.5)
+    IGNORE_TYPES=(), IGNORE_OVERLAP=0.5,
+    # (not in the reference, whose stored lidar_bv/*.npy maps cannot be rotated; needs cfg.LIDAR_BV_FROM_SCAN) SCAN_AUGMENT: every visit
+    # of a training frame draws a similarity transform A of the LIDAR frame -- a rotation about the vertical axis by theta in
+    # [-SCAN_AUGMENT_ROTATION, SCAN_AUGMENT_ROTATION) radians, a uniform scale in SCAN_AUGMENT_SCALE = (lo, hi), a shift by (dx, dy, dz)
+    # with |d| below SCAN_AUGMENT_SHIFT metres per axis -- from a generator of datasets/augment.py's own (seeded RNG_SEED + rank; the
+    # numpy RNG stream of the target layers' draws is the key-off stream).  The uploaded scan is transformed on the device in front of
+    # the crop and the rasters (ops.scan_transform), Tr_velo_to_cam takes A^-1, so the image and every
+    # camera-frame quantity stay as they are, and the LIDAR-frame ground truth and ignore regions follow A
+    # (datasets.augment.augment_annotation).  The mirror (USE_FLIPPED) composes with it.  The test-time loops never augment.  The
+    # default ranges (10 degrees, 5 % scale, no shift) are a guess that nothing here can validate: parity unpinned, no accuracy
+    # claim.  On without LIDAR_BV_FROM_SCAN, or with a scale bound <= 0, prepare_roidb raises ValueError (ops.scan_augment).
+    # False = every blob, launch and RNG stream as before.
+    SCAN_AUGMENT=False, SCAN_AUGMENT_ROTATION=0.17453292519943295, SCAN_AUGMENT_SCALE=(0.95, 1.05),
+    SCAN_AUGMENT_SHIFT=(0.0, 0.0, 0.0))
 cfg.TEST = _section(
     NMS=0.5, HAS_RPN=True, RPN_NMS_THRESH=0.7, RPN_PRE_NMS_TOP_N=12000, RPN_POST_NMS_TOP_N=2000, RPN_MIN_SIZE=5,
     DEBUG_TIMELINE=False,

@@ -237,6 +237,9 @@ class SolverWrapper(object):
         shard = list(sharding.frame_shard(len(self.roidb), rank, world)) or [rank % len(self.roidb)]   # (fewer frames than ranks:
         roidb = self.roidb if world == 1 else [self.roidb[i] for i in shard]        # wrap around -- no rank may sit out a collective)
         data_layer = get_data_layer(roidb, self.imdb.num_classes)
+        if cfg.TRAIN.get('SCAN_AUGMENT', False):               # the augmentation's own draw stream, one per rank (never numpy's global one)
+            from ..datasets import augment
+            augment.seed(cfg.RNG_SEED + rank)
         if self.pretrained_model is not None:
             self.log('Loading pretrained model weights from {:s}'.format(self.pretrained_model))
             self.net.load(self.pretrained_model, sess, self.saver, True)

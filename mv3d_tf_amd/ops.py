@@ -968,6 +968,70 @@ def scan_crop_to_image(points, offsets, calib, image_hw, out=None, offsets_out=N
     return out, offsets_out
 
 
+def scan_augment():
+    """cfg.TRAIN.SCAN_AUGMENT checked: True where training transforms its scans (scan_transform, datasets/augment.py); on without
+    cfg.LIDAR_BV_FROM_SCAN raises ValueError (a stored lidar_bv/*.npy map cannot be rotated), as does a scale bound <= 0 or any
+    other range datasets.augment.check_config refuses.  prepare_roidb calls it before the first step."""
+    from .datasets.augment import check_config
+    return check_config()
+
+
+def scan_transform(points, offsets, xform, out=None):
+    """Scan augmentation's transform of the points (csrc/scan_transform.hip; parity unpinned, the definition
+    is tests/scan_augment_restatement.py): B clouds back to back -> the (P,4) f32 device tensor of their rows, a row [x, y, z, r] of
+    frame b with finite x, y, z taken to A_b . [x, y, z, 1] (one f64 fma chain per coordinate, rounded to f32 once) and r kept bit for
+    bit.  A row with a non-finite coordinate and a row no frame owns come back as the same bits.
+    points, offsets as ops.point_cloud_2_front takes them (offsets None: one frame of every row).  xform = (B,3,4) or (B,12) f64, per
+    frame the matrix A of datasets.augment.transform_matrix (a numpy array, which is uploaded, or a device tensor).
+    out = None allocates the result; out = points (the same device tensor) transforms in place; any other out must be a contiguous
+    (P,4) f32 device tensor, 16-byte aligned, with no byte in common with points.  With device inputs and out given the call
+    allocates nothing and can be captured, and a replay may find other clouds, offsets and matrices in the same buffers.  Every
+    argument is checked before anything is uploaded, allocated or launched: TypeError for a wrong dtype, ValueError for a wrong
+    shape, value or device.  Under malformed device offsets the call stays inside its buffers (include/mv3d_hip.h)."""
+    fn = "scan_transform"
+    table = None
+
+    def more(B, P, dev):
+        nonlocal table
+        if isinstance(xform, torch.Tensor):
+            if xform.dtype != torch.float64:
+                raise TypeError("{}: an xform tensor must be float64, got {}".format(fn, xform.dtype))
+            table = xform
+        else:
+            table = np.asarray(xform)
+            if table.dtype != np.float64:
+                raise TypeError("{}: xform must be float64, got {}".format(fn, table.dtype))
+        if tuple(table.shape) not in ((B, 3, 4), (B, 12)):
+            raise ValueError("{}: xform must be ({}, 3, 4) or ({}, 12), one matrix per frame, got {}".format(fn, B, B, tuple(table.shape)))
+        # (a numpy cloud with no tensor beside it goes to the current device)
+        here = lambda t: t.is_cuda and t.device == (dev if isinstance(dev, torch.device) else torch.device("cuda", torch.cuda.current_device()))
+        if isinstance(table, torch.Tensor) and not here(table):
+            raise ValueError("{}: xform on {}: every tensor must live on one HIP device".format(fn, table.device))
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32:
+                raise TypeError("{}: out must be a {} tensor".format(fn, torch.float32))
+            if tuple(out.shape) != (P, 4) or not out.is_contiguous():
+                raise ValueError("{}: out must be contiguous {}, got {}".format(fn, (P, 4), tuple(out.shape)))
+            if not here(out):
+                raise ValueError("{}: out on {}: every tensor must live on one HIP device".format(fn, out.device))
+            if out.data_ptr() % 16:
+                raise ValueError("{}: out must be 16-byte aligned".format(fn))
+            if isinstance(points, torch.Tensor) and P and out.data_ptr() != points.data_ptr() and \
+                    out.data_ptr() < points.data_ptr() + 16 * P and points.data_ptr() < out.data_ptr() + 16 * P:
+                raise ValueError("{}: out must be points itself or not overlap it".format(fn))
+            if isinstance(points, torch.Tensor) and out.data_ptr() == points.data_ptr() and P and not points.is_contiguous():
+                raise ValueError("{}: points must be contiguous to be transformed in place".format(fn))
+
+    pts, off, B, P, _, dev = _scan_args(fn, points, offsets, None, None, more=more)
+    if pts.data_ptr() % 16:
+        raise ValueError("{}: points must be 16-byte aligned".format(fn))
+    A = (table if isinstance(table, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(table)).to(pts.device)).contiguous()
+    if out is None:
+        out = torch.empty((P, 4), dtype=torch.float32, device=pts.device)
+    check(lib().mv3d_scan_transform(_ptr(pts), _ptr(off), B, P, _ptr(A), _ptr(out), _stream()), "mv3d_scan_transform")
+    return out
+
+
 def gt_encode(box_cam, cos_sin, inv_rot, tr):
     """box_cam (G,6) f32, cos_sin (G,2) f64, inv_rot (9) f32, tr (12) f32 device tensors -> (corners_cam (G,24),
     corners_lidar (G,24), boxes_3d (G,6), boxes_bv (G,4)) f32 in ONE buffer (pack, views): a host caller fetches it with

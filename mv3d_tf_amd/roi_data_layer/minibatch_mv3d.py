@@ -20,11 +20,15 @@ inside the frame's own image before either raster reads it: see `_device_cloud`.
 caller's and stay as they are.
 cfg.IMAGE_BLOB_ON_DEVICE (not in the reference; default off) builds `image_data` on the device: see `image_blob`.
 cfg.TRAIN.IGNORE_TYPES (not in the reference; default () = the blobs above exactly) adds the frame's ignore regions, `ignore_boxes_bv`
-(K,4) and `ignore_boxes_img` (M,4) f32 host arrays (datasets.kitti_mv3d.ignore_blobs); the roidb must have been parsed under the key."""
+(K,4) and `ignore_boxes_img` (M,4) f32 host arrays (datasets.kitti_mv3d.ignore_blobs); the roidb must have been parsed under the key.
+cfg.TRAIN.SCAN_AUGMENT (not in the reference; default off = the blobs above exactly; needs LIDAR_BV_FROM_SCAN) draws a similarity
+transform of the LIDAR frame at every call and returns the blobs of the transformed frame, plus `scan_transform`, its (3,4) f64
+matrix: see `_augmented`."""
 import numpy as np
 import numpy.random as npr
 
 from .. import ops
+from ..datasets import augment
 from ..datasets.kitti_mv3d import gt_blobs, ignore_blobs
 from ..fast_rcnn.config import cfg
 from ..utils.read_image import read_image_bgr
@@ -47,13 +51,17 @@ def _entry_cloud(entry, key, own_map):
     return pts
 
 
-def _device_cloud(entry, key, own_map, image):
+def _device_cloud(entry, key, own_map, image, xform=None):
     """(points, offsets) of a roidb entry's scan on the device, what the rasterisers take: `_entry_cloud` uploaded once, offsets None
     = one frame of every row.  Under cfg.LIDAR_CROP_TO_IMAGE the upload is cropped (ops.scan_crop_to_image) to the points the entry's
     calibration table puts inside `image`, the frame's own (h, w, 3) pixels: offsets is then the crop's (2,) device tensor, and the
     rows of `points` behind offsets[1] belong to no frame.  A `flipped` entry's cloud, y negated, is cropped with the entry's own,
-    mirrored table; at the image border that need not be the mirror of the source frame's crop."""
+    mirrored table; at the image border that need not be the mirror of the source frame's crop.  xform = the (3,4) f64 matrix of
+    cfg.TRAIN.SCAN_AUGMENT: the upload is transformed in place (ops.scan_transform) in front of the crop, which `entry`, the augmented
+    one, then judges with its own table."""
     cloud = ops._dev(_entry_cloud(entry, key, own_map))
+    if xform is not None:
+        ops.scan_transform(cloud, None, np.asarray(xform, np.float64).reshape(1, 3, 4), out=cloud)
     if ops.scan_crop():
         return ops.scan_crop_to_image(cloud, None, [entry['calib']], [np.shape(image)])
     return cloud, None
@@ -93,13 +101,36 @@ def image_blob(entry, image):
     return ops.image_blob([image], canvas=cfg.IMAGE_CANVAS, flip=[bool(entry.get('flipped', False))])
 
 
+_FRAME_DATA = ('image', 'velodyne', 'lidar_bv', 'lidar_fv')        # a frame carried in memory: arrays that no annotation transform copies
+
+
+def _augmented(entry):
+    """(cfg.TRAIN.SCAN_AUGMENT) one draw of datasets.augment -> (the roidb entry of the transformed frame, A): the LIDAR-frame ground
+    truth and ignore regions follow the (3,4) f64 matrix A, `calib` carries A^-1 in Tr_velo_to_cam, every other field -- the frame's
+    files and in-memory arrays, the camera-frame fields, `flipped` -- is the entry's own.  `entry` is not modified.  The draw comes
+    from the module's own generator, never from numpy's global one.  An entry that carries a 'lidar_bv' or 'lidar_fv' map raises
+    ValueError: that map is the caller's and cannot be transformed."""
+    for k in ('lidar_bv', 'lidar_fv'):
+        if k in entry:
+            raise ValueError("cfg.TRAIN.SCAN_AUGMENT is on and the roidb entry carries an in-memory '{}' map, which cannot be "
+                             "transformed: give the frame's scan ('velodyne' or 'velodyne_path')".format(k))
+    theta, scale, shift = augment.draw_scan_transform()
+    A, A_inv = augment.transform_matrix(theta, scale, shift)
+    out = dict(entry)
+    out.update(augment.augment_annotation({k: v for k, v in entry.items() if k not in _FRAME_DATA}, A, scale))
+    out['calib'] = augment.augment_calib(entry['calib'], A_inv)
+    return out, A
+
+
 def get_minibatch(roidb, num_classes):
     num_images = len(roidb)
     npr.randint(0, high=len(cfg.TRAIN.SCALES), size=num_images)          # RNG-stream parity (:22-23)
     assert cfg.TRAIN.BATCH_SIZE % num_images == 0, \
         'num_images ({}) must divide BATCH_SIZE ({})'.format(num_images, cfg.TRAIN.BATCH_SIZE)
     assert num_images == 1, "Single batch only"
-    entry = roidb[0]
+    entry, xform = roidb[0], None
+    if cfg.TRAIN.get('SCAN_AUGMENT', False) and ops.scan_augment():
+        entry, xform = _augmented(entry)
     image = entry['image'] if 'image' in entry else read_image_bgr(entry['image_path'])
     on_device = bool(cfg.IMAGE_BLOB_ON_DEVICE)              # then image_data is final here: built, and mirrored, by ops.image_blob
     image_data = image_blob(entry, image) if on_device else (image.astype(np.float32, copy=True) - cfg.PIXEL_MEANS)[None].astype(np.float32)
@@ -108,7 +139,7 @@ def get_minibatch(roidb, num_classes):
         # no stored map: the scan is uploaded once (a mirrored frame's with y negated, whose raster IS the column-reversed map:
         # tests/test_mirror.py::test_bev_raster_commutes_with_the_mirror), cropped to the image under cfg.LIDAR_CROP_TO_IMAGE, and
         # rasterised on the device
-        cloud, offsets = _device_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv', image)
+        cloud, offsets = _device_cloud(entry, 'LIDAR_BV_FROM_SCAN', 'lidar_bv', image, xform)
         bev = ops.scan_bev(cloud, offsets)
         blobs = {'image_data': image_data, 'lidar_bv_data': bev.reshape((1,) + tuple(bev.shape[-3:])), 'calib': entry['calib']}
         blobs.update(gt_blobs(entry, ops.BEV_SHAPE))
@@ -133,4 +164,6 @@ def get_minibatch(roidb, num_classes):
         blobs['lidar_fv_data'] = front_view_blob(entry, cloud, offsets)
     if cfg.TRAIN.get('IGNORE_TYPES', ()):
         blobs.update(ignore_blobs(entry))
+    if xform is not None:
+        blobs['scan_transform'] = xform                      # for the record: nothing downstream reads it
     return blobs

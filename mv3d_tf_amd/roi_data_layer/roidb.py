@@ -2,8 +2,8 @@
 lib/roi_data_layer/roidb.py:15-60): file paths, the (4,12) calibration table, and per-object max overlap / class taken from
 the one-hot `gt_overlaps`.  cfg.LIDAR_BV_FROM_SCAN (not in the reference): no `lidar_bv_path` is recorded and imdb.lidar_path_at is not
 called -- the data layer rasterises the map from `velodyne_path`, which the imdb must then be able to name.
-cfg.LIDAR_BV_ENCODING and cfg.LIDAR_CROP_TO_IMAGE are checked first (ops.bev_encoding, ops.scan_crop): 'paper' and the crop need
-LIDAR_BV_FROM_SCAN."""
+cfg.LIDAR_BV_ENCODING, cfg.LIDAR_CROP_TO_IMAGE and cfg.TRAIN.SCAN_AUGMENT are checked first (ops.bev_encoding, ops.scan_crop,
+ops.scan_augment): 'paper', the crop and the augmentation need LIDAR_BV_FROM_SCAN."""
 import numpy as np
 
 from .. import ops
@@ -13,6 +13,7 @@ from ..fast_rcnn.config import cfg
 def prepare_roidb(imdb):
     ops.bev_encoding()                                         # cfg.LIDAR_BV_ENCODING: 'paper' without LIDAR_BV_FROM_SCAN, or an unknown value, raises
     ops.scan_crop()                                            # cfg.LIDAR_CROP_TO_IMAGE without LIDAR_BV_FROM_SCAN raises
+    ops.scan_augment()                                         # cfg.TRAIN.SCAN_AUGMENT without LIDAR_BV_FROM_SCAN, or with a bad range, raises
     from_scan = bool(cfg.LIDAR_BV_FROM_SCAN)
     if from_scan and not hasattr(imdb, 'velodyne_path_at'):
         raise ValueError("cfg.LIDAR_BV_FROM_SCAN is on and the imdb has no velodyne_path_at(i) to name the scans the bird's-eye-view "
