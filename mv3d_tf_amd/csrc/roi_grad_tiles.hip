@@ -46,7 +46,7 @@
 
 #define RGT_MAXPX 16
 #define RGT_RING 256                 // ring entries: a chunk of bins appends <= 240 (60 bins x 4 rows | 64 x 2), < 16 are left over from the last drain
-#define RGT_BIGBIT 0x100             // entry word 0: the bin has more than 255 pixels (16-bit codes in the escape plane)
+#define RGT_BIGBIT 0x100             // entry word 0: roi_rect_wide -- the bin has more than 255 pixels (16-bit codes in the escape plane)
 #define RGT_EXACT_MAX 2048           // ROI extents (map pixels) up to which "forward rectangle inside backward range" is proven exhaustively
 
 #ifdef MV3D_TUNING
@@ -209,8 +209,8 @@ __device__ __forceinline__ int2 rgt_exact_span(const int lo, const int hi, const
 {
     int a = INT_MAX, b = INT_MIN;                                      // (an empty [lo, hi] stays empty)
     for (int x = lo; x <= hi; ++x) {
-        const int s = min(max((int)floorf((float)(x - start) / bin), 0), P), e = min(max((int)ceilf((float)(x - start + 1) / bin), 0), P);
-        if (s <= p && p < e) { a = min(a, x); b = max(b, x); }
+        const RoiSpan r = roi_pixel_bins(x, start, bin, P);
+        if (r.s <= p && p < r.e) { a = min(a, x); b = max(b, x); }
     }
     return make_int2(a, b);
 }
@@ -242,9 +242,7 @@ __global__ __launch_bounds__(64) RGT_OCC void roi_pair_tiles_kernel(RgtPack p)
         if (k >= p.n || ths > 2 || tws > 2 || b >= p.v[k].B || (unsigned)th0 >= (unsigned)p.v[k].H || (unsigned)tw0 >= (unsigned)p.v[k].W) return;
 #endif
     } else {
-#pragma unroll
-        for (int j = 1; j < MV3D_MAX_ROI_VIEWS; ++j)
-            if (j < p.n && blockIdx.x >= p.v[j].first_block) k = j;
+        k = roi_view_of(blockIdx.x, p.n, [&](int j) { return p.v[j].first_block; });
         const RgtView &u = p.v[k];
         const unsigned lb = blockIdx.x - u.first_block;
         slice = (int)(lb % (unsigned)u.nsl);
@@ -311,6 +309,8 @@ __global__ __launch_bounds__(64) RGT_OCC void roi_pair_tiles_kernel(RgtPack p)
             if (RGT_DBG(p.dbg, 1)) todo = 0ull;
             // the bin sizes of this pass's ROIs, lane = ROI (roi_pooling_op.cc:148-151): one pair of f32 divides per pass with a hit instead of
             // one per hit ROI (a wave that got past the work list's empty flag usually has many)
+            // (roi_extent without its forced minimum of 1: the filter drops the ROIs with an end before their start, and only hit ROIs'
+            // sizes are read)
             float bhl = 0.0f, bwl = 0.0f;
             if (todo != 0ull) {
                 bhl = (float)(g.reh - g.rsh + 1) / (float)PH;
@@ -335,11 +335,9 @@ __global__ __launch_bounds__(64) RGT_OCC void roi_pair_tiles_kernel(RgtPack p)
                         ph = (int)(((unsigned)bin * (unsigned)p.inv_pw) >> 16); pw = bin - ph * PW;
                         fph0 = (float)ph; fph1 = (float)(ph + 1); fpw0 = (float)pw; fpw1 = (float)(pw + 1);
                     }
-                    // the bin's rectangle as the forward computes it (roi_pool.hip fwd_bin_rect, roi_pooling_op.cc:153-162)
-                    const int hs0 = (int)floorf(__fmul_rn(fph0, bh)), ws0 = (int)floorf(__fmul_rn(fpw0, bw));
-                    const int he0 = (int)ceilf(__fmul_rn(fph1, bh)), we0 = (int)ceilf(__fmul_rn(fpw1, bw));
-                    const int hs = min(max(hs0 + rsh, 0), H), he = min(max(he0 + rsh, 0), H);
-                    const int ws = min(max(ws0 + rsw, 0), Wd), we = min(max(we0 + rsw, 0), Wd);
+                    // the bin's rectangle as the forward computes it (roi_geom.h: roi_bin_rect's two spans, roi_pooling_op.cc:153-162)
+                    const RoiSpan rows = roi_bin_span(fph0, fph1, bh, rsh, H), cols = roi_bin_span(fpw0, fpw1, bw, rsw, Wd);
+                    const int hs = rows.s, he = rows.e, ws = cols.s, we = cols.e;
                     // (rectangle x tile), cut to the rounded ROI: hs >= rsh and ws >= rsw hold by construction
                     int ih0 = max(hs, th0), ih1 = min(min(he, th1) - 1, reh), iw0 = max(ws, tw0), iw1 = min(min(we, tw1) - 1, rew);
                     if (exact && bin < PHW && he > hs && we > ws) {
@@ -349,7 +347,7 @@ __global__ __launch_bounds__(64) RGT_OCC void roi_pair_tiles_kernel(RgtPack p)
                     const bool meets = bin < PHW && he > hs && we > ws && ih1 >= ih0 && iw1 >= iw0;
                     if (__ballot(meets) == 0ull) continue;
                     const int bwid = we - ws;
-                    const int ex = (((r * PHW + bin) * C) * 4) | (iw0 - tw0) | ((iw1 - iw0) << 4) | ((he - hs) * bwid > 255 ? RGT_BIGBIT : 0);
+                    const int ex = (((r * PHW + bin) * C) * 4) | (iw0 - tw0) | ((iw1 - iw0) << 4) | (roi_rect_wide(he - hs, bwid) ? RGT_BIGBIT : 0);
                     const int ey = (iw0 - ws) - hs * bwid;
                     // ---- one entry per row of the tile a bin's rectangle meets, bins outermost (ph, pw order), a bin's rows in turn: a pixel
                     // meets at most one row segment of a bin, so every pixel still sees its bins in the reference's order.  Positions by ONE

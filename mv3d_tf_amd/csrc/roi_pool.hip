@@ -55,26 +55,17 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float *__restri
         const int pw = (int)(t % PW); t /= PW;
         const int ph = (int)(t % PH);
         const int n = (int)(t / PH);
-        const float *roi = rois + 5 * n;
-        const int bi = (int)roi[0];
-        const RoiGeom g = roi_geom(roi, scale);
-        const int rw = max(g.rew - g.rsw + 1, 1), rh = max(g.reh - g.rsh + 1, 1);   // :146-147
-        const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;        // :148-151
-        int hs = (int)floorf(__fmul_rn((float)ph, bh)), ws = (int)floorf(__fmul_rn((float)pw, bw));
-        int he = (int)ceilf(__fmul_rn((float)(ph + 1), bh)), we = (int)ceilf(__fmul_rn((float)(pw + 1), bw));
-        hs = min(max(hs + g.rsh, 0), H); he = min(max(he + g.rsh, 0), H);          // :159-162
-        ws = min(max(ws + g.rsw, 0), W); we = min(max(we + g.rsw, 0), W);
-        const bool bad_batch = (bi < 0 || bi >= B);
-        const bool empty = (he <= hs) || (we <= ws) || bad_batch;
+        const BinGeom g = roi_bin_rect(rois + 5 * n, ph, pw, scale, B, H, W, PH, PW);
+        const bool empty = g.base < 0;
         const int c0 = cv * VEC;
         float mv[VEC];
         int mi[VEC];
 #pragma unroll
         for (int v = 0; v < VEC; ++v) { mv[v] = empty ? 0.0f : -FLT_MAX; mi[v] = -1; }
         if (!empty) {
-            const float *d = data + (long long)bi * H * W * C;
-            for (int h = hs; h < he; ++h)
-                for (int w = ws; w < we; ++w) {
+            const float *d = data + (long long)g.base * H * W * C;
+            for (int h = g.hs; h < g.he; ++h)
+                for (int w = g.ws; w < g.we; ++w) {
                     const int idx = (h * W + w) * C + c0;
                     if (VEC == 4) {
                         const float4 x = *reinterpret_cast<const float4 *>(d + idx);
@@ -108,7 +99,6 @@ __global__ __launch_bounds__(256) void roi_pool_fwd_kernel(const float *__restri
 // while the overlapping bins of neighbouring ROIs re-read it.  The bin geometry (f32 divides,
 // round / floor / ceil) is computed once per bin by the first lanes and broadcast through LDS.
 #define LDS_FENCE() __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup", "local")
-struct BinGeom { int hs, he, ws, we; int base; int pad0, pad1, pad2; };   // base < 0: empty / bad batch index
 
 __device__ __forceinline__ void upd4pos(const float4 x, int pos, float4 &mv, int4 &mi)
 {
@@ -131,29 +121,12 @@ __device__ __forceinline__ void upd4max(const float4 x, float4 &mv)
 //   bins of <= 255 pixels (every bin of a ROI smaller than ~100 x 100 feature pixels): ONE BYTE per pooled value, 0xFF = "none"
 //       (the reference's -1), in the byte plane at the front of the caller's argmax buffer, [0, N), N = R * PH * PW * C;
 //   larger bins (ROIs far larger than the map): 16-bit codes, 0xFFFF = none, in the escape plane behind it, bytes [N, 3 N).
-// Which plane a bin uses follows from its geometry alone, so the gradient (roi_grad_tiles.hip) knows it too.  3 / 8 of the pair's
+// Which plane a bin uses follows from its geometry alone (roi_geom.h, roi_bin_wide), so the gradient (roi_grad_tiles.hip) knows it too.  3 / 8 of the pair's
 // record bytes (8 -> 5 B per pooled value) are neither written here nor read by the gradient; a code names the pixel inside its
 // bin, so the gradient finds the pixel a value goes to (roi_pooling_op.cc:433) without the reference's flat index.
 // mv3d_roi_pool_argmax_decode gives the reference's plane back (tests, bench).
-// the rectangle of bin (ph, pw) of the ROI row rr[5] as roi_pooling_op.cc:139-162 computes it
-__device__ __forceinline__ BinGeom fwd_bin_rect(const float rr[5], const int ph, const int pw, const float scale, const int B, const int H, const int W,
-                                                const int PH, const int PW)
-{
-    BinGeom g;
-    g.pad0 = g.pad1 = g.pad2 = 0;
-    const int bi = (int)rr[0];
-    const RoiGeom q = roi_geom(rr, scale);
-    const int rw = max(q.rew - q.rsw + 1, 1), rh = max(q.reh - q.rsh + 1, 1);   // roi_pooling_op.cc:146-147
-    const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;        // :148-151
-    int hs = (int)floorf(__fmul_rn((float)ph, bh)), ws = (int)floorf(__fmul_rn((float)pw, bw));
-    int he = (int)ceilf(__fmul_rn((float)(ph + 1), bh)), we = (int)ceilf(__fmul_rn((float)(pw + 1), bw));
-    g.hs = min(max(hs + q.rsh, 0), H); g.he = min(max(he + q.rsh, 0), H);      // :159-162
-    g.ws = min(max(ws + q.rsw, 0), W); g.we = min(max(we + q.rsw, 0), W);
-    const bool empty = (g.he <= g.hs) || (g.we <= g.ws) || bi < 0 || bi >= B;
-    g.base = empty ? -1 : bi;
-    return g;
-}
-// the rectangle of pooled bin `bin` (= (roi n, ph, pw) flattened)
+
+// the rectangle (roi_geom.h, roi_bin_rect) of pooled bin `bin` (= (roi n, ph, pw) flattened)
 __device__ __forceinline__ BinGeom fwd_bin_geom(const long long bin, const long long nbins, const float *__restrict__ rois, const float scale,
                                                 const int B, const int H, const int W, const int PH, const int PW)
 {
@@ -171,7 +144,7 @@ __device__ __forceinline__ BinGeom fwd_bin_geom(const long long bin, const long 
         float rr[5];
 #pragma unroll
         for (int u = 0; u < 5; ++u) rr[u] = roi[u];
-        g = fwd_bin_rect(rr, ph, pw, scale, B, H, W, PH, PW);
+        g = roi_bin_rect(rr, ph, pw, scale, B, H, W, PH, PW);
     }
     return g;
 }
@@ -276,7 +249,7 @@ __device__ __forceinline__ void roi_pool_fwd_xcd_pool(const BinGeom *s_g, const 
             if (NOARG) {
             } else if (COMPACT) {
                 unsigned char *const plane8 = reinterpret_cast<unsigned char *>(argmax);
-                if (g.base < 0 || (g.he - g.hs) * (g.we - g.ws) <= 255) {      // four one-byte codes (-1 -> 0xFF), 4 bytes per lane
+                if (!roi_bin_wide(g)) {              // four one-byte codes (-1 -> 0xFF), 4 bytes per lane
                     const unsigned cv = ((unsigned)mi.x & 0xffu) | (((unsigned)mi.y & 0xffu) << 8) | (((unsigned)mi.z & 0xffu) << 16) | ((unsigned)mi.w << 24);
                     __builtin_nontemporal_store(cv, reinterpret_cast<unsigned *>(plane8 + o));
                 } else {                             // a bin of more than 255 pixels: four 16-bit codes in the escape plane
@@ -498,15 +471,11 @@ __global__ __launch_bounds__(256) void roi_pool_bwd_kernel(const float *__restri
                 const int rr = r0 + __builtin_ctzll(bal);
                 bal &= bal - 1;
                 const int4 g = s_geom[rr];
-                const int rw = max(g.z - g.x + 1, 1), rh = max(g.w - g.y + 1, 1);
-                const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
-                // :423-426 (identical to the CUDA form roi_pooling_op_gpu.cu.cc:169-172)
-                int phs = (int)floorf((float)(h - g.y) / bh), phe = (int)ceilf((float)(h - g.y + 1) / bh);
-                int pws = (int)floorf((float)(w - g.x) / bw), pwe = (int)ceilf((float)(w - g.x + 1) / bw);
-                phs = min(max(phs, 0), PH); phe = min(max(phe, 0), PH);
-                pws = min(max(pws, 0), PW); pwe = min(max(pwe, 0), PW);
+                const float bh = (float)roi_extent(g.y, g.w) / (float)PH, bw = (float)roi_extent(g.x, g.z) / (float)PW;
+                const RoiSpan pr = roi_pixel_bins(h, g.y, bh, PH), pc = roi_pixel_bins(w, g.x, bw, PW);
+                const int phs = pr.s, pws = pc.s;
                 const long long off = (long long)(base + rr) * PH * PW * C;
-                const int nw = pwe - pws, nbins = (phe - phs) * nw;    // <= PH * PW candidates, (ph, pw) order
+                const int nw = pc.e - pc.s, nbins = (pr.e - pr.s) * nw;    // <= PH * PW candidates, (ph, pw) order
                 for (int b0 = 0; b0 < nbins; b0 += 64) {
                     const int take = min(nbins - b0, 64);
                     if (ncand + take > BWD_CAND) {            // list full: drain it, in order
@@ -594,11 +563,61 @@ __device__ __forceinline__ float bwd_drain_records(const int *cand, const int t0
     return a;
 }
 
+// The ROI row filter of the sliced and the indexed body: the ROIs of one pass that have candidates for a row segment, in ROI order
+// (LDS).  Per entry: the ROI, its rounded columns, its pooled rows for the segment's map row (phs | phe << 8) and its bin width.
+struct RoiRowList {
+    int roi[BW_CHUNK], rsw[BW_CHUNK], rew[BW_CHUNK], prow[BW_CHUNK];
+    float bw[BW_CHUNK];
+    int wcnt[4];                     // survivors per wave
+};
+
+// Filters ROIs [pass * BW_CHUNK, + BW_CHUNK) of view v (thread = ROI; the whole 256-thread workgroup calls) for row h of frame n and
+// the columns [w0, w0 + npx): frame, row and column span (roi_pooling_op.cc:392-403, containment on the unclamped rounded ROI), the
+// f32 divides only for survivors, a non-empty pooled row range.  Compacts the survivors into L in ROI order (ballot, per-wave
+// counts) and returns their number.  Two barriers; the caller's own barrier in front keeps the previous list's readers out.
+__device__ __forceinline__ int roi_row_filter(RoiRowList &L, const RoiGradViewDev &v, const int PH, const int PW, const int pass, const int n,
+                                              const int h, const int w0, const int npx, const int lane, const int wave)
+{
+    const int r = pass * BW_CHUNK + (int)threadIdx.x;
+    bool ok = false;
+    int rsw = 0, rew = 0, prow = 0;
+    float bw = 1.0f;
+    if (r < v.R) {
+        const float *roi = v.rois + 5 * (long long)r;
+        const RoiGeom q = roi_geom(roi, v.scale);
+        ok = ((int)roi[0] == n) && h >= q.rsh && h <= q.reh && q.rew >= w0 && q.rsw < w0 + npx;
+        if (ok) {
+            const RoiSpan pr = roi_pixel_bins(h, q.rsh, (float)roi_extent(q.rsh, q.reh) / (float)PH, PH);
+            ok = pr.e > pr.s;
+            rsw = q.rsw; rew = q.rew; prow = pr.s | (pr.e << 8);
+            bw = (float)roi_extent(q.rsw, q.rew) / (float)PW;
+        }
+    }
+    const unsigned long long bal = __ballot(ok);
+    if (lane == 0) L.wcnt[wave] = __popcll(bal);
+    __syncthreads();
+    int pos = __popcll(bal & ((1ull << lane) - 1ull));
+    int nlist = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { const int t = L.wcnt[q]; if (q < wave) pos += t; nlist += t; }
+    if (ok) { L.roi[pos] = r; L.rsw[pos] = rsw; L.rew[pos] = rew; L.prow[pos] = prow; L.bw[pos] = bw; }
+    __syncthreads();
+    return nlist;
+}
+
+// x = the pooled columns of list entry e that may hold map column w (:423-431); false: none (w outside the ROI's rounded columns, or
+// an empty range)
+__device__ __forceinline__ bool roi_row_entry_cols(const RoiRowList &L, const int e, const int w, const int PW, RoiSpan &x)
+{
+    const int xs = L.rsw[e], xe = L.rew[e];
+    if (w < xs || w > xe) return false;
+    x = roi_pixel_bins(w, xs, L.bw[e], PW);
+    return x.e > x.s;
+}
+
 __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGradPack p)
 {
-    __shared__ int s_roi[BW_CHUNK], s_rsw[BW_CHUNK], s_rew[BW_CHUNK], s_prow[BW_CHUNK];
-    __shared__ float s_bw[BW_CHUNK];
-    __shared__ int s_wcnt[4];
+    __shared__ RoiRowList s_list;
     __shared__ int s_cand[4][BW_CAND];
     extern __shared__ float s_carry[];                   // [pxg][64] partial sums between ROI passes (only when R > BW_CHUNK)
     const RoiGradViewDev &v = p.v[roi_view_of(blockIdx.x, p.n, [&](int j) { return p.v[j].first_block; })];
@@ -622,35 +641,7 @@ __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGrad
     for (int pass = 0; pass < npass; ++pass) {
         // ---- pass part 1: ROIs of this frame that contain row h and touch the columns of the segment, in ROI order
         if (pass) __syncthreads();                         // the previous list is fully consumed
-        const int r = pass * BW_CHUNK + (int)threadIdx.x;
-        bool ok = false;
-        int rsw = 0, rew = 0, prow = 0;
-        float bw = 1.0f;
-        if (r < R) {
-            const float *roi = v.rois + 5 * (long long)r;
-            const RoiGeom q = roi_geom(roi, v.scale);
-            // roi_pooling_op.cc:392-403: batch match, containment on the unclamped rounded ROI
-            ok = ((int)roi[0] == n) && h >= q.rsh && h <= q.reh && q.rew >= w0 && q.rsw < w0 + npx;
-            if (ok) {
-                const int rh = max(q.reh - q.rsh + 1, 1), rw = max(q.rew - q.rsw + 1, 1);
-                const float bh = (float)rh / (float)PH;
-                // :423-426 (identical to the CUDA form roi_pooling_op_gpu.cu.cc:169-172)
-                int phs = (int)floorf((float)(h - q.rsh) / bh), phe = (int)ceilf((float)(h - q.rsh + 1) / bh);
-                phs = min(max(phs, 0), PH); phe = min(max(phe, 0), PH);
-                ok = phe > phs;
-                rsw = q.rsw; rew = q.rew; prow = phs | (phe << 8);
-                bw = (float)rw / (float)PW;
-            }
-        }
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) s_wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int pos = __popcll(bal & ((1ull << lane) - 1ull));
-        int nlist = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int t = s_wcnt[q]; if (q < wave) pos += t; nlist += t; }
-        if (ok) { s_roi[pos] = r; s_rsw[pos] = rsw; s_rew[pos] = rew; s_prow[pos] = prow; s_bw[pos] = bw; }
-        __syncthreads();
+        const int nlist = roi_row_filter(s_list, v, PH, PW, pass, n, h, w0, npx, lane, wave);
         const bool last = (pass == npass - 1);
         // ---- part 2: pixel j of the segment belongs to wave j % 4 (neighbouring, similarly loaded pixels spread over the
         // waves); one pixel at a time, one channel per lane
@@ -662,19 +653,12 @@ __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGrad
                 // lane i: entry e0 + i -> its candidate bins for pixel (h, w)
                 const int e = e0 + lane;
                 int nb = 0, phs = 0, pws = 0, nw = 1, rec0 = 0;
-                if (e < nlist) {
-                    const int xs = s_rsw[e], xe = s_rew[e];
-                    if (w >= xs && w <= xe) {
-                        const float fbw = s_bw[e];
-                        int x0 = (int)floorf((float)(w - xs) / fbw), x1 = (int)ceilf((float)(w - xs + 1) / fbw);
-                        x0 = min(max(x0, 0), PW); x1 = min(max(x1, 0), PW);
-                        if (x1 > x0) {
-                            const int pr = s_prow[e];
-                            phs = pr & 255; pws = x0; nw = x1 - x0;
-                            nb = ((pr >> 8) - phs) * nw;
-                            rec0 = s_roi[e] * PH * PW;
-                        }
-                    }
+                RoiSpan x;
+                if (e < nlist && roi_row_entry_cols(s_list, e, w, PW, x)) {
+                    const int pr = s_list.prow[e];
+                    phs = pr & 255; pws = x.s; nw = x.e - x.s;
+                    nb = ((pr >> 8) - phs) * nw;
+                    rec0 = s_list.roi[e] * PH * PW;
                 }
                 if (!__any(nb > 0)) continue;
                 int tot = nb;                                     // inclusive prefix over the lanes
@@ -691,7 +675,7 @@ __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGrad
                     if (ncand == 0) continue;
                     if (lane >= s0 && lane < s0 + step && nb > 0) {
                         int o = tot - nb - before;                // exclusive prefix inside the piece
-                        for (int ph = phs; ph < phs + nb / nw; ++ph)
+                        for (int ph = phs; ph < phs + (int)((unsigned)nb / (unsigned)nw); ++ph)     // (nb > 0, nw >= 1)
                             for (int pw = pws; pw < pws + nw; ++pw) cand[o++] = rec0 + ph * PW + pw;
                     }
                     LDS_FENCE();
@@ -731,30 +715,29 @@ __global__ __launch_bounds__(BW_THREADS) void roi_pool_bwd_sliced_kernel(RoiGrad
 // compact item list; a same-address global atomic costs ~20 ns however many workgroups issue it (1 k slab allocations =
 // 20 us) -> sizes and offsets in two launches instead; a wave that walks pixels one after the other behind LDS round trips
 // pays every pixel's memory round trips in sequence (the sliced kernel above: 102 us on the training batch).
-// Workspace: [0, 256) header {-, item count}, per-segment sizes (2 ints per 16-pixel segment), the item list (int4 per
-// pixel of all views), the candidate pool.  Pool bound per ROI: the sum over the rows of (phe - phs) is <= PH + 2 rows + 3
-// (floor / ceil slack), likewise over the columns.  Every word is written before it is read: no memset, no zero contract.
+// Workspace: [0, 256) header (word 1: the item count of the launch), per-segment sizes (one int per 16-pixel segment: candidates
+// << 5 | pixels that have any), the item list (int4 per pixel of all views), the candidate pool.  Pool bound per ROI: the sum over
+// the rows of (phe - phs) is <= PH + 2 rows + 3 (floor / ceil slack), likewise over the columns.  Every word is written before it
+// is read: no memset, no zero contract.
 #define BWI_PIX 16
 #define BWG_GROUPS 256                // gather grid = BWG_GROUPS x nsl workgroups of 4 waves (~ what the chip holds at once)
-#define BWI_SPIN_LIMIT (1 << 16)      // polls of one published word before a look-back gives up (and flags the index invalid)
 struct RoiGradIdxPack {
     long long *trace; int4 *items; int *pool; int *header;
-    int *seg_tot, *seg_mask;                         // per 16-pixel segment: candidates, 16-bit mask of the pixels that have any
+    int *seg_tot;                                    // per 16-pixel segment: candidates << 5 | pixels that have any
     unsigned first_block[MV3D_MAX_ROI_VIEWS]; int gpr[MV3D_MAX_ROI_VIEWS];
 };
 
 // LDS of one index workgroup
 struct RoiIdxShared {
     int red[8];
-    int roi[BW_CHUNK], rsw[BW_CHUNK], rew[BW_CHUNK], prow[BW_CHUNK];
-    float bw[BW_CHUNK];
+    RoiRowList list;
     unsigned char nb[BW_CHUNK][BWI_PIX], xr[BW_CHUNK][BWI_PIX];
-    int wcnt[4], cnt[BWI_PIX], base[BWI_PIX], run[BWI_PIX];
+    int cnt[BWI_PIX], base[BWI_PIX], run[BWI_PIX];
     int part[16][BWI_PIX];
 };
 
 // One index workgroup = one 16-pixel segment of a map row.
-// FILL = false: zero-fill + sizes (candidates of the segment, mask of its non-empty pixels); FILL = true: slab offsets from the
+// FILL = false: zero-fill + sizes (candidates of the segment, number of its non-empty pixels); FILL = true: slab offsets from the
 // sizes of the preceding segments (a plain sum: the sizing launch is complete), items and candidate lists.  No atomics on global
 // memory, no state that has to be zero on entry.
 template <bool FILL>
@@ -790,48 +773,17 @@ __device__ __forceinline__ void roi_bwd_index_block(RoiIdxShared &S, const RoiGr
     // filter one pass of ROIs into the ordered LDS list, then evaluate every (entry, pixel) pair: number of candidate
     // bins and the column range
     auto build = [&](const int pass) -> int {
-        __syncthreads();
-        const int r = pass * BW_CHUNK + (int)threadIdx.x;
-        bool ok = false;
-        int rsw = 0, rew = 0, prow = 0;
-        float bw = 1.0f;
-        if (r < R) {
-            const float *roi = v.rois + 5 * (long long)r;
-            const RoiGeom t = roi_geom(roi, v.scale);
-            ok = ((int)roi[0] == n) && h >= t.rsh && h <= t.reh && t.rew >= w0 && t.rsw < w0 + npx;   // roi_pooling_op.cc:392-403
-            if (ok) {
-                const int rh = max(t.reh - t.rsh + 1, 1), rw = max(t.rew - t.rsw + 1, 1);
-                const float bh = (float)rh / (float)PH;
-                int phs = (int)floorf((float)(h - t.rsh) / bh), phe = (int)ceilf((float)(h - t.rsh + 1) / bh);   // :423-426
-                phs = min(max(phs, 0), PH); phe = min(max(phe, 0), PH);
-                ok = phe > phs;
-                rsw = t.rsw; rew = t.rew; prow = phs | (phe << 8);
-                bw = (float)rw / (float)PW;
-            }
-        }
-        const unsigned long long bal = __ballot(ok);
-        if (lane == 0) S.wcnt[wave] = __popcll(bal);
-        __syncthreads();
-        int pos = __popcll(bal & ((1ull << lane) - 1ull));
-        int nl = 0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { const int cw = S.wcnt[t]; if (t < wave) pos += cw; nl += cw; }
-        if (ok) { S.roi[pos] = r; S.rsw[pos] = rsw; S.rew[pos] = rew; S.prow[pos] = prow; S.bw[pos] = bw; }
-        __syncthreads();
+        __syncthreads();                                  // the previous list is fully consumed (first pass: S.cnt is zeroed)
+        const int nl = roi_row_filter(S.list, v, PH, PW, pass, n, h, w0, npx, lane, wave);
         int local = 0;
         const int w = w0 + j;
         for (int e = q; e < nl; e += 256 / BWI_PIX) {
             int nb = 0, xr = 0;
-            const int xs = S.rsw[e], xe = S.rew[e];
-            if (j < npx && w >= xs && w <= xe) {
-                const float fbw = S.bw[e];
-                int x0 = (int)floorf((float)(w - xs) / fbw), x1 = (int)ceilf((float)(w - xs + 1) / fbw);
-                x0 = min(max(x0, 0), PW); x1 = min(max(x1, 0), PW);
-                if (x1 > x0) {
-                    const int pr = S.prow[e];
-                    nb = ((pr >> 8) - (pr & 255)) * (x1 - x0);
-                    xr = x0 | (x1 << 4);
-                }
+            RoiSpan x;
+            if (j < npx && roi_row_entry_cols(S.list, e, w, PW, x)) {
+                const int pr = S.list.prow[e];
+                nb = ((pr >> 8) - (pr & 255)) * (x.e - x.s);
+                xr = x.s | (x.e << 4);
             }
             S.nb[e][j] = (unsigned char)nb;
             S.xr[e][j] = (unsigned char)xr;
@@ -850,7 +802,7 @@ __device__ __forceinline__ void roi_bwd_index_block(RoiIdxShared &S, const RoiGr
 #pragma unroll
             for (int m = 1; m < BWI_PIX; m <<= 1) tot += __shfl_xor(tot, m);
             const unsigned mask = (unsigned)(__ballot(c > 0) & 0xffffull);
-            if (lane == 0) { ix.seg_tot[block] = (tot << 5) | __popc(mask); ix.seg_mask[block] = (int)mask; }
+            if (lane == 0) ix.seg_tot[block] = (tot << 5) | __popc(mask);
         }
         return;
     }
@@ -903,8 +855,8 @@ __device__ __forceinline__ void roi_bwd_index_block(RoiIdxShared &S, const RoiGr
         for (int e = e0; e < e1; ++e) {
             const int nb = S.nb[e][sp];
             if (nb == 0) continue;
-            const int xr = S.xr[e][sp], x0 = xr & 15, x1 = xr >> 4, pr = S.prow[e];
-            const int rec0 = S.roi[e] * PH * PW;
+            const int xr = S.xr[e][sp], x0 = xr & 15, x1 = xr >> 4, pr = S.list.prow[e];
+            const int rec0 = S.list.roi[e] * PH * PW;
             for (int ph = pr & 255; ph < (pr >> 8); ++ph)
                 for (int pw = x0; pw < x1; ++pw) *dst++ = (rec0 + ph * PW + pw) * C * 4;     // the record's byte offset
         }
@@ -921,45 +873,33 @@ __global__ __launch_bounds__(256) void roi_bwd_index_kernel(RoiGradPack p, RoiGr
 }
 
 // records u0 .. u0 + W - 1 of the 64 whose byte offsets sit in the lanes of `cur`: per record one v_readlane (-> SGPR) and two
-// buffer loads (CPL dwords per lane) whose scalar offset is that SGPR, then CPL x (compare / select / add); W x 2 loads per
-// lane in flight
-template <int CPL> struct BwdVec;
-template <> struct BwdVec<1> { typedef unsigned int T; static __device__ __forceinline__ T ld(__amdgpu_buffer_rsrc_t r, int v, int s) { return __builtin_amdgcn_raw_buffer_load_b32(r, v, s, 0); } };
-template <int CPL> __device__ __forceinline__ unsigned bwd_elem(const typename BwdVec<CPL>::T &x, int j);
-template <> __device__ __forceinline__ unsigned bwd_elem<1>(const unsigned int &x, int) { return x; }
-
-template <int CPL, int W, bool MASKED>
+// buffer loads (one dword per lane) whose scalar offset is that SGPR, then compare / select / add; W x 2 loads per lane in flight
+template <int W, bool MASKED>
 __device__ __forceinline__ void bwd_drain_lanes(const int cur, const int u0, const int m, const __amdgpu_buffer_rsrc_t ra,
-                                                const __amdgpu_buffer_rsrc_t rt, const int voff, const int want, float (&a)[CPL])
+                                                const __amdgpu_buffer_rsrc_t rt, const int voff, const int want, float &a)
 {
-    typename BwdVec<CPL>::T am_v[W], td_v[W];
+    unsigned am_v[W], td_v[W];
 #pragma unroll
     for (int u = 0; u < W; ++u) {
         const int so = __builtin_amdgcn_readlane(cur, MASKED ? min(u0 + u, 63) : u0 + u);
-        am_v[u] = BwdVec<CPL>::ld(ra, voff, so);
-        td_v[u] = BwdVec<CPL>::ld(rt, voff, so);
+        am_v[u] = __builtin_amdgcn_raw_buffer_load_b32(ra, voff, so, 0);
+        td_v[u] = __builtin_amdgcn_raw_buffer_load_b32(rt, voff, so, 0);
     }
 #pragma unroll
     for (int u = 0; u < W; ++u)
-        if (!MASKED || u0 + u < m) {
-#pragma unroll
-            for (int j = 0; j < CPL; ++j)
-                a[j] += ((int)bwd_elem<CPL>(am_v[u], j) == want + j) ? __builtin_bit_cast(float, bwd_elem<CPL>(td_v[u], j)) : 0.0f;
-        }
+        if (!MASKED || u0 + u < m) a += ((int)am_v[u] == want) ? __builtin_bit_cast(float, td_v[u]) : 0.0f;
 }
 
-// A persistent grid; wave = (item, slice of 64 CPL channels).  XCD x (= blockIdx % 8) works on slice x % nsl of the items of
+// A persistent grid; wave = (item, slice of 64 channels).  XCD x (= blockIdx % 8) works on slice x % nsl of the items of
 // part x / nsl (the item list is in pixel order: a part is a band of rows / frames), so that every record slice is pulled
 // into ONE private L2.  A wave walks its items i, i + stride, ... software-pipelined: while item n's records are in flight,
 // the offsets of item n + 1 and the header of item n + 2 are already requested.
-// CPL = 1 only: 64-channel slices, 256-B pieces of a record per wave.  Wider pieces (2 / 4 channels per lane, 512 B / 1 KB) were
+// One channel per lane: 64-channel slices, 256-B pieces of a record per wave.  Wider pieces (2 / 4 channels per lane, 512 B / 1 KB) were
 // measured slower on the training batch, 82 / 105 us against 75 for the three launches: the walk is bound by its dependent round
 // trips, and a lane with more channels holds fewer records in flight.
-template <int CPL>
 __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const RoiGradIdxPack &ix, const int nsl, const unsigned vblock,
                                                      const unsigned vgrid)
 {
-    static_assert(CPL == 1, "one channel per lane: the loads, the window W and the store below are that width's");
     const int lane = threadIdx.x & 63;
     const int xcd = (int)(vblock & 7);
     const int slice = xcd % nsl, part = xcd / nsl, nparts = 8 / nsl;
@@ -981,7 +921,7 @@ __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const
     if (tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) tr[1] = (long long)__builtin_readcyclecounter(); }
     int idx = ix.pool[it.y + min(lane, it.z - 1)];
     if (tr) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (lane == 0) tr[2] = (long long)__builtin_readcyclecounter(); }
-    const int voff = lane * 4 * CPL;
+    const int voff = lane * 4;
     constexpr int W = 32;
     for (; i < i_end; i += stride) {
         const int pix = __builtin_amdgcn_readfirstlane(it.x), off = __builtin_amdgcn_readfirstlane(it.y);
@@ -993,16 +933,14 @@ __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const
         if (more) idx1 = ix.pool[__builtin_amdgcn_readfirstlane(nxt.y) + min(lane, __builtin_amdgcn_readfirstlane(nxt.z) - 1)];
         const RoiGradViewDev &v = p.v[k];
         const int C = v.C;
-        const int c = slice * 64 * CPL + lane * CPL;
+        const int c = slice * 64 + lane;
         const int want = (pix % (v.H * v.W)) * C + c;
         const int *cand = ix.pool + off;
         // the slice lives in the (wave-uniform) base address, the lane in the vector offset, the record's byte offset is
         // the scalar offset of the load
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)(v.argmax + slice * 64 * CPL), 0, 0x7fffffff, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)(v.top_diff + slice * 64 * CPL), 0, 0x7fffffff, 0x00020000);
-        float a[CPL];
-#pragma unroll
-        for (int j = 0; j < CPL; ++j) a[j] = 0.0f;
+        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void *)(v.argmax + slice * 64), 0, 0x7fffffff, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void *)(v.top_diff + slice * 64), 0, 0x7fffffff, 0x00020000);
+        float a = 0.0f;
         // 64 record offsets per vector load (lane l holds candidate t0 + l); the next 64 are requested before the current
         // ones are consumed
         for (int t0 = 0; t0 < cnt; t0 += 64) {
@@ -1010,24 +948,23 @@ __device__ __forceinline__ void roi_bwd_gather_block(const RoiGradPack &p, const
             if (t0 + 64 < cnt) idx = cand[min(t0 + 64 + lane, cnt - 1)];
             const int m = min(64, cnt - t0);
             int u0 = 0;
-            for (; u0 + W <= m; u0 += W) bwd_drain_lanes<CPL, W, false>(cur, u0, m, ra, rt, voff, want, a);
-            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
-            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
-            if (u0 + 8 <= m) { bwd_drain_lanes<CPL, 8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
-            if (u0 + 4 <= m) { bwd_drain_lanes<CPL, 4, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 4; }
-            if (u0 < m) bwd_drain_lanes<CPL, 4, true>(cur, u0, m, ra, rt, voff, want, a);
+            for (; u0 + W <= m; u0 += W) bwd_drain_lanes<W, false>(cur, u0, m, ra, rt, voff, want, a);
+            if (u0 + 8 <= m) { bwd_drain_lanes<8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 8 <= m) { bwd_drain_lanes<8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 8 <= m) { bwd_drain_lanes<8, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 8; }
+            if (u0 + 4 <= m) { bwd_drain_lanes<4, false>(cur, u0, m, ra, rt, voff, want, a); u0 += 4; }
+            if (u0 < m) bwd_drain_lanes<4, true>(cur, u0, m, ra, rt, voff, want, a);
         }
-        __builtin_nontemporal_store(a[0], v.bottom_diff + (long long)pix * C + c);
+        __builtin_nontemporal_store(a, v.bottom_diff + (long long)pix * C + c);
         it = nxt; idx = idx1;
         if (tr) { if (n_done == 0) t_first = (long long)__builtin_readcyclecounter(); ++n_done; n_cand += cnt; }
     }
     if (tr && lane == 0) { tr[3] = t_first; tr[4] = (long long)__builtin_readcyclecounter(); tr[5] = n_done; tr[6] = n_cand; tr[7] = 0; }
 }
 
-template <int CPL>
 __global__ __launch_bounds__(256) void roi_bwd_gather_kernel(RoiGradPack p, RoiGradIdxPack ix, int nsl)
 {
-    roi_bwd_gather_block<CPL>(p, ix, nsl, blockIdx.x, gridDim.x);
+    roi_bwd_gather_block(p, ix, nsl, blockIdx.x, gridDim.x);
 }
 
 // ===============================================================================================================================
@@ -1042,7 +979,8 @@ __global__ __launch_bounds__(256) void roi_bwd_gather_kernel(RoiGradPack p, RoiG
 // index inside the frame, -1 for none); tests and bench.py's verification only.  One thread per pooled value; the bin geometry as
 // the forward computes it.
 __global__ __launch_bounds__(256) void roi_argmax_decode_kernel(const unsigned char *__restrict__ plane8, const float *__restrict__ rois,
-                                                                float scale, int R, int H, int W, int C, int PH, int PW, int *__restrict__ out)
+                                                                float scale, int B, int R, int H, int W, int C, int PH, int PW,
+                                                                int *__restrict__ out)
 {
     const long long total = (long long)R * PH * PW * C;
     const unsigned short *const plane16 = reinterpret_cast<const unsigned short *>(plane8 + total);
@@ -1052,20 +990,13 @@ __global__ __launch_bounds__(256) void roi_argmax_decode_kernel(const unsigned c
         const int pw = (int)(t % PW); t /= PW;
         const int ph = (int)(t % PH);
         const int n = (int)(t / PH);
-        const float *roi = rois + 5 * (long long)n;
-        const RoiGeom q = roi_geom(roi, scale);
-        const int rw = max(q.rew - q.rsw + 1, 1), rh = max(q.reh - q.rsh + 1, 1);
-        const float bh = (float)rh / (float)PH, bw = (float)rw / (float)PW;
-        const int hs = min(max((int)floorf(__fmul_rn((float)ph, bh)) + q.rsh, 0), H);
-        const int he = min(max((int)ceilf(__fmul_rn((float)(ph + 1), bh)) + q.rsh, 0), H);
-        const int ws = min(max((int)floorf(__fmul_rn((float)pw, bw)) + q.rsw, 0), W);
-        const int we = min(max((int)ceilf(__fmul_rn((float)(pw + 1), bw)) + q.rsw, 0), W);
-        const bool big = he > hs && we > ws && (he - hs) * (we - ws) > 255;
+        const BinGeom g = roi_bin_rect(rois + 5 * (long long)n, ph, pw, scale, B, H, W, PH, PW);
+        const bool big = roi_bin_wide(g);
         const unsigned code = big ? (unsigned)plane16[i] : (unsigned)plane8[i];
         int res = -1;
         if (code != (big ? 0xffffu : 0xffu)) {
-            const int bwid = max(we - ws, 1);
-            res = ((hs + (int)code / bwid) * W + ws + (int)code % bwid) * C + c;
+            const int bwid = max(g.we - g.ws, 1);
+            res = ((g.hs + (int)code / bwid) * W + g.ws + (int)code % bwid) * C + c;
         }
         out[i] = res;
     }
@@ -1217,33 +1148,33 @@ static bool bwd_generic_ok(const mv3d_roi_grad_view &w)
     return (long long)w.batch_size * w.height * w.width <= 0x7fffffffLL && w.channels / (bwd_generic_vec4(w) ? 4 : 1) <= 64 * 16;
 }
 
-static int roi_pool_backward_generic(const mv3d_roi_grad_view &w, int pooled_height, int pooled_width, void *stream)
+// generic shapes: one launch of the generic kernel per view
+static int launch_roi_bwd_generic(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width, hipStream_t s)
 {
-    if (!bwd_generic_ok(w)) return MV3D_ERR_INVALID_ARG;
-    const float *top_diff = w.top_diff, *bottom_rois = w.bottom_rois;
-    float *bottom_diff = w.bottom_diff;
-    const int32_t *argmax_data = w.argmax_data;
-    const float spatial_scale = w.spatial_scale;
-    const int batch_size = w.batch_size, num_rois = w.num_rois, height = w.height, width = w.width, channels = w.channels;
-    const long long pixels = (long long)batch_size * height * width;
-    const bool v4 = bwd_generic_vec4(w);
-    const int cv = channels / (v4 ? 4 : 1);
-    const int nacc = cv <= 64 ? 1 : (cv <= 128 ? 2 : (cv <= 256 ? 4 : (cv <= 512 ? 8 : 16)));
-    const unsigned blocks = (unsigned)((pixels + BWD_PIX - 1) / BWD_PIX);
-    hipStream_t s = (hipStream_t)stream;
-#define MV3D_BWD(V, N)                                                                                             \
-    hipLaunchKernelGGL((roi_pool_bwd_kernel<V, N>), dim3(blocks), dim3(256), 0, s, top_diff, spatial_scale, batch_size, \
-                       num_rois, height, width, channels, pooled_height, pooled_width, bottom_rois, bottom_diff,   \
-                       argmax_data)
-    if (v4) {
-        switch (nacc) { case 1: MV3D_BWD(4, 1); break; case 2: MV3D_BWD(4, 2); break; case 4: MV3D_BWD(4, 4); break;
-                        case 8: MV3D_BWD(4, 8); break; default: MV3D_BWD(4, 16); break; }
-    } else {
-        switch (nacc) { case 1: MV3D_BWD(1, 1); break; case 2: MV3D_BWD(1, 2); break; case 4: MV3D_BWD(1, 4); break;
-                        case 8: MV3D_BWD(1, 8); break; default: MV3D_BWD(1, 16); break; }
-    }
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_grad_view &w = views[k];
+        if (!bwd_generic_ok(w)) return MV3D_ERR_INVALID_ARG;
+        const long long pixels = (long long)w.batch_size * w.height * w.width;
+        const bool v4 = bwd_generic_vec4(w);
+        const int cv = w.channels / (v4 ? 4 : 1);
+        const int nacc = cv <= 64 ? 1 : (cv <= 128 ? 2 : (cv <= 256 ? 4 : (cv <= 512 ? 8 : 16)));
+        const unsigned blocks = (unsigned)((pixels + BWD_PIX - 1) / BWD_PIX);
+#define MV3D_BWD(V, N)                                                                                                      \
+    hipLaunchKernelGGL((roi_pool_bwd_kernel<V, N>), dim3(blocks), dim3(256), 0, s, w.top_diff, w.spatial_scale, w.batch_size, \
+                       w.num_rois, w.height, w.width, w.channels, pooled_height, pooled_width, w.bottom_rois, w.bottom_diff, \
+                       w.argmax_data)
+        if (v4) {
+            switch (nacc) { case 1: MV3D_BWD(4, 1); break; case 2: MV3D_BWD(4, 2); break; case 4: MV3D_BWD(4, 4); break;
+                            case 8: MV3D_BWD(4, 8); break; default: MV3D_BWD(4, 16); break; }
+        } else {
+            switch (nacc) { case 1: MV3D_BWD(1, 1); break; case 2: MV3D_BWD(1, 2); break; case 4: MV3D_BWD(1, 4); break;
+                            case 8: MV3D_BWD(1, 8); break; default: MV3D_BWD(1, 16); break; }
+        }
 #undef MV3D_BWD
-    return mv3d_launch_status();
+        const int rc = mv3d_launch_status();
+        if (rc != MV3D_OK) return rc;
+    }
+    return MV3D_OK;
 }
 
 // The per-view arguments of the multi-view forward entries.  pooled: the entry pools (the map, and the top when there are ROIs, are
@@ -1364,15 +1295,26 @@ extern "C" size_t mv3d_roi_pool_backward_workspace_bytes(int num_views, const mv
         total += mv3d_align_up(bwd_pool_entries(w, pooled_height, pooled_width) * sizeof(int));
         nseg += bwd_segments(w);
     }
-    // header | candidates per segment | mask per segment | items | pool
-    return total + 2 * mv3d_align_up(nseg * sizeof(int)) + MV3D_ALIGN;
+    // header | sizes per segment | items | pool
+    return total + mv3d_align_up(nseg * sizeof(int)) + MV3D_ALIGN;
+}
+
+// the view's fields every RoiPoolGrad body reads; the launch geometry (pxg, gpr, first_block) is the sliced launcher's to fill
+static RoiGradViewDev grad_view_dev(const mv3d_roi_grad_view &w)
+{
+    RoiGradViewDev v;
+    v.top_diff = w.top_diff; v.rois = w.bottom_rois; v.argmax = w.argmax_data; v.bottom_diff = w.bottom_diff;
+    v.scale = w.spatial_scale; v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
+    v.nsl = w.channels / 64;
+    v.first_block = 0; v.pxg = 4; v.gpr = 0;
+    return v;
 }
 
 // The views in index order (the densest view first -- candidates per pixel ~ R PH PW / pixels: the 8 x 64 front-view map carries
 // ~10 x the lists of the others -- so that its pixels head the item list and the gather's waves start with the long lists instead
 // of ending with them: the kernel's time is its slowest wave) and the segment numbering
-struct BwdOrder { RoiGradPack p; unsigned first_block[MV3D_MAX_ROI_VIEWS]; int gpr[MV3D_MAX_ROI_VIEWS]; unsigned iblocks; size_t n_items, pool_entries; };
-static void bwd_order(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, BwdOrder &o)
+struct BwdIndexPlan { RoiGradPack p; RoiGradIdxPack ix; unsigned iblocks; size_t n_items, pool_entries; };
+static void bwd_order(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, BwdIndexPlan &o)
 {
     RoiGradPack &p = o.p;
     p.n = num_views; p.PH = PH; p.PW = PW;
@@ -1385,45 +1327,35 @@ static void bwd_order(int num_views, const mv3d_roi_grad_view *views, int PH, in
             const double dy = (double)y.num_rois / ((double)y.batch_size * y.height * y.width);
             if (dy > dx) { const int t = ord[a]; ord[a] = ord[b]; ord[b] = t; }
         }
+    o.ix = RoiGradIdxPack{};
     o.iblocks = 0; o.n_items = 0; o.pool_entries = 0;
     for (int k = 0; k < num_views; ++k) {
         const mv3d_roi_grad_view &w = views[ord[k]];
-        RoiGradViewDev &v = p.v[k];
-        v.top_diff = w.top_diff; v.rois = w.bottom_rois; v.argmax = w.argmax_data; v.bottom_diff = w.bottom_diff;
-        v.scale = w.spatial_scale; v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
-        v.nsl = w.channels / 64;
-        v.first_block = 0; v.pxg = 4; v.gpr = 0;
+        p.v[k] = grad_view_dev(w);
         o.n_items += (size_t)w.batch_size * w.height * w.width;
-        o.first_block[k] = o.iblocks;
-        o.gpr[k] = (w.width + BWI_PIX - 1) / BWI_PIX;
+        o.ix.first_block[k] = o.iblocks;
+        o.ix.gpr[k] = (w.width + BWI_PIX - 1) / BWI_PIX;
         o.iblocks += bwd_segments(w);
         o.pool_entries += bwd_pool_entries(w, PH, PW);
     }
-    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) { p.v[k] = p.v[0]; o.first_block[k] = 0; o.gpr[k] = 1; }
+    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) { p.v[k] = p.v[0]; o.ix.first_block[k] = 0; o.ix.gpr[k] = 1; }
 }
 
-struct BwdIndexPlan { RoiGradPack p; RoiGradIdxPack ix; unsigned iblocks; };
+// the ordered views and the workspace's regions: header | sizes per segment | items | pool
 static int bwd_index_plan(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, void *workspace, BwdIndexPlan &pl)
 {
-    BwdOrder o;
-    bwd_order(num_views, views, PH, PW, o);
-    if (o.pool_entries > 0x7fffffffull) return MV3D_ERR_INVALID_ARG;
-    pl.p = o.p;
+    bwd_order(num_views, views, PH, PW, pl);
+    if (pl.pool_entries > 0x7fffffffull) return MV3D_ERR_INVALID_ARG;
     RoiGradIdxPack &ix = pl.ix;
-    ix = RoiGradIdxPack{};
-    for (int k = 0; k < MV3D_MAX_ROI_VIEWS; ++k) { ix.first_block[k] = o.first_block[k]; ix.gpr[k] = o.gpr[k]; }
     char *ws = (char *)workspace;
     size_t off = MV3D_ALIGN;
     ix.header = (int *)ws;
-    ix.seg_tot = (int *)(ws + off); off += mv3d_align_up((size_t)o.iblocks * sizeof(int));
-    ix.seg_mask = (int *)(ws + off); off += mv3d_align_up((size_t)o.iblocks * sizeof(int));
-    ix.items = (int4 *)(ws + off); off += mv3d_align_up(o.n_items * sizeof(int4));
+    ix.seg_tot = (int *)(ws + off); off += mv3d_align_up((size_t)pl.iblocks * sizeof(int));
+    ix.items = (int4 *)(ws + off); off += mv3d_align_up(pl.n_items * sizeof(int4));
     ix.pool = (int *)(ws + off);
-    ix.trace = nullptr;
 #ifdef MV3D_TUNING                                                     // diagnostics (tools/roi_bwd_trace.py), experiment builds only
     ix.trace = getenv("MV3D_BWD_TRACE") ? (long long *)strtoull(getenv("MV3D_BWD_TRACE"), nullptr, 10) : nullptr;
 #endif
-    pl.iblocks = o.iblocks;
     return MV3D_OK;
 }
 
@@ -1435,6 +1367,58 @@ static int bwd_gather_groups()
 #else
     return BWG_GROUPS;
 #endif
+}
+
+// the indexed body: sizing + half of the zero fill, lists + the other half, gather
+static int launch_roi_bwd_indexed(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, void *workspace, hipStream_t s)
+{
+    // the gather's 64-channel slices, one per XCD or XCD group: the slice count divides 8 (C = 64, 128, 256 or 512)
+    const int nsl = views[0].channels / 64;
+    BwdIndexPlan pl;
+    const int rc = bwd_index_plan(num_views, views, PH, PW, workspace, pl);
+    if (rc != MV3D_OK) return rc;
+    hipLaunchKernelGGL(roi_bwd_index_kernel<false>, dim3(pl.iblocks), dim3(256), 0, s, pl.p, pl.ix);
+    hipLaunchKernelGGL(roi_bwd_index_kernel<true>, dim3(pl.iblocks), dim3(256), 0, s, pl.p, pl.ix);
+    hipLaunchKernelGGL(roi_bwd_gather_kernel, dim3((unsigned)(bwd_gather_groups() * 8)), dim3(256), 0, s, pl.p, pl.ix, nsl);
+    return mv3d_launch_status();
+}
+
+// the sliced body: all views in one launch
+static int launch_roi_bwd_sliced(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, hipStream_t s)
+{
+    RoiGradPack p;
+    p.n = num_views; p.PH = PH; p.PW = PW;
+    unsigned blocks = 0;
+    size_t carry = 0;
+    for (int k = 0; k < num_views; ++k) {
+        const mv3d_roi_grad_view &w = views[k];
+        RoiGradViewDev &v = p.v[k];
+        v = grad_view_dev(w);
+        v.first_block = blocks;
+        // a workgroup = one row segment x one slice.  Long segments amortise the ROI filter and the launch of a workgroup
+        // over many (mostly empty) pixels; small maps get short segments so that the launch still fills the chip
+        const long long rows = (long long)w.batch_size * w.height * v.nsl;
+        long long gpr = (w.width + BW_MAXPXG - 1) / BW_MAXPXG;
+        if (rows * gpr < 1024) gpr = (1024 + rows - 1) / rows;
+        if (gpr > w.width) gpr = w.width;
+        v.pxg = (int)((w.width + gpr - 1) / gpr);
+        v.gpr = (w.width + v.pxg - 1) / v.pxg;
+        blocks += (unsigned)(rows * v.gpr);
+        if (w.num_rois > BW_CHUNK && (size_t)v.pxg * 64 * sizeof(float) > carry) carry = (size_t)v.pxg * 64 * sizeof(float);
+    }
+    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
+    hipLaunchKernelGGL(roi_pool_bwd_sliced_kernel, dim3(blocks), dim3(BW_THREADS), carry, s, p);
+    return mv3d_launch_status();
+}
+
+// the pair's body: ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip): the round-5 structure it
+// replaced (index + zero fill, gather: three launches) was level alone and 3 - 7 % slower in the path (profiles/r06_g, DESIGN.md
+// section 3.6).  argmax_data holds the compact codes mv3d_roi_pool_forward_views_pair wrote on the same decision from the same shapes
+static int launch_roi_bwd_tiles(int num_views, const mv3d_roi_grad_view *views, int PH, int PW, hipStream_t s)
+{
+    for (int k = 0; k < num_views; ++k)
+        if (!aligned16(views[k].bottom_diff) || !aligned16(views[k].top_diff) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
+    return mv3d_launch_roi_pair_tiles(num_views, views, PH, PW, s);
 }
 
 // the shape half of the backward entries' argument check (the query below answers from it alone, pointers may be NULL there)
@@ -1499,57 +1483,11 @@ static int roi_pool_backward_run(int num_views, const mv3d_roi_grad_view *views,
                          workspace_bytes >= mv3d_roi_pool_backward_workspace_bytes(num_views, views, pooled_height, pooled_width);
     const char *path = mv3d_roi_pool_backward_path(num_views, views, pooled_height, pooled_width, have_ws, pair);
     if (!path) return MV3D_ERR_INVALID_ARG;
-    if (path == ROI_GRAD_TILES) {
-        // the decision mv3d_roi_pool_forward_views_pair took from the same shapes: compact codes in argmax_data
-        for (int k = 0; k < num_views; ++k)
-            if (!aligned16(views[k].bottom_diff) || !aligned16(views[k].top_diff) || !aligned16(views[k].argmax_data)) return MV3D_ERR_INVALID_ARG;
-        // ONE launch of map tiles, no index, no fill, no scratch memory (roi_grad_tiles.hip): the round-5 structure it replaced (index +
-        // zero fill, gather: three launches) was level alone and 3 - 7 % slower in the path (profiles/r06_g)
-        return mv3d_launch_roi_pair_tiles(num_views, views, pooled_height, pooled_width, (hipStream_t)stream);
-    }
-    if (path == ROI_GRAD_GENERIC) {
-        for (int k = 0; k < num_views; ++k) {
-            const int rc = roi_pool_backward_generic(views[k], pooled_height, pooled_width, stream);
-            if (rc != MV3D_OK) return rc;
-        }
-        return MV3D_OK;
-    }
-    if (path == ROI_GRAD_INDEXED) {
-        // the gather's 64-channel slices, one per XCD or XCD group: the slice count divides 8 (C = 64, 128, 256 or 512)
-        const int nsl = views[0].channels / 64;
-        BwdIndexPlan pl;
-        const int rc = bwd_index_plan(num_views, views, pooled_height, pooled_width, workspace, pl);
-        if (rc != MV3D_OK) return rc;
-        hipLaunchKernelGGL(roi_bwd_index_kernel<false>, dim3(pl.iblocks), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
-        hipLaunchKernelGGL(roi_bwd_index_kernel<true>, dim3(pl.iblocks), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix);
-        hipLaunchKernelGGL(roi_bwd_gather_kernel<1>, dim3((unsigned)(bwd_gather_groups() * 8)), dim3(256), 0, (hipStream_t)stream, pl.p, pl.ix, nsl);
-        return mv3d_launch_status();
-    }
-    RoiGradPack p;
-    p.n = num_views; p.PH = pooled_height; p.PW = pooled_width;
-    unsigned blocks = 0;
-    size_t carry = 0;
-    for (int k = 0; k < num_views; ++k) {
-        const mv3d_roi_grad_view &w = views[k];
-        RoiGradViewDev &v = p.v[k];
-        v.top_diff = w.top_diff; v.rois = w.bottom_rois; v.argmax = w.argmax_data; v.bottom_diff = w.bottom_diff;
-        v.scale = w.spatial_scale; v.B = w.batch_size; v.R = w.num_rois; v.H = w.height; v.W = w.width; v.C = w.channels;
-        v.nsl = w.channels / 64;
-        v.first_block = blocks;
-        // sliced kernel: a workgroup = one row segment x one slice.  Long segments amortise the ROI filter and the launch
-        // of a workgroup over many (mostly empty) pixels; small maps get short segments so that the launch still fills the chip
-        const long long rows = (long long)w.batch_size * w.height * v.nsl;
-        long long gpr = (w.width + BW_MAXPXG - 1) / BW_MAXPXG;
-        if (rows * gpr < 1024) gpr = (1024 + rows - 1) / rows;
-        if (gpr > w.width) gpr = w.width;
-        v.pxg = (int)((w.width + gpr - 1) / gpr);
-        v.gpr = (w.width + v.pxg - 1) / v.pxg;
-        blocks += (unsigned)(rows * v.gpr);
-        if (w.num_rois > BW_CHUNK && (size_t)v.pxg * 64 * sizeof(float) > carry) carry = (size_t)v.pxg * 64 * sizeof(float);
-    }
-    for (int k = num_views; k < MV3D_MAX_ROI_VIEWS; ++k) p.v[k] = p.v[0];
-    hipLaunchKernelGGL(roi_pool_bwd_sliced_kernel, dim3(blocks), dim3(BW_THREADS), carry, (hipStream_t)stream, p);
-    return mv3d_launch_status();
+    hipStream_t s = (hipStream_t)stream;
+    if (path == ROI_GRAD_TILES) return launch_roi_bwd_tiles(num_views, views, pooled_height, pooled_width, s);
+    if (path == ROI_GRAD_GENERIC) return launch_roi_bwd_generic(num_views, views, pooled_height, pooled_width, s);
+    if (path == ROI_GRAD_INDEXED) return launch_roi_bwd_indexed(num_views, views, pooled_height, pooled_width, workspace, s);
+    return launch_roi_bwd_sliced(num_views, views, pooled_height, pooled_width, s);
 }
 
 extern "C" int mv3d_roi_pool_backward_views(int num_views, const mv3d_roi_grad_view *views, int pooled_height, int pooled_width,
@@ -1564,15 +1502,14 @@ static void grad_views_of(int num_views, const mv3d_roi_view *views, mv3d_roi_gr
 {
     for (int k = 0; k < num_views; ++k) {
         const mv3d_roi_view &w = views[k];
-        g[k].bottom_diff = nullptr; g[k].bottom_rois = w.bottom_rois; g[k].top_diff = nullptr; g[k].argmax_data = nullptr;
-        g[k].spatial_scale = w.spatial_scale; g[k].batch_size = w.batch_size; g[k].num_rois = w.num_rois; g[k].height = w.height;
-        g[k].width = w.width; g[k].channels = w.channels;
+        g[k] = {nullptr, w.bottom_rois, nullptr, nullptr, w.spatial_scale, w.batch_size, w.num_rois, w.height, w.width, w.channels};
     }
 }
 
 // Do these views go through the pair's own kernels (compact argmax codes)?  Decided from the SHAPES alone (channel widths the
-// XCD-sliced forward handles, at least one ROI per view, the index's own conditions, bins whose scan positions fit 16 bits), so that
-// the forward, the backward and the decode entries take the same decision independently.
+// XCD-sliced forward handles, at least one ROI per view, the limits the tiles kernel shares with the indexed body (bwd_index_eligible:
+// one C for all views, pooled sizes <= 15, 31-bit record offsets), bins whose scan positions fit 16 bits), so that the forward, the
+// backward and the decode entries take the same decision independently.
 static bool roi_pair_shapes(int num_views, const mv3d_roi_grad_view *g, int PH, int PW)
 {
     if (!bwd_index_eligible(num_views, g, PH, PW)) return false;
@@ -1649,7 +1586,7 @@ extern "C" int mv3d_roi_pool_argmax_decode(int num_views, const mv3d_roi_view *v
         if ((void *)argmax_out[k] == (void *)w.argmax_data) return MV3D_ERR_INVALID_ARG;
         const unsigned blocks = (unsigned)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
         hipLaunchKernelGGL(roi_argmax_decode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char *)w.argmax_data,
-                           w.bottom_rois, w.spatial_scale, w.num_rois, w.height, w.width, w.channels, pooled_height, pooled_width, argmax_out[k]);
+                           w.bottom_rois, w.spatial_scale, w.batch_size, w.num_rois, w.height, w.width, w.channels, pooled_height, pooled_width, argmax_out[k]);
     }
     return mv3d_launch_status();
 }
@@ -1659,10 +1596,7 @@ extern "C" int mv3d_roi_pool_backward(const float *top_diff, float spatial_scale
                                       const float *bottom_rois, float *bottom_diff, const int32_t *argmax_data,
                                       void *stream)
 {
-    mv3d_roi_grad_view w;
-    w.bottom_diff = bottom_diff; w.bottom_rois = bottom_rois; w.top_diff = top_diff; w.argmax_data = argmax_data;
-    w.spatial_scale = spatial_scale; w.batch_size = batch_size; w.num_rois = num_rois; w.height = height; w.width = width;
-    w.channels = channels;
+    const mv3d_roi_grad_view w = {bottom_diff, bottom_rois, top_diff, argmax_data, spatial_scale, batch_size, num_rois, height, width, channels};
     return mv3d_roi_pool_backward_views(1, &w, pooled_height, pooled_width, nullptr, 0, stream);
 }
 

@@ -80,13 +80,13 @@ def unpack_host(pack, spec):
     return outs
 
 
-def _workspace(nbytes, device, tag, zero=False):
-    """Reused per (device, stream, tag) so hot calls never allocate (buffers are 256-B aligned).  zero=True: zero-filled
-    when it is (re)allocated (workspaces whose header the kernels expect zero on first use and leave zero)."""
+def _workspace(nbytes, device, tag):
+    """Reused per (device, stream, tag) so hot calls never allocate (buffers are 256-B aligned).  Uninitialised: every kernel
+    that takes a workspace writes what it reads."""
     key = (str(device), torch.cuda.current_stream().cuda_stream, tag)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = (torch.zeros if zero else torch.empty)(max(nbytes, 256), dtype=torch.uint8, device=device)
+        buf = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf
 
@@ -572,7 +572,7 @@ def roi_pool_backward_views(views, pooled_height, pooled_width, outs=None, works
     arr, res = _roi_grad_views(views, outs)
     if workspace is None:
         nbytes = lib().mv3d_roi_pool_backward_workspace_bytes(len(views), arr, pooled_height, pooled_width)
-        workspace = _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
+        workspace = _workspace(nbytes, views[0][0].device, "roi_bwd")
     wp, wn = (None, 0) if workspace is False else (_ptr(workspace), workspace.numel())
     check(lib().mv3d_roi_pool_backward_views(len(views), arr, pooled_height, pooled_width, wp, wn, _stream()),
           "mv3d_roi_pool_backward_views")
@@ -628,7 +628,7 @@ def roi_pool_pair_workspace(views, pooled_height, pooled_width):
     for k, (_, rois, _, (B, H, W, Cc), scale) in enumerate(views):       # (the size query reads the shapes only)
         arr[k] = RoiGradView(None, None, None, None, float(scale), B, rois.shape[0], H, W, Cc)
     nbytes = lib().mv3d_roi_pool_pair_workspace_bytes(len(views), arr, pooled_height, pooled_width)
-    return _workspace(nbytes, views[0][0].device, "roi_bwd", zero=True)
+    return _workspace(nbytes, views[0][0].device, "roi_bwd")
 
 
 def rois_3d_to_fv(rois_3d, out=None):

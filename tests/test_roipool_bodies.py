@@ -15,8 +15,11 @@ THE TABLE (CASES below, built from these rules; test_table_covers_every_body_and
                  stack  300 copies of a one-pixel ROI on an interior pixel + 300 on the map's last pixel
                  cover  70 ROIs that each contain the whole map
                  many   700 random boxes
+                 chunks the `many` generator with 1100 boxes: more than the 1024 ROIs (BWD_CHUNK) the generic kernel stages in LDS at
+                        a time, so its second chunk and the barrier between chunks run
     pooled       all bodies: POOLED_ALL; sliced and generic: + (16, 16), (22, 23); generic: + (23, 23) at C = 64
-    rows         every (body, pooled size) runs `edges`; stack and cover run at (1,1), (7,7), (8,8), (15,15); many at (7,7), (15,15)
+    rows         every (body, pooled size) runs `edges`; stack and cover run at (1,1), (7,7), (8,8), (15,15); many at (7,7), (15,15);
+                 chunks: generic only, C = 20 (vector loads) at (3,5) and C = 6 (scalar loads) at (7,7)
     scale        SCALES, rotating with the pooled size and the population (every body sees every scale)
     channels     rotating with the pooled size, per body: BODY_WIDTHS (the big populations take each body's narrowest width)
 
@@ -47,6 +50,8 @@ POOLED_BIG = [(16, 16), (22, 23)]                          # sliced and generic 
 POOLED_OVER = (23, 23)                                     # 529 > BW_CAND bins: generic even at C = 64
 POOLED_HEAVY = [(1, 1), (7, 7), (8, 8), (15, 15)]          # stack and cover
 POOLED_MANY = [(7, 7), (15, 15)]
+CHUNKS = [(20, (3, 5)), (6, (7, 7))]                       # (C, pooled) of the generic body's `chunks` rows
+POPULATIONS = ["edges", "stack", "cover", "many", "chunks"]
 # (C, workspace given) per body, rotating with the pooled size on the `edges` rows; the first entry serves the big populations
 BODY_WIDTHS = {
     # vector loads / scalar loads / two accumulators (324 = 81 float4 lanes; 320 is 5 x 64 and takes the sliced body at <= 512 bins,
@@ -68,7 +73,7 @@ class Case:
 
 def _scale_of(pooled, pop):
     order = POOLED_ALL + POOLED_BIG + [POOLED_OVER]
-    return SCALES[(order.index(pooled) + ["edges", "stack", "cover", "many"].index(pop)) % 4]
+    return SCALES[(order.index(pooled) + POPULATIONS.index(pop)) % 4]
 
 
 def _build_cases():
@@ -85,6 +90,8 @@ def _build_cases():
     cases.append(Case("sliced", 64, (16, 16), "edges", _scale_of((16, 16), "edges"), True))      # too large for the index: sliced
     cases.append(Case("sliced", 64, (22, 23), "edges", _scale_of((22, 23), "edges"), False))
     cases.append(Case("sliced", 192, (22, 23), "cover", _scale_of((22, 23), "cover"), True))
+    for Cc, pooled in CHUNKS:
+        cases.append(Case("generic", Cc, pooled, "chunks", _scale_of(pooled, "chunks"), False))
     cases.append(Case("generic", 64, POOLED_OVER, "edges", _scale_of(POOLED_OVER, "edges"), False))
     cases.append(Case("generic", 320, POOLED_OVER, "edges", _scale_of(POOLED_OVER, "edges"), False))
     return sorted(cases, key=lambda c: (c.key, c.body))      # cases that share inputs are neighbours
@@ -118,8 +125,7 @@ def population(pop, rng, B, H, W, scale):
     if pop == "cover":
         return np.array([[j % B, -(j % 5) / scale, -(j % 3) / scale, (W - 1 + j % 7) / scale, (H - 1 + j % 4) / scale]
                          for j in range(70)], np.float32)
-    assert pop == "many"
-    n = 700
+    n = {"many": 700, "chunks": 1100}[pop]
     x1, y1 = rng.uniform(-2, W - 1, n), rng.uniform(-2, H - 1, n)
     x2, y2 = x1 + rng.uniform(0, W / 2.0, n), y1 + rng.uniform(0, H / 2.0, n)
     return np.stack([rng.randint(0, B, n), x1 / scale, y1 / scale, x2 / scale, y2 / scale], 1).astype(np.float32)
@@ -211,6 +217,7 @@ def test_table_covers_every_body_and_pooled_size():
             assert (body, pooled, "many") in have, (body, pooled)
         assert {c.scale for c in CASES if c.body == body} == set(SCALES), body
     assert ("generic", POOLED_OVER, "edges") in have
+    assert {(c.body, c.C, c.pooled) for c in CASES if c.pop == "chunks"} == {("generic", 20, (3, 5)), ("generic", 6, (7, 7))}
     want = {"generic": {(6, False), (20, False), (324, False), (320, False), (64, False)},
             "sliced": {(64, False), (1024, False), (192, True), (64, True)},
             "indexed": {(64, True), (128, True), (256, True), (512, True)},
@@ -221,6 +228,7 @@ def test_table_covers_every_body_and_pooled_size():
     assert any(c.body == "sliced" and c.C == 64 and c.ws and c.pooled == (16, 16) for c in CASES)
     assert len({c.id for c in CASES}) == len(CASES)
     assert population("stack", None, 2, 10, 19, 0.125).shape[0] > 512 and population("many", np.random.RandomState(0), 2, 10, 19, 0.5).shape[0] == 700
+    assert population("chunks", np.random.RandomState(0), 2, 10, 19, 0.5).shape[0] == 1100 > 1024       # BWD_CHUNK (csrc/roi_pool.hip)
 
 
 @pytest.fixture(scope="module")
