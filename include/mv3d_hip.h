@@ -716,6 +716,14 @@ int mv3d_train_path_finish(mv3d_train_path *path, int slot, int32_t *rows_out, i
 /* host seconds the helper spent waiting for stage 1 / drawing since the last call (diagnostics); either pointer may be NULL */
 int mv3d_train_path_host_seconds(mv3d_train_path *path, double *wait_s, double *draw_s);
 void mv3d_train_path_destroy(mv3d_train_path *path);     /* waits for the slots in flight, joins the thread */
+/* What a path of this configuration enqueues per batch (host only, no device call): the launches of stage 1 (submit) and of stage 2
+ * (the host stage; the lists' upload counts as one, and so does the disable launch, which a batch with nothing to disable skips), the
+ * NMS rounds counted by the plan of mv3d_nms_round_plan (round 1 is two launches), the reports written through mapped pinned buffers.
+ * Returns 1 when independent launches of the batch are paired in one grid (proposal decode || anchor overlap, local rank || anchor
+ * labels, merge rank || anchor compaction, anchor emit || ROI emit; the reports written by the last launch of stage 1), 0 when the
+ * configuration keeps the single-purpose launches (the counting rank path: more than 24576 keys per frame), -1 for a configuration
+ * mv3d_train_path_create refuses.  Either pointer may be NULL. */
+int mv3d_train_path_launch_plan(const mv3d_train_path_config *config, int32_t *stage1_launches, int32_t *stage2_launches);
 
 /* KITTI label rows -> ground-truth encodings (lib/datasets/kitti_mv3d.py:240-272 with computeCorners3D, camera_to_lidar_cnr,
  * lidar_cnr_to_3d, lidar_3d_to_bv of lib/utils/transform.py:441-465,502-524,172-187,113-142), one thread per labelled object:

@@ -118,15 +118,18 @@ __device__ __forceinline__ void mv3d_block_compact(const int N, Pred pred, Emit 
 // (workgroups are dispatched in order, so a predecessor is always running or done).  agg has
 // gridDim.x*NP + 1 words and must be zero on entry; the workgroup that finishes last clears it again.
 // pred(i, flags[NP]) classifies item i, emit(k, pos, i) stores it at position pos of list k.  totals[] is
-// valid in the LAST workgroup (blockIdx.x == gridDim.x - 1) only.
+// valid in the LAST workgroup (b == G - 1) only.
 #define MV3D_GC_ITEMS 1024
+// The workgroup's index b and the workgroups' number G are arguments: a kernel that runs the compaction in a part of its
+// grid (another body in the rest) passes the part's own numbering -- the compaction's workgroups must then hold the
+// LOWEST indices of their blockIdx.y, so that the predecessors a workgroup looks back on were dispatched before it.
 template <int NP, typename Pred, typename Emit>
-__device__ __forceinline__ void mv3d_grid_compact(const int N, Pred pred, Emit emit, int32_t *agg, int totals[NP])
+__device__ __forceinline__ void mv3d_grid_compact(const int N, Pred pred, Emit emit, int32_t *agg, int totals[NP], const int b,
+                                                  const int G)
 {
     __shared__ int s_cnt[4][NP];
     __shared__ int s_off[NP];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int b = blockIdx.x, G = gridDim.x;
     const int beg = b * MV3D_GC_ITEMS + wave * 256;
     bool f[4][NP];
     int cnt[NP];
@@ -151,7 +154,7 @@ __device__ __forceinline__ void mv3d_grid_compact(const int N, Pred pred, Emit e
         __hip_atomic_store(&agg[b * NP + k], s_cnt[0][k] + s_cnt[1][k] + s_cnt[2][k] + s_cnt[3][k] + 1, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
-    for (int t = threadIdx.x; t < b * NP; t += blockDim.x) {      // look back over all predecessors at once
+    for (int t = threadIdx.x; t < b * NP; t += 256) {             // look back over all predecessors at once
         int v;
         while ((v = __hip_atomic_load(&agg[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0) __builtin_amdgcn_s_sleep(2);
         atomicAdd(&s_off[t % NP], v - 1);
@@ -181,3 +184,8 @@ __device__ __forceinline__ void mv3d_grid_compact(const int N, Pred pred, Emit e
     }
 }
 
+template <int NP, typename Pred, typename Emit>
+__device__ __forceinline__ void mv3d_grid_compact(const int N, Pred pred, Emit emit, int32_t *agg, int totals[NP])
+{
+    mv3d_grid_compact<NP>(N, pred, emit, agg, totals, (int)blockIdx.x, (int)gridDim.x);
+}

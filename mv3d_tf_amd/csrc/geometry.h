@@ -143,14 +143,15 @@ __device__ __forceinline__ double bbox_overlap_f64(double b0, double b1, double 
 }
 
 // The two target layers stage a frame's ground-truth BEV boxes, columns 0..3 of gt_bv (G, 5), in LDS (4 floats per box,
-// TARGET_MAX_GT boxes at most; the workgroup synchronises afterwards).
+// TARGET_MAX_GT boxes at most; the workgroup synchronises afterwards) -- by the first `threads` threads of the workgroup.
 #define TARGET_MAX_GT 1024
-__device__ __forceinline__ void stage_gt_bv(const float *__restrict__ gt_bv, int G, float *s_gt)
+__device__ __forceinline__ void stage_gt_bv(const float *__restrict__ gt_bv, int G, float *s_gt, const int threads)
 {
-    for (int g = threadIdx.x; g < G; g += blockDim.x)
+    for (int g = threadIdx.x; g < G; g += threads)
 #pragma unroll
         for (int j = 0; j < 4; ++j) s_gt[4 * g + j] = gt_bv[5 * g + j];
 }
+__device__ __forceinline__ void stage_gt_bv(const float *__restrict__ gt_bv, int G, float *s_gt) { stage_gt_bv(gt_bv, G, s_gt, blockDim.x); }
 
 // transform.py:483-500 for one box given its 6 decoded numbers
 __device__ __forceinline__ void image_box(const float M[12], const float P[6], int32_t out[4])

@@ -7,10 +7,13 @@
 // the reference's subsampling draws between their two stages are mv3d_draw_training_subsamples (legacy_rng.hip) on numpy's own
 // generator.  Through round 4 a Python class issued these calls; its ~0.3 ms of interpreter time per batch had become the limit of
 // the path on new inputs (the device needs ~0.15 ms per batch), so the sequence lives here now:
-//   * submit(): stage 1 + one small launch that writes the batch's reports into the pinned host buffers (tp_report_kernel; three
-//     device-to-host copies when those buffers are not mapped into the device) + an event, all on the caller's stream -- one call;
+//   * submit(): stage 1, whose last launch (pt_compact_kernel, one workgroup per frame) also writes the frame's reports into the
+//     pinned host buffers (PtMirror; three device-to-host copies when those buffers are not mapped into the device) + an event, all
+//     on the caller's stream -- one call;
 //   * a helper thread per object: waits for the event, draws (slots strictly in submission order = the reference's order of draws),
-//     uploads the lists, enqueues stage 2 on the same stream.  The caller's thread never touches the draws;
+//     uploads the lists, enqueues stage 2 on the same stream: the disable launch and ONE launch whose workgroups run the anchor
+//     layer's emit + relabel body or the proposal-target layer's emit body (tp_stage2_kernel).  The caller's thread never touches
+//     the draws;
 //   * finish(): waits for "stage 2 enqueued" and reports the row counts.
 // No device memory is owned here: every buffer is the caller's (mv3d_train_path_slot).
 #include <hip/hip_runtime.h>
@@ -21,8 +24,10 @@
 #include <new>
 #include <thread>
 #include <vector>
-#include "common.h"
-#include "../../include/mv3d_hip.h"
+#include "anchor_target.h"
+#include "proposal.h"
+#include "proposal_target.h"
+#include "rank.h"
 
 #define TP_MAX_BATCH 16
 
@@ -63,9 +68,68 @@ static bool tp_force_copies()
 #endif
 }
 
+// ---- Launches of the path's own: two independent bodies side by side in ONE grid ("horizontal fusion") --------------------------------
+// A batch is a chain of dependent launches, most of them 5 - 12 us long and latency-bound, on one of a few hardware queues that each
+// run one kernel at a time; every launch also leaves a gap on its queue.  Where two bodies of the chain read nothing of each other,
+// one grid runs both: workgroups [0, n_at) of a frame (blockIdx.y) run the anchor layer's body, the rest the other body, each with
+// its own numbering (the bodies take their workgroup index and count as arguments: anchor_target.h, proposal.h, rank.h,
+// proposal_target.h).  No arithmetic changes, no workgroup waits for the other body, no cooperative launch.  The workgroup is the
+// larger of the two bodies'; the smaller body's other waves (whole waves: every size is a multiple of 64) return before its first
+// barrier.  A compaction body is the one at the low indices: its look-back waits for workgroups of lower index of the same frame,
+// which are dispatched before it.  The argument blocks hold only what the bodies read (AtStage1Frame, AtEmitFrame, PtEmitFrame):
+// AtBatch + anything else would not fit the 4 KB of kernel arguments.
+//   stage 1:  proposal_decode || at_overlap,  rank_local || at_label,  rank_merge || at_compact   (then the NMS rounds, pt_overlap and
+//             pt_compact, which also writes the reports to the host: PtMirror)
+//   stage 2:  at_disable_all, then at_emit_relabel || pt_emit
+// A configuration on the counting rank path (rank.hip B: key_stride > RANK_LDS_KEYS) keeps the single-purpose launches: tp_plan().
+struct TpAtStage1 { AtStage1Frame f[TP_MAX_BATCH]; int n_agg1, n_agg2; };
+struct TpStage2 {
+    AtEmitFrame at[TP_MAX_BATCH];
+    PtEmitFrame pt[TP_MAX_BATCH];
+    AtEmitGrid g;
+};
+#define TP_KERNARG_BYTES 4096
+static_assert(sizeof(TpAtStage1) + sizeof(ProposalDev) + 2 * sizeof(int) <= TP_KERNARG_BYTES, "kernel arguments: 4 KB");
+static_assert(sizeof(TpAtStage1) + sizeof(RankMergeArgs) + 2 * sizeof(int) <= TP_KERNARG_BYTES, "kernel arguments: 4 KB");
+static_assert(sizeof(TpStage2) + sizeof(int) <= TP_KERNARG_BYTES, "kernel arguments: 4 KB");
+static_assert(TP_MAX_BATCH <= AT_MAX_BATCH && TP_MAX_BATCH <= PT_MAX_BATCH, "batch limits");
+static_assert(DEC_THREADS <= AT_THREADS && DEC_THREADS % MV3D_WAVE == 0 && AT_THREADS % MV3D_WAVE == 0 && PT_EMIT_THREADS <= 256 &&
+              PT_EMIT_THREADS % MV3D_WAVE == 0 && AT_THREADS <= RANK_NSUB * RANK_LK, "the smaller body's threads are whole waves of the workgroup");
+
+__global__ __launch_bounds__(AT_THREADS) void tp_decode_overlap_kernel(TpAtStage1 at, ProposalDev p, int n_at, int n_dec)
+{
+    const int f = blockIdx.y, wg = blockIdx.x;
+    if (wg < n_at) at_overlap_body(at.f[f], at.n_agg1, at.n_agg2, wg);
+    else if (threadIdx.x < DEC_THREADS) proposal_decode_body(p, f, wg - n_at, n_dec);
+}
+
+__global__ __launch_bounds__(RANK_NSUB * RANK_LK) void tp_rank_label_kernel(TpAtStage1 at, RankMergeArgs r, int n_at, int n_rank)
+{
+    const int f = blockIdx.y, wg = blockIdx.x;
+    if (wg >= n_at) rank_local_body(r, f, wg - n_at, n_rank);
+    else if (threadIdx.x < AT_THREADS) at_label_body(at.f[f], wg);
+}
+
+__global__ __launch_bounds__(256) void tp_merge_compact_kernel(TpAtStage1 at, RankMergeArgs r, int n_at)
+{
+    const int f = blockIdx.y, wg = blockIdx.x;
+    if (wg < n_at) at_compact_body(at.f[f], wg, n_at);
+    else rank_merge_body(r, f, wg - n_at);
+}
+
+__global__ __launch_bounds__(256) void tp_stage2_kernel(TpStage2 a, int n_at)
+{
+    const int f = blockIdx.y, wg = blockIdx.x;
+    if (wg < n_at) at_emit_relabel_body(a.at[f], a.g, wg, n_at);
+    else if (threadIdx.x < PT_EMIT_THREADS) pt_emit_body(a.pt[f], wg - n_at);        // (no barrier in that body)
+}
+
+__global__ __launch_bounds__(256) void tp_disable_all_kernel(AtBatch bt) { at_disable_all_body(bt.f[blockIdx.y], blockIdx.x, gridDim.x); }
+
 // A batch's reports -- the head of every frame's anchor report, the proposal-target counts, the proposal counts | status words -- written
 // by ONE small launch straight into the caller's pinned host buffers (16-byte stores over the host link) instead of three copy launches of
-// the runtime (17 us of queue time each with eight batches in flight, profiles/r06_s_kernel_stats.txt: __amd_rocclr_copyBuffer).
+// the runtime (17 us of queue time each with eight batches in flight, profiles/r06_s_kernel_stats.txt: __amd_rocclr_copyBuffer).  The
+// single-purpose sequence's; the paired sequence has pt_compact_kernel write them (PtMirror).
 __global__ __launch_bounds__(256) void tp_report_kernel(const uint8_t *__restrict__ report, size_t report_row, uint8_t *__restrict__ h_report,
                                                         size_t h_row, int B, const int32_t *__restrict__ pt_counts, int32_t *__restrict__ h_pt,
                                                         const int32_t *__restrict__ nump, int32_t *__restrict__ h_nump)
@@ -77,6 +141,22 @@ __global__ __launch_bounds__(256) void tp_report_kernel(const uint8_t *__restric
     }
     for (int i = threadIdx.x; i < 4 * B; i += 256) h_pt[i] = pt_counts[i];
     for (int i = threadIdx.x; i < 2 * B; i += 256) h_nump[i] = nump[i];
+}
+
+// What the path enqueues per batch: the one place that decides between the paired and the single-purpose sequence, and the count of
+// launches either way (mv3d_train_path_launch_plan).  The NMS rounds are the plan mv3d_launch_nms walks (round 1 is two launches);
+// the lists' upload counts as one launch of stage 2, and so does at_disable_all (skipped for a batch with nothing to disable).
+struct TpPlan { bool paired; int stage1, stage2; };
+bool tp_plan(const mv3d_train_path_config &c, TpPlan &pl)
+{
+    ProposalLayout L;
+    if (!proposal_layout(c.batch, c.H, c.W, &c.proposal, L)) return false;
+    int32_t rounds[3 * 8];
+    const int nms = mv3d_nms_round_plan(L.order_cap, L.cap, rounds) + 1;
+    pl.paired = L.key_stride <= RANK_LDS_KEYS;                         // (the argument blocks fit for every batch <= TP_MAX_BATCH: static_assert)
+    pl.stage1 = pl.paired ? 3 + nms + 2 : 3 + nms + 3 + 2 + 1;        // [decode, rank x 2] + NMS + [anchor x 3] + proposal target x 2 + [report]
+    pl.stage2 = pl.paired ? 3 : 4;                                     // upload, disable, [emit + relabel, emit]
+    return true;
 }
 
 }  // namespace
@@ -92,6 +172,7 @@ struct mv3d_train_path {
     std::condition_variable cv_work, cv_done;
     std::deque<int> queue;
     double t_wait = 0.0, t_draw = 0.0;
+    bool paired = false;                                   // tp_plan(): the paired launches, or the single-purpose sequence
 };
 
 namespace {
@@ -105,6 +186,8 @@ bool config_ok(const mv3d_train_path_config &c)
 void set_params(mv3d_train_path *tp, const mv3d_train_path_config &c)
 {
     tp->cfg = c;
+    TpPlan pl;
+    tp->paired = tp_plan(c, pl) && pl.paired;
     for (int b = 0; b < c.batch; ++b) {
         tp->tpar[b] = c.target;
         tp->tpar[b].num_classes = c.num_classes;
@@ -198,9 +281,6 @@ int host_stage(mv3d_train_path *tp, Slot &s)
             cnt[k][b] = s.sizes[5 * b + k];
             lst[k][b] = cnt[k][b] ? lists + off[5 * b + k] : nullptr;
         }
-    rc = mv3d_anchor_target_stage2_batch(B, H, W, &c.anchor, lst[0], cnt[0], lst[1], cnt[1], lst[2], cnt[2], u.rpn_labels, u.anchors,
-                                         u.anchors_3d, u.n_anchors, c.anchor_cap, s.a_ws, u.anchor_ws_bytes, s.stream);
-    if (rc != MV3D_OK) return rc;
     float *o_bev[TP_MAX_BATCH], *o_rgb[TP_MAX_BATCH], *o_fv[TP_MAX_BATCH], *o_3d[TP_MAX_BATCH], *o_tg[TP_MAX_BATCH];
     int32_t *o_lab[TP_MAX_BATCH];
     const float *cal[TP_MAX_BATCH];
@@ -218,9 +298,31 @@ int host_stage(mv3d_train_path *tp, Slot &s)
         cal[b] = s.calib + (size_t)b * 48;
         row += (size_t)S;
     }
-    return mv3d_proposal_target_stage2_batch_devn(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.gt_c, s.G, cal, tp->tpar, lst[3],
-                                                  cnt[3], lst[4], cnt[4], o_bev, o_rgb, o_lab, o_tg, o_3d, u.rois_fv ? o_fv : nullptr, s.p_ws,
-                                                  s.p_wsz, s.stream);
+    if (!tp->paired) {                                                // the single-purpose sequence (tp_plan)
+        rc = mv3d_anchor_target_stage2_batch(B, H, W, &c.anchor, lst[0], cnt[0], lst[1], cnt[1], lst[2], cnt[2], u.rpn_labels, u.anchors,
+                                             u.anchors_3d, u.n_anchors, c.anchor_cap, s.a_ws, u.anchor_ws_bytes, s.stream);
+        if (rc != MV3D_OK) return rc;
+        return mv3d_proposal_target_stage2_batch_devn(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.gt_c, s.G, cal, tp->tpar,
+                                                      lst[3], cnt[3], lst[4], cnt[4], o_bev, o_rgb, o_lab, o_tg, o_3d,
+                                                      u.rois_fv ? o_fv : nullptr, s.p_ws, s.p_wsz, s.stream);
+    }
+    // the two layers' argument blocks, checked and laid out by the functions their own entries use
+    AtBatch at;
+    AtLayout L;
+    PtBatch pt;
+    int most_dis, most_rois;
+    rc = at_stage2_args(B, H, W, &c.anchor, lst[0], cnt[0], lst[1], cnt[1], lst[2], cnt[2], u.rpn_labels, u.anchors, u.anchors_3d, u.n_anchors,
+                        c.anchor_cap, s.a_ws, u.anchor_ws_bytes, at, L, most_dis);
+    if (rc != MV3D_OK) return rc;
+    rc = pt_stage2_args(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.gt_c, s.G, cal, tp->tpar, lst[3], cnt[3], lst[4], cnt[4], o_bev,
+                        o_rgb, o_lab, o_tg, o_3d, u.rois_fv ? o_fv : nullptr, s.p_ws, s.p_wsz, pt, most_rois);
+    if (rc != MV3D_OK) return rc;
+    TpStage2 a;
+    for (int b = 0; b < TP_MAX_BATCH; ++b) { a.at[b] = at_emit_frame(at.f[b]); a.pt[b] = pt_emit_frame(pt.f[b]); }
+    a.g = at_emit_grid(at.f[0], at.cap);
+    if (most_dis > 0) hipLaunchKernelGGL(tp_disable_all_kernel, dim3((most_dis + 255) / 256, B), dim3(256), 0, s.stream, at);
+    hipLaunchKernelGGL(tp_stage2_kernel, dim3(L.ncwg + pt_emit_workgroups(most_rois), B), dim3(256), 0, s.stream, a, L.ncwg);
+    return mv3d_launch_status();
 }
 
 // (the C-ABI promises "no exceptions": an allocation failure of the spill buffer becomes a status)
@@ -231,6 +333,75 @@ int host_stage_noexcept(mv3d_train_path *tp, Slot &s)
     } catch (...) {
         return MV3D_ERR_WORKSPACE;
     }
+}
+
+// Stage 1 of a batch as the single-purpose entries enqueue it, and the reports by a launch of their own
+int stage1_single(mv3d_train_path *tp, Slot &s, const float *prob, const float *pred, const float *im_info, const uint8_t *anchor_mask,
+                  const uint8_t *const *masks)
+{
+    const mv3d_train_path_config &c = tp->cfg;
+    const mv3d_train_path_slot &u = s.buf;
+    const int B = c.batch;
+    int rc = mv3d_proposal_3d_masked(prob, pred, B, c.H, c.W, im_info, s.calib, &c.proposal, anchor_mask, u.blob_bv, u.blob_img, u.blob_3d,
+                                     u.num_proposals, u.num_proposals + B, u.proposal_ws, u.proposal_ws_bytes, s.stream);
+    if (rc != MV3D_OK) return rc;
+    rc = mv3d_anchor_target_stage1_batch_masked(B, c.H, c.W, im_info, s.gt_bv, s.gt_3d, s.G, &c.anchor, masks, u.rpn_labels, u.rpn_targets,
+                                                s.a_cnt, s.a_fgh, s.a_ws, u.anchor_ws_bytes, s.stream);
+    if (rc != MV3D_OK) return rc;
+    rc = mv3d_proposal_target_stage1_batch_devn(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.G, tp->tpar, s.p_cnt, s.p_ws,
+                                                s.p_wsz, s.stream);
+    if (rc != MV3D_OK) return rc;
+    if (s.dv_report) {
+        hipLaunchKernelGGL(tp_report_kernel, dim3(1), dim3(256), 0, s.stream, (const uint8_t *)u.report, (size_t)u.report_row, s.dv_report,
+                           (size_t)u.h_report_row, B, (const int32_t *)u.pt_counts, s.dv_pt_counts, (const int32_t *)u.num_proposals,
+                           s.dv_num_proposals);
+        return mv3d_launch_status();
+    }
+    return MV3D_OK;
+}
+
+// Stage 1 of a batch in the paired launches: the same arguments, checks and workspace layouts as the three entries' (their own
+// functions lay them out), the anchor layer's three bodies inside the proposal layer's first three launches, and the reports
+// written by the last launch
+int stage1_paired(mv3d_train_path *tp, Slot &s, const float *prob, const float *pred, const float *im_info, const uint8_t *anchor_mask,
+                  const uint8_t *const *masks)
+{
+    const mv3d_train_path_config &c = tp->cfg;
+    const mv3d_train_path_slot &u = s.buf;
+    const int B = c.batch;
+    ProposalLayout L;
+    if (!proposal_layout(B, c.H, c.W, &c.proposal, L) || L.key_stride > RANK_LDS_KEYS || c.proposal.feat_stride <= 0) return MV3D_ERR_INVALID_ARG;
+    if (!u.proposal_ws || u.proposal_ws_bytes < L.total || ((uintptr_t)u.proposal_ws % MV3D_ALIGN)) return MV3D_ERR_WORKSPACE;
+    char *ws = (char *)u.proposal_ws;
+    ProposalDev d;
+    NmsLaunch nl;
+    proposal_launch_args(L, prob, pred, B, c.H, c.W, im_info, s.calib, &c.proposal, anchor_mask, u.blob_bv, u.blob_img, u.blob_3d,
+                         u.num_proposals, u.num_proposals + B, ws, d, nl);
+    const RankMergeArgs r = rank_merge_args(d.key, L.N, L.key_stride, B, (int32_t *)nl.emit.order, L.order_cap, d.blockcnt, L.n_blocks,
+                                            (int32_t *)nl.n_dev, ws + L.o_rank, d.bv, (float4 *)nl.boxes);
+    AtBatch at;
+    AtLayout AL;
+    int rc = at_stage1_args(B, c.H, c.W, im_info, s.gt_bv, s.gt_3d, s.G, &c.anchor, masks, u.rpn_labels, u.rpn_targets, s.a_cnt, s.a_fgh, s.a_ws,
+                            u.anchor_ws_bytes, at, AL);
+    if (rc != MV3D_OK) return rc;
+    TpAtStage1 a;
+    for (int b = 0; b < TP_MAX_BATCH; ++b) a.f[b] = at_stage1_frame(at.f[b]);
+    a.n_agg1 = at.n_agg1; a.n_agg2 = at.n_agg2;
+    const int n_rank = L.key_stride / RANK_LK;                        // (= L.n_blocks: both bodies own 128 keys per workgroup)
+    hipLaunchKernelGGL(tp_decode_overlap_kernel, dim3(AL.nblk + L.n_blocks, B), dim3(AT_THREADS), 0, s.stream, a, d, AL.nblk, L.n_blocks);
+    hipLaunchKernelGGL(tp_rank_label_kernel, dim3(AL.nblk + n_rank, B), dim3(RANK_NSUB * RANK_LK), 0, s.stream, a, r, AL.nblk, n_rank);
+    hipLaunchKernelGGL(tp_merge_compact_kernel, dim3(AL.ncwg + n_rank, B), dim3(256), 0, s.stream, a, r, AL.ncwg);
+    if (mv3d_launch_status() != MV3D_OK) return MV3D_ERR_HIP;
+    rc = mv3d_launch_nms(nl, s.stream);
+    if (rc != MV3D_OK) return rc;
+    PtMirror mirror = {};
+    mirror.batch = B;
+    if (s.dv_report) {
+        mirror.report = u.report; mirror.h_report = s.dv_report; mirror.report_row = u.report_row; mirror.h_row = u.h_report_row;
+        mirror.h_pt_counts = s.dv_pt_counts; mirror.num_proposals = u.num_proposals; mirror.h_num_proposals = s.dv_num_proposals;
+    }
+    return mv3d_pt_stage1_batch_mirrored(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.G, tp->tpar, s.p_cnt, s.p_ws, s.p_wsz, mirror,
+                                         s.stream);
 }
 
 void helper_main(mv3d_train_path *tp)
@@ -279,7 +450,7 @@ extern "C" int mv3d_train_path_create(const mv3d_train_path_config *config, int 
         Slot &s = tp->slots[k];
         s.buf = slots[k];
         slot_tables(tp->cfg, s);
-        // the pinned report buffers as the device addresses them (one launch writes the reports); anything unmapped or unaligned: copies
+        // the pinned report buffers as the device addresses them (stage 1's last launch writes the reports); anything unmapped or unaligned: copies
         {
             void *d0 = nullptr, *d1 = nullptr, *d2 = nullptr;
             const bool mapped = hipHostGetDevicePointer(&d0, s.buf.h_report, 0) == hipSuccess && hipHostGetDevicePointer(&d1, s.buf.h_pt_counts, 0) == hipSuccess &&
@@ -350,22 +521,9 @@ extern "C" int mv3d_train_path_submit_masked(mv3d_train_path *tp, int slot, cons
     // anchor_mask (B, N): the frames' empty-anchor masks for the proposal layer and the anchor targets (NULL: every anchor takes part)
     const uint8_t *masks[TP_MAX_BATCH];
     for (int b = 0; b < B; ++b) masks[b] = anchor_mask ? anchor_mask + (size_t)b * 4 * c.H * c.W : nullptr;
-    int rc = mv3d_proposal_3d_masked(prob, pred, B, c.H, c.W, im_info, calib, &c.proposal, anchor_mask, u.blob_bv, u.blob_img, u.blob_3d,
-                                     u.num_proposals, u.num_proposals + B, u.proposal_ws, u.proposal_ws_bytes, stream);
+    int rc = tp->paired ? stage1_paired(tp, s, prob, pred, im_info, anchor_mask, masks) : stage1_single(tp, s, prob, pred, im_info, anchor_mask, masks);
     if (rc != MV3D_OK) return rc;
-    rc = mv3d_anchor_target_stage1_batch_masked(B, c.H, c.W, im_info, s.gt_bv, s.gt_3d, s.G, &c.anchor, masks, u.rpn_labels, u.rpn_targets,
-                                                s.a_cnt, s.a_fgh, s.a_ws, u.anchor_ws_bytes, stream);
-    if (rc != MV3D_OK) return rc;
-    rc = mv3d_proposal_target_stage1_batch_devn(B, s.p_bv, s.p_3d, s.p_cap, s.p_num, s.gt_bv, s.gt_3d, s.G, tp->tpar, s.p_cnt, s.p_ws,
-                                                s.p_wsz, stream);
-    if (rc != MV3D_OK) return rc;
-    // the reports: one launch that writes them into the pinned host buffers (three device-to-host copies when those are not mapped)
-    if (s.dv_report) {
-        hipLaunchKernelGGL(tp_report_kernel, dim3(1), dim3(256), 0, s.stream, (const uint8_t *)u.report, (size_t)u.report_row, s.dv_report,
-                           (size_t)u.h_report_row, B, (const int32_t *)u.pt_counts, s.dv_pt_counts, (const int32_t *)u.num_proposals,
-                           s.dv_num_proposals);
-        if (mv3d_launch_status() != MV3D_OK) return MV3D_ERR_HIP;
-    } else {
+    if (!s.dv_report) {                                               // the reports as three device-to-host copies (buffers not mapped)
         TP_HIP(hipMemcpy2DAsync(u.h_report, u.h_report_row, u.report, u.report_row, u.h_report_row, (size_t)B, hipMemcpyDeviceToHost, s.stream));
         TP_HIP(hipMemcpyAsync(u.h_pt_counts, u.pt_counts, (size_t)B * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
         TP_HIP(hipMemcpyAsync(u.h_num_proposals, u.num_proposals, (size_t)B * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s.stream));
@@ -431,6 +589,15 @@ extern "C" int mv3d_train_path_host_seconds(mv3d_train_path *tp, double *wait_s,
     if (draw_s) *draw_s = tp->t_draw;
     tp->t_wait = tp->t_draw = 0.0;
     return MV3D_OK;
+}
+
+extern "C" int mv3d_train_path_launch_plan(const mv3d_train_path_config *c, int32_t *stage1, int32_t *stage2)
+{
+    TpPlan pl;
+    if (!c || !config_ok(*c) || !tp_plan(*c, pl)) return -1;
+    if (stage1) *stage1 = pl.stage1;
+    if (stage2) *stage2 = pl.stage2;
+    return pl.paired ? 1 : 0;
 }
 
 extern "C" void mv3d_train_path_destroy(mv3d_train_path *tp)
