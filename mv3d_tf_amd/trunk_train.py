@@ -47,7 +47,9 @@ class BufferPool:
     """Framed buffers of a training trunk, kept across steps (their zero frames are written once).  ONE forward / backward pair
     per trunk (tag prefix) may be in flight: the next forward overwrites the activations the backward pass reads -- every forward
     takes a new generation number and a backward pass that finds a newer one raises instead of computing wrong gradients.
-    Per tag at most `max_shapes` buffer shapes stay alive (least recently used first out: KITTI images come in four sizes)."""
+    Per tag at most `max_shapes` buffer shapes stay alive (least recently used first out: KITTI images come in four sizes).
+    The kernels rely on zeros they never write staying zero across steps -- the one-pixel frame, the input layers' padding channels,
+    the row / column an odd-sized VALID pool drops from a pool gradient: tests/test_trunk_train_chain.py holds them under reuse."""
 
     def __init__(self, max_shapes=4):
         self._buf = {}                     # tag -> {shape key: buffer}, insertion order = recency
@@ -179,7 +181,8 @@ class TrunksFunction(torch.autograd.Function):
             if i == 0:
                 break
             c_in = c_ins[0]
-            # two gradient buffers per resolution alternate (dy of layer i is read while dx = dy of layer i - 1 is written)
+            # one gradient buffer per layer and tag (/dx<i>, and /g<i - 1> where a pool sits below): dy of layer i is read while dx = dy
+            # of layer i - 1 is written, and every buffer of a step stays as written until the next forward of this trunk
             obufs = [bufs.get("%s/dx%d" % (tags[v], i), dys[v].shape[0], saved[v][i][2], saved[v][i][3], c_in, dev, dt) for v in range(nv)]
             y_prev = [saved[v][i - 1][1] for v in range(nv)]
             wd = [ctx.packed_dgrad[v][i] for v in range(nv)]

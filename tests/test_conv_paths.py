@@ -19,7 +19,8 @@ Two kinds of operands:
     p = 11 (f16) / 8 (bf16) / no term (f32 out), L = the kernel's real summation length: 9 Cin + 1 for the forward, pixels per K split
     + number of splits for the weight gradient (the split count is read from the workspace size the planner asks for).
 
-The reference is nine shifted float64 GEMMs (rocBLAS dgemm on the device, not MIOpen), a frame chunk at a time.  Every output's
+The reference (tests/conv_float64_reference.py) is nine shifted float64 GEMMs (rocBLAS dgemm on the device, not MIOpen), a frame
+chunk at a time.  Every output's
 interior is NaN before the launch (a skipped tile stays NaN), and its frame must stay zero (the next layer reads it as padding)."""
 import ctypes as C
 import os
@@ -28,6 +29,8 @@ import zlib
 from collections import namedtuple
 
 import pytest
+
+from conv_float64_reference import _bound_check, _conv_ref, _wgrad_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mv3d_tf_amd", "csrc")
@@ -277,34 +280,6 @@ def _dtype(torch, dt):
     return {"f16": torch.float16, "bf16": torch.bfloat16, "f32": torch.float32}[dt]
 
 
-def _chunk(B, per_frame_elems, budget=2 ** 26):
-    return max(1, min(B, budget // max(1, per_frame_elems)))
-
-
-def _conv_ref(torch, xp, w, b, relu=False, gate=None, pool=False, absval=False):
-    """xp (B, H + 2, W + 2, Cin) framed f64 map, w (Cout, Cin, 3, 3) f64, b (Cout) f64 -> yields (b0, y) chunks of the float64
-    result (nb, H, W, Cout) [gated by gate > 0, ReLU, 2x2 VALID max pool]: nine shifted GEMMs per chunk of frames"""
-    B, Hp, Wp, cin = xp.shape
-    H, W, cout = Hp - 2, Wp - 2, w.shape[0]
-    if absval:
-        xp, w, b = xp.abs(), w.abs(), b.abs()
-    step = _chunk(B, H * W * max(cin, cout))
-    for b0 in range(0, B, step):
-        nb = min(step, B - b0)
-        y = b.expand(nb * H * W, cout).clone()
-        for ty in range(3):
-            for tx in range(3):
-                y.addmm_(xp[b0:b0 + nb, ty:ty + H, tx:tx + W].reshape(nb * H * W, cin), w[:, :, ty, tx].t())
-        y = y.view(nb, H, W, cout)
-        if gate is not None:
-            y = torch.where(gate[b0:b0 + nb, 1:-1, 1:-1] > 0, y, torch.zeros_like(y))
-        if relu:
-            y = torch.relu(y)
-        if pool:
-            y = torch.nn.functional.max_pool2d(y.permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)
-        yield b0, y
-
-
 def _nan_output(torch, B, H, W, cout, framed, T):
     """the output buffer: framed = zero frame + NaN interior, bare = all NaN"""
     if framed:
@@ -413,19 +388,6 @@ def test_forward_path_exact_on_integer_operands(gpu, hiplib, c, dt):
         assert big > 2048, big                                  # the sums leave the range a 16-bit accumulator would hold
 
 
-def _bound_check(torch, got, ref, S, L, out_dt, what):
-    p = {"f16": 11, "bf16": 8}.get(out_dt)
-    bound = 1.01 * L * 2.0 ** -24 * S
-    if p is not None:
-        bound = bound + 2.0 ** -p * ref.abs()
-    err = (got.double() - ref).abs()
-    ok = err <= bound
-    if not bool(ok.all()):
-        i = tuple((~ok).nonzero()[0].tolist())
-        raise AssertionError("%s: %d elements beyond the bound, first at %s: got %r, float64 %r, bound %r" % (
-            what, int((~ok).sum()), i, float(got[i]), float(ref[i]), float(bound[i])))
-
-
 @gpu_mark
 @pytest.mark.parametrize("c,dt", _CASE_PARAMS)
 def test_forward_path_within_float64_bound_on_random_operands(gpu, hiplib, c, dt):
@@ -496,23 +458,6 @@ WCASES = [
     WCase("views_bf16", "bf16", [(2, 152, 152), (2, 94, 311), (2, 16, 128)], 128, 128, None, False),
     WCase("views_f32_input", "f32", [(1, 304, 304), (1, 96, 320), (1, 64, 512)], 64, 64, [9, 3, 3], False),
 ]
-
-
-def _wgrad_ref(torch, xp, dyp, absval=False):
-    """float64 dW (Cout, Cin, 3, 3) = sum over pixels of dy x x_shift(tap), db = sum dy"""
-    B, Hp, Wp, cin = xp.shape
-    H, W, cout = Hp - 2, Wp - 2, dyp.shape[3]
-    if absval:
-        xp, dyp = xp.abs(), dyp.abs()
-    dw = torch.zeros((cout, cin, 3, 3), dtype=torch.float64, device="cuda")
-    step = _chunk(B, H * W * max(cin, cout))
-    for b0 in range(0, B, step):
-        nb = min(step, B - b0)
-        d = dyp[b0:b0 + nb, 1:-1, 1:-1].reshape(nb * H * W, cout)
-        for ty in range(3):
-            for tx in range(3):
-                dw[:, :, ty, tx] += d.t() @ xp[b0:b0 + nb, ty:ty + H, tx:tx + W].reshape(nb * H * W, cin)
-    return dw, dyp.sum((0, 1, 2))
 
 
 def _plan(views, cin, cout, dt):
