@@ -1016,6 +1016,56 @@ int mv3d_adam_step(const mv3d_adam_tensor *tensors_dev, const int32_t *chunk_ten
                    double lr, double beta1, double beta2, double eps, int step, int lowp_dtype /* of param_lowp: 0 none, 1 f16, 2 bf16 */,
                    void *stream);
 
+/* ------------------------------------------------------------------ the training solver (csrc/solver.hip, csrc/adam.hip)
+ * New here (the reference leaves its MomentumOptimizer, exponential_decay and WEIGHT_DECAY commented out or unread:
+ * lib/fast_rcnn/train_mv.py:138-146, lib/fast_rcnn/config.py:38-40): the global gradient norm with a clip coefficient and a
+ * non-finite guard that stay on the device, a momentum-SGD step and the Adam step above under the same control.  The chunk tables
+ * are those of mv3d_adam_step (mv3d_adam_chunk_elements() elements per chunk).  DESIGN.md section 3.28.
+ *
+ * mv3d_grad_norm: sumsq = sum over every element of every tensor of (double)g * (double)g -- each square exact in f64, the sum in f64
+ * in an order that is a function of the tensors' sizes alone (element i of a chunk always goes to the same thread and the same place
+ * in its chain, the threads, waves, chunks' partials are reduced in fixed trees; no floating-point atomics), so neither addresses,
+ * alignment nor scheduling move a bit of it.  Two launches: one workgroup per chunk writes partials_dev[chunk], one workgroup of
+ * MV3D_GRAD_NORM_FINISH_THREADS reduces them and writes *control_dev:
+ *   norm = (float)sqrt(sumsq);  skip = guard && !isfinite(sumsq);
+ *   coef = 0 under skip, else 1 if max_norm == 0, else c = max_norm / (sqrt(sumsq) + 1e-6) in f64, coef = c >= 1 ? 1 : (float)c
+ *          (torch.nn.utils.clip_grad_norm_'s rule);  skipped_total += skip;  calls_total += 1.
+ * num_chunks == 0 writes sumsq 0, coef 1, skip 0.  The caller owns the record, zeroes it once and need never read it: the update
+ * launches read coef and skip from the device.
+ *
+ * mv3d_sgd_step: per element, f32, g' = coef * g (not evaluated when coef == 1 or control_dev is NULL); g' += weight_decay * p (not
+ * evaluated when the tensor's weight_decay == 0);  buf = momentum * buf + g';  p -= lr * buf -- torch.optim.SGD's and TensorFlow's
+ * MomentumOptimizer's rule (state0 = the momentum buffer, state1 unused).  Under control_dev->skip nothing is written.
+ *
+ * mv3d_adam_step_ctl: mv3d_adam_step with g replaced by the same g' (state0 = exp_avg, state1 = exp_avg_sq), nothing written under
+ * skip.  `step` lives on the host and the host never reads the flag back, so a skipped step still counts as a step for the bias
+ * corrections.  With coef == 1, every weight_decay == 0 and skip == 0 the result equals mv3d_adam_step's bit for bit. */
+typedef struct {
+    float *param;
+    const float *grad;
+    float *state0, *state1;      /* SGD: momentum buffer, NULL;  Adam: exp_avg, exp_avg_sq */
+    long long numel;
+    void *param_lowp;            /* as mv3d_adam_tensor.param_lowp */
+    float weight_decay;          /* L2 decay of this tensor, added to the gradient; 0 = none */
+    int32_t reserved0;
+} mv3d_solver_tensor;
+typedef struct {
+    double sumsq;                /* the squared global gradient norm of the last mv3d_grad_norm */
+    float norm, coef;
+    int32_t skip;                /* 1: the last norm was non-finite under `guard`; the update launches write nothing */
+    int32_t skipped_total, calls_total;
+    int32_t reserved0;
+} mv3d_step_control;
+#define MV3D_GRAD_NORM_FINISH_THREADS 1024
+int mv3d_grad_norm(const mv3d_solver_tensor *tensors_dev, const int32_t *chunk_tensor_dev, const int32_t *chunk_first_dev, int num_chunks,
+                   double max_norm /* 0 = no clipping */, int guard, double *partials_dev /* [num_chunks] */,
+                   mv3d_step_control *control_dev, void *stream);
+int mv3d_sgd_step(const mv3d_solver_tensor *tensors_dev, const int32_t *chunk_tensor_dev, const int32_t *chunk_first_dev, int num_chunks,
+                  double lr, double momentum, const mv3d_step_control *control_dev /* may be NULL */, int lowp_dtype, void *stream);
+int mv3d_adam_step_ctl(const mv3d_solver_tensor *tensors_dev, const int32_t *chunk_tensor_dev, const int32_t *chunk_first_dev,
+                       int num_chunks, double lr, double beta1, double beta2, double eps, int step,
+                       const mv3d_step_control *control_dev /* may be NULL */, int lowp_dtype, void *stream);
+
 /* ------------------------------------------------------------------ KITTI evaluation (csrc/kitti_eval.hip)
  * Bird's-eye-view and 3D average precision of LIDAR-corner detections over a whole split (new here: the reference writes
  * result files for the KITTI devkit binary, lib/datasets/kitti_mv3d.py:321-352, and never runs it).  Frames are CSR ranges:

@@ -118,6 +118,18 @@ class AdamTensor(C.Structure):
                 ("param_lowp", C.c_void_p)]
 
 
+class SolverTensor(C.Structure):
+    """mv3d_solver_tensor"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state0", C.c_void_p), ("state1", C.c_void_p), ("numel", C.c_longlong),
+                ("param_lowp", C.c_void_p), ("weight_decay", C.c_float), ("reserved0", C.c_int32)]
+
+
+class StepControl(C.Structure):
+    """mv3d_step_control"""
+    _fields_ = [("sumsq", C.c_double), ("norm", C.c_float), ("coef", C.c_float), ("skip", C.c_int32), ("skipped_total", C.c_int32),
+                ("calls_total", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class KittiSplit(C.Structure):
     """mv3d_kitti_split"""
     _fields_ = [("num_frames", C.c_int32), ("num_dets", C.c_int32), ("num_gts", C.c_int32), ("img_height", C.c_int32),
@@ -290,6 +302,9 @@ _SIGS = {
     "mv3d_softmax_rows": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P]),
     "mv3d_adam_chunk_elements": (C.c_int, []),
     "mv3d_adam_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, _P]),
+    "mv3d_grad_norm": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_int, _P, _P, _P]),
+    "mv3d_sgd_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, _P, C.c_int, _P]),
+    "mv3d_adam_step_ctl": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P]),
     "mv3d_kitti_eval_overlaps": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, _P]),
     "mv3d_kitti_eval_match": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P]),
     "mv3d_kitti_eval_count": (C.c_int, [C.POINTER(KittiSplit), C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),

@@ -72,7 +72,21 @@ cfg.TRAIN = _section(
     # claim.  On without LIDAR_BV_FROM_SCAN, or with a scale bound <= 0, prepare_roidb raises ValueError (ops.scan_augment).
     # False = every blob, launch and RNG stream as before.
     SCAN_AUGMENT=False, SCAN_AUGMENT_ROTATION=0.17453292519943295, SCAN_AUGMENT_SCALE=(0.95, 1.05),
-    SCAN_AUGMENT_SHIFT=(0.0, 0.0, 0.0))
+    SCAN_AUGMENT_SHIFT=(0.0, 0.0, 0.0),
+    # (not in the reference, whose one live solver line is AdamOptimizer(1e-5): its MomentumOptimizer, exponential_decay and WEIGHT_DECAY
+    # sit commented out or unread, lib/fast_rcnn/train_mv.py:138-146, config.py:38-40) SOLVER: 'reference' = that line, Adam at
+    # SolverWrapper.LEARNING_RATE, a constant rate, none of the keys below read; 'adam' or 'sgd' = optim.Adam / optim.SGD at the rate
+    # optim.learning_rate(it) = LEARNING_RATE * GAMMA ** (it // STEPSIZE), times min(1, (it + 1) / WARMUP_ITERS) when WARMUP_ITERS > 0,
+    # set before every step.  MOMENTUM: 'sgd' only (torch.optim.SGD's and TensorFlow's rule buf = momentum buf + g, p -= lr buf).
+    # WEIGHT_DECAY: L2 decay added to the gradient of every tensor with ndim >= 2 (weights; biases get none).  Anything else in SOLVER
+    # raises ValueError at the top of train_model.
+    SOLVER='reference', MOMENTUM=0.9, WEIGHT_DECAY=0.0, GAMMA=0.1, STEPSIZE=50000, WARMUP_ITERS=0,
+    # ('adam' / 'sgd' only) CLIP_GRAD_NORM: the global L2 norm the averaged gradients are scaled down to before the update
+    # (torch.nn.utils.clip_grad_norm_'s rule; 0 = off).  SKIP_NON_FINITE: a step whose global gradient norm is inf or NaN changes no
+    # weight and no optimizer buffer (it still counts as an iteration, and as a step of Adam's bias corrections).  Norm, coefficient
+    # and flag stay on the device (ops of csrc/solver.hip); they are read and logged on DISPLAY steps only.
+    # The paper's recipe is SOLVER='sgd', LEARNING_RATE=0.001, STEPSIZE=100000, GAMMA=0.1; nothing here can validate it: no accuracy claim.
+    CLIP_GRAD_NORM=0.0, SKIP_NON_FINITE=False)
 cfg.TEST = _section(
     NMS=0.5, HAS_RPN=True, RPN_NMS_THRESH=0.7, RPN_PRE_NMS_TOP_N=12000, RPN_POST_NMS_TOP_N=2000, RPN_MIN_SIZE=5,
     DEBUG_TIMELINE=False,

@@ -198,6 +198,7 @@ class SolverWrapper(object):
     """lib/fast_rcnn/train_mv.py:26-219.  `sess` and `saver` are accepted for signature compatibility and ignored."""
 
     LEARNING_RATE = 0.00001                                   # train_mv.py:143
+    SOLVERS = ('reference', 'adam', 'sgd')                    # cfg.TRAIN.SOLVER
 
     def __init__(self, sess, saver, network, imdb, roidb, output_dir, pretrained_model=None):
         self.net, self.imdb, self.roidb = network, imdb, roidb
@@ -218,7 +219,7 @@ class SolverWrapper(object):
             np.save(f, {name: {'weights': _tf_layout(w), 'biases': b.detach().cpu().numpy()}
                         for name, (w, b) in self.net.params.items()}, allow_pickle=True)
         if self.optimizer is not None:
-            state = {'iter': iter + 1, 'optimizer': self.optimizer.state_dict()}
+            state = {'iter': iter + 1, 'optimizer': self.optimizer.state_dict(), 'solver': cfg.TRAIN.get('SOLVER', 'reference')}
             if getattr(self.net, "drop_path_rng", None) is not None:
                 state['drop_path_rng'] = rng_state_plain(self.net.drop_path_rng)
             torch.save(state, filename + '.optim.pt')
@@ -229,8 +230,15 @@ class SolverWrapper(object):
         """Network training loop (:87-219).  Returns the list of per-iteration loss tuples
         (total, rpn_loss_cls, rpn_loss_box, loss_cls, loss_box).  `resume` = a snapshot written by snapshot(): its weights are
         loaded, and -- when the `<snapshot>.optim.pt` written next to it exists -- the Adam state and the iteration counter, so
-        that training continues where it stopped (the reference can only restart from weights)."""
+        that training continues where it stopped (the reference can only restart from weights).
+
+        cfg.TRAIN.SOLVER: 'reference' is the loop above; 'adam' / 'sgd' run optim.Adam / optim.SGD at the
+        scheduled rate optim.learning_rate(it), weight decay on the tensors with ndim >= 2, and the global-norm clip and non-finite
+        guard of cfg.TRAIN.CLIP_GRAD_NORM / SKIP_NON_FINITE on the averaged gradients, every rank for itself."""
         from .. import sharding
+        solver = cfg.TRAIN.get('SOLVER', 'reference')
+        if solver not in self.SOLVERS:
+            raise ValueError("cfg.TRAIN.SOLVER must be one of %r, got %r" % (self.SOLVERS, solver))
         dist = _dist()
         rank = dist.get_rank() if dist is not None else 0
         world = dist.get_world_size() if dist is not None else 1
@@ -256,14 +264,29 @@ class SolverWrapper(object):
         lr = self.LEARNING_RATE
         # tf.train.AdamOptimizer(lr) defaults: beta 0.9 / 0.999, eps 1e-8.  fused: ONE launch over all parameters on the device
         # (the foreach form is seven launches and 4 ms of a step for the 214 M parameters of the 3-view graph); same update rule
+        from .. import optim
         from ..optim import Adam                                      # (torch.optim.Adam whose step is ONE launch of mv3d_adam_step)
-        self.optimizer = Adam(params, lr=lr) if all(p.is_cuda for p in params) else torch.optim.Adam(params, lr=lr)
+        T = cfg.TRAIN
+        watched = solver != 'reference' and (T.CLIP_GRAD_NORM > 0 or T.SKIP_NON_FINITE)     # the `grad norm:` line of DISPLAY steps
+        if solver == 'reference':
+            self.optimizer = Adam(params, lr=lr) if all(p.is_cuda for p in params) else torch.optim.Adam(params, lr=lr)
+        else:
+            # two groups: the weights (ndim >= 2) decay, the biases do not.  The classes take host parameters too (their host path)
+            lr = optim.learning_rate(start_iter)
+            groups = [{"params": [p for p in params if p.ndim >= 2], "weight_decay": float(T.WEIGHT_DECAY)},
+                      {"params": [p for p in params if p.ndim < 2], "weight_decay": 0.0}]
+            groups = [g for g in groups if g["params"]]
+            kw = dict(lr=lr, clip_grad_norm=float(T.CLIP_GRAD_NORM), skip_non_finite=bool(T.SKIP_NON_FINITE))
+            self.optimizer = optim.SGD(groups, momentum=float(T.MOMENTUM), **kw) if solver == 'sgd' else Adam(groups, **kw)
         if hasattr(self.net, "attach_optimizer"):
             self.net.attach_optimizer(self.optimizer)
         if resume is not None:
             self.net.load(resume, sess, self.saver, False)
             if os.path.exists(resume + '.optim.pt'):
                 state = torch.load(resume + '.optim.pt', map_location=params[0].device)
+                if state.get('solver', 'reference') != solver:
+                    raise ValueError("%s holds the optimizer state of cfg.TRAIN.SOLVER = %r; this run has SOLVER = %r"
+                                     % (resume + '.optim.pt', state.get('solver', 'reference'), solver))
                 self.optimizer.load_state_dict(state['optimizer'])
                 start_iter = int(state['iter'])
                 if 'drop_path_rng' in state and getattr(self.net, "drop_path_rng", None) is not None:
@@ -296,7 +319,11 @@ class SolverWrapper(object):
                 if "ignored" in layers and (it + 1) % cfg.TRAIN.DISPLAY == 0:             # (cfg.TRAIN.IGNORE_TYPES; read on display steps only)
                     ignored = ignored + layers["ignored"].sum(0).cpu().numpy()
             bucketer.finish()
-            self.optimizer.step()
+            if solver != 'reference':                            # the schedule is a function of `it` alone: nothing to store, nothing to resume
+                lr = optim.learning_rate(it)
+                for group in self.optimizer.param_groups:
+                    group["lr"] = lr
+            self.optimizer.step()                                # ('adam' / 'sgd': the norm of the AVERAGED gradients, every rank for itself)
             if torch.cuda.is_available():
                 torch.cuda.synchronize()
             spent += time.perf_counter() - t0
@@ -312,6 +339,9 @@ class SolverWrapper(object):
                          % (it + 1, max_iters, history[-1][0], rpn_loss_cls, rpn_loss_box, loss_cls, loss_box, lr))
                 if cfg.TRAIN.get('IGNORE_TYPES', ()):
                     self.log('ignored: %d anchors, %d rois' % (ignored[0], ignored[1]))
+                if watched:                                      # the one read-back of the control record, on DISPLAY steps only
+                    c = self.optimizer.control()
+                    self.log('grad norm: %.4f, clip: %.4f, skipped: %d' % (c["norm"], c["coef"], c["skipped_total"]))
                 self.log('speed: {:.3f}s / iter'.format(spent / (it + 1 - start_iter)))
             if (it + 1) % cfg.TRAIN.SNAPSHOT_ITERS == 0:
                 last_snapshot_iter = it
